@@ -35,8 +35,21 @@ tests/test_gpu_timed_config.py holds those same steps to the oracle):
 `--global-draws G` fixes the total for any config.  Inputs are resident in HBM before the timed region.
 
 Timing: `value` comes from EXACTLY --steps steps between barrier + synchronize
-on both sides (max over ranks).  Independently of --steps, `timing` reports
-median / p10 / p90 per step over >= 100 steps and >= 2 s.
+on both sides (max over ranks), after the un-timed setup steps and --warmup.
+
+A plain run does only that: set up, warm up, time the --steps steps, print the
+line (`roofline`, `cpu_baseline` null; `configs_ms` holds the timed config only).
+`--full` adds everything else: the same W + K timed once before the setup steps
+(`value_after_contract_warmup_only`), `timing` (median / p10 / p90 per step over
+>= 100 steps and >= 2 s, SURVEY.md 8d, independently of --steps), the per-kernel
+figures of `roofline`, the `extras` legs (C2, one GPU), the CPU baseline, and the
+full record in a side file; --no-stats / --no-extras / --no-cpu-baseline drop
+parts of it.
+
+`--dump-outputs DIR`: after the timed steps, what the last of them computed --
+the arrays the caller of the step receives -- goes to DIR/<name>.npy (float64;
+dump_outputs below).  The inputs are seeded: the same arguments give the same
+inputs on every run, so two builds can be compared output for output.
 """
 import argparse
 import ctypes
@@ -1003,6 +1016,39 @@ def write_full_record(out):
         out["full_record"] = None
 
 
+DUMP_LIMIT = 64 << 20           # bytes of everything --dump-outputs writes
+DUMP_ARRAY_LIMIT = 32 << 20     # an output larger than this is written as a seeded sample of its rows
+DUMP_SEED = 0
+# the outputs of a Workload's step in front of its leaf gradients, by `grads_from`: the dense flux and sum(gbar * flux) per
+# draw (C2, C4), or the log-likelihood per draw (C3, C5)
+DUMP_HEAD = {2: ("flux", "flux_dot_gbar"), 1: ("loglike",)}
+
+
+def dump_outputs(d, wl, outputs, suffix=""):
+    """what the step computed (`outputs`: the tuple `wl.fn` returns) -> d/<name><suffix>.npy, float64: the outputs of
+    DUMP_HEAD, then the gradient of every leaf as `grad_<leaf>`.  An output over DUMP_ARRAY_LIMIT (the dense flux array) is
+    written as the whole rows of a fixed, seeded sample of draws, their indices beside it as <name>_rows<suffix>.npy."""
+    names = list(DUMP_HEAD[wl.grads_from]) + ["grad_" + n for n in wl.names]
+    if len(names) != len(outputs):
+        raise RuntimeError(f"--dump-outputs: {len(outputs)} outputs, {len(names)} names")
+    os.makedirs(d, exist_ok=True)
+    arrays = {}
+    for name, x in zip(names, outputs):
+        x = x.detach()
+        if x.numel() * x.element_size() > DUMP_ARRAY_LIMIT:
+            row_bytes = x.numel() // x.shape[0] * x.element_size()
+            k = min(x.shape[0], max(1, DUMP_ARRAY_LIMIT // row_bytes))
+            rows = np.sort(np.random.default_rng(DUMP_SEED).choice(x.shape[0], size=k, replace=False))
+            arrays[name + "_rows"] = rows.astype(np.float64)
+            x = x[torch.as_tensor(rows, device=x.device)]
+        arrays[name] = x.to(torch.float64).cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT:
+        raise RuntimeError(f"--dump-outputs: {total} bytes over the limit of {DUMP_LIMIT}")
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + suffix + ".npy"), a)
+
+
 def launcher_argv(n_gpus, argv):
     """The command `python bench.py --gpus N ...` turns itself into when it was not started by a launcher."""
     import socket
@@ -1026,10 +1072,15 @@ def main():
                          "as BASELINE.json states them over 8 GPUs")
     ap.add_argument("--c5-bright", type=int, default=0, help="profiling aid (--config c5): that many chains at a conditioning score of 1e6 "
                     "(workload_c5); not a BASELINE configuration")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the cold W + K, the >= 2 s timing loop, per-kernel / roofline figures, the extras "
+                         "legs, the CPU baseline and the full record (module docstring)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
     ap.add_argument("--no-graph", action="store_true", help="launch the step eagerly instead of replaying a hipGraph")
-    ap.add_argument("--no-extras", action="store_true")
-    ap.add_argument("--no-stats", action="store_true", help="skip the >= 100 steps / >= 2 s median / p10 / p90 loop")
+    ap.add_argument("--no-extras", action="store_true", help="(--full) skip the extras legs")
+    ap.add_argument("--no-stats", action="store_true", help="(--full) skip the >= 100 steps / >= 2 s median / p10 / p90 loop")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -1078,7 +1129,7 @@ def main():
         D, n_global, scaling = hi - lo, global_draws, "strong"
     else:
         D, n_global, scaling = args.draws_per_gpu, world * args.draws_per_gpu, "weak"
-    events = HipEvents(max(args.steps, 20))
+    events = HipEvents(max(args.steps, 20)) if args.full else None
     wl = WORKLOADS[cfg](xo, ops, dev, D, rank, **({"bright": args.c5_bright} if cfg == "c5" and args.c5_bright else {}))
     leaves = dict(zip(wl.names, wl.leaves))
     N = wl.n_cad
@@ -1092,24 +1143,40 @@ def main():
     if not args.no_graph:
         graph = xo.GraphedStep(wl.fn, *wl.leaves)
 
-    run, drain = make_runner(graph if graph is not None else (lambda: wl.fn(*wl.leaves)), wl.scalar_index, exchange, consume)
+    # (the graph's static outputs hold the last replay's results; eager steps keep their last outputs only for --dump-outputs)
+    last = [None]
+
+    def eager_step():
+        out = wl.fn(*wl.leaves)
+        if args.dump_outputs:
+            last[0] = out
+        return out
+
+    run, drain = make_runner(graph if graph is not None else eager_step, wl.scalar_index, exchange, consume)
 
     # setup, outside the contract's W + K steps: bring clocks, caches and the allocator to the state a sampler runs
     # in (a few hundred steps, ~0.1 s; the same count on every rank)
     SETUP_STEPS = 300 if cfg in ("c2", "c4") else 30
-    # (the contract's W + K with NOTHING in front first -- reported beside `value` as
+    # (--full: the contract's W + K with NOTHING in front first -- reported beside `value` as
     # `value_after_contract_warmup_only` -- then the setup steps, then the W + K that `value` is)
-    wall_cold = time_steps(run, args.steps, args.warmup, dist, dev, drain=drain if exchange is not None else None)
+    wall_cold = None
+    if args.full:
+        wall_cold = time_steps(run, args.steps, args.warmup, dist, dev, drain=drain if exchange is not None else None)
     for _ in range(SETUP_STEPS):
         run(-1)
     torch.cuda.synchronize(dev)
     wall = time_steps(run, args.steps, args.warmup, dist, dev, drain=drain if exchange is not None else None)
-    wall_t = torch.tensor([wall, wall_cold], dtype=torch.float64, device=dev)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, wl, graph.outputs if graph is not None else last[0],
+                     "" if world == 1 else f".rank{rank}")
+        last[0] = None
+    wall_t = torch.tensor([wall, wall_cold or 0.0], dtype=torch.float64, device=dev)
     if dist is not None:
         dist.all_reduce(wall_t, op=dist.ReduceOp.MAX)
-    wall, wall_cold = float(wall_t[0].item()), float(wall_t[1].item())
+    wall = float(wall_t[0].item())
+    wall_cold = float(wall_t[1].item()) if wall_cold is not None else None
     timing = None
-    if not args.no_stats:
+    if args.full and not args.no_stats:
         # >= 100 steps and >= 2 s, whatever --steps was; the count follows from the
         # max-over-ranks step time above, so it is the same on every rank
         n_stat = int(min(6000, max(100, np.ceil(2.0 / max(wall / args.steps, 1e-6)))))
@@ -1120,7 +1187,7 @@ def main():
 
     light_curve_only = cfg in ("c2", "c4")
     kernel_ms = per_launch = n_active = None
-    if light_curve_only:
+    if args.full and light_curve_only:
         # hipEvents cannot bracket a node inside a replayed graph: time the kernels of the sweep over
         # directly launched steps on the same inputs (events recorded by the C ABI on the launch stream)
         n_ev = len(events.pairs)
@@ -1135,7 +1202,7 @@ def main():
                                        omega=leaves["omega"])
             rec0, ld0, _, flags0 = orbit0.kernel_inputs(leaves["r"], (leaves["u1"], leaves["u2"]), use_in_transit=False)
             n_active = ops.transit_flux_sparse(t_dev, rec0.detach(), ld0.detach(), flags=flags0).n_solved()
-    else:
+    elif args.full:
         # GP configs: the step is a chain of ~20 kernels; the whole replayed step is timed with events on the stream it
         # is replayed on (per-kernel averages and counters: profiles/r06_*)
         q = time_events(lambda: run(-1), dev, 20)
@@ -1146,7 +1213,7 @@ def main():
     if rank == 0:
         evals = n_global * args.steps
         survey_bytes = wl.survey_bytes_per_unit * D * N
-        counters = load_counters()
+        counters = load_counters() if args.full else None
         out = {
             "metric": "light-curve evals/sec (value+grad) at 150k cadences" if cfg == "c2" else
                       f"evals/sec (value+grad) of BASELINE config {cfg.upper()} ({N} cadences)",
@@ -1156,7 +1223,7 @@ def main():
             "steps": args.steps,
             "warmup": args.warmup,
             "setup_steps_before_warmup": SETUP_STEPS,
-            "value_after_contract_warmup_only": evals / wall_cold,
+            "value_after_contract_warmup_only": evals / wall_cold if wall_cold is not None else None,
             "ms_per_step": 1e3 * wall / args.steps,
             "higher_is_better": True,
             "scaling": scaling,
@@ -1176,7 +1243,9 @@ def main():
             },
             "timing": timing,
         }
-        if light_curve_only:
+        if not args.full:
+            out["roofline"] = None
+        elif light_curve_only:
             # bytes this design must move per sweep: the dense flux array once (zeros); for every solved
             # cadence t and gbar in, its flux out to the run-ordered value array, back in and out to its
             # place in the flux array (the binary searches of the windows are a few MB)
@@ -1259,7 +1328,7 @@ def main():
 
     # the extra legs are single-GPU diagnostics: under torch.distributed.run they would only add
     # barriers that every rank has to reach (an exception on one rank would hang the others)
-    if not args.no_extras and world == 1 and dist is None and cfg == "c2":
+    if args.full and not args.no_extras and world == 1 and dist is None and cfg == "c2":
         extras = {}
         t, gbar = wl.data["t"], wl.data["gbar"]
 
@@ -1429,7 +1498,7 @@ def main():
             out["extras"] = extras
 
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(config=cfg)
         else:
             out["cpu_baseline"] = None
@@ -1455,6 +1524,8 @@ def main():
                                   if isinstance(ex.get("ops"), dict) and "quad_solution_vector_with_derivs" in ex["ops"] else None),
             "note": "ms per value + gradient step, one MI355X, hipGraph replay; c2 / sparse / chi2 at 1024 draws x 150000 cadences",
         }
+        if not args.full:           # (the other configs are extras legs)
+            out["configs_ms"] = {cfg: out["configs_ms"][cfg]}
     if dist is not None:
         dist.destroy_process_group()
     if rank == 0:
@@ -1464,9 +1535,10 @@ def main():
             ctypes.CDLL(None).fflush(None)
         except Exception:
             pass
-        # The full record (extras, every CPU leg, definitions) goes to a side file and to stderr; the LAST line of stdout is the
+        # --full: the full record (extras, every CPU leg, definitions) goes to a side file; the LAST line of stdout is the
         # compact contract line only (a 20.8 KB line was not parsed by the driver)
-        write_full_record(out)
+        if args.full:
+            write_full_record(out)
         print(json.dumps(compact_line(out)), flush=True)
 
 

@@ -83,3 +83,35 @@ def test_compact_line_without_optional_blocks():
     line = bench.compact_line(full)
     assert line["cpu_baseline"] is None and line["roofline"]["traffic"] is None
     assert len(json.dumps(line)) < bench.COMPACT_LIMIT
+
+
+def test_dump_outputs_names_sample_and_limit(tmp_path):
+    """--dump-outputs on stand-in outputs of a C2-shaped step: one float64 file per output, named after what it is; the dense
+    flux array as whole rows of a seeded sample of draws (the same rows every time), the indices beside it; under 64 MB"""
+    import numpy as np
+    import torch
+
+    import bench
+
+    class Wl:
+        grads_from, names = 2, ["period", "u1"]
+
+    D, N = 64, 150_000
+    g = torch.Generator().manual_seed(1)
+    outs = (torch.randn(D, N, dtype=torch.float64, generator=g), torch.randn(D, dtype=torch.float64, generator=g),
+            torch.randn(D, 1, dtype=torch.float64, generator=g), torch.randn(D, dtype=torch.float64, generator=g))
+    bench.dump_outputs(str(tmp_path / "a"), Wl, outs)
+    bench.dump_outputs(str(tmp_path / "b"), Wl, outs)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["flux.npy", "flux_dot_gbar.npy", "flux_rows.npy", "grad_period.npy", "grad_u1.npy"]
+    load = lambda d, f: np.load(tmp_path / d / f)  # noqa: E731
+    assert all(load("a", f).dtype == np.float64 for f in files)
+    assert sum((tmp_path / "a" / f).stat().st_size for f in files) <= bench.DUMP_LIMIT
+    rows = load("a", "flux_rows.npy").astype(np.int64)
+    assert 0 < rows.size < D and np.all(np.diff(rows) > 0)
+    assert np.array_equal(load("a", "flux.npy"), outs[0].numpy()[rows])
+    for f, x in (("flux_dot_gbar.npy", outs[1]), ("grad_period.npy", outs[2]), ("grad_u1.npy", outs[3])):
+        assert np.array_equal(load("a", f), x.numpy())
+    assert all(np.array_equal(load("a", f), load("b", f)) for f in files)
+    with pytest.raises(RuntimeError):
+        bench.dump_outputs(str(tmp_path / "c"), Wl, outs[:3])

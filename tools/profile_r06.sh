@@ -37,16 +37,16 @@ for leg in c2 c3 c4 c5 c5b j8 j10 sparse chi2 kepler quadsv; do
     rocprofv3 --pmc $c --kernel-trace --output-format csv -d $d -o p -- ${CMD[$leg]} > /dev/null 2>&1
   done
 done
-python $R/bench.py --steps 5 --no-extras --no-cpu-baseline --no-stats > $out/bench_pre.json 2> /dev/null
+python $R/bench.py --full --steps 5 --no-extras --no-cpu-baseline --no-stats > $out/bench_pre.json 2> /dev/null
 python $R/tools/make_profile_r06.py $out $R/profiles
 # gpurun merges at most 64 MiB of gpurun_out back: keep the summaries (and the kernel-stats tables), drop the raw traces
 mkdir -p $out/profiles && cp $R/profiles/r06_* $out/profiles/
 for leg in c2 c3 c4 c5 c5b j8 j10 sparse chi2 kepler quadsv; do cp $(find $out/${leg}_trace -name "*kernel_stats.csv" | head -1) $out/profiles/r06_${leg}_kernel_stats.csv 2>/dev/null; done
 rm -rf $out/*_trace $out/*_pmc_*
 # the un-profiled bench line last, with this record's counters in place (roofline.traffic / .valu filled in from it)
-python $R/bench.py > $out/bench.json 2> $out/bench.err
+python $R/bench.py --full > $out/bench.json 2> $out/bench.err
 cp $R/gpurun_out/bench_full.json $out/profiles/r06_bench_full.json 2>/dev/null
 tail -1 $out/bench.json > $out/profiles/r06_bench.json
-python $R/bench.py --config c4 --global-draws 64 --steps 50 --no-cpu-baseline > $out/bench_c4_64.json 2> /dev/null
-python $R/bench.py --config c5 --global-draws 128 --steps 20 --no-cpu-baseline > $out/bench_c5_128.json 2> /dev/null
-python $R/bench.py --config c3 --steps 20 --no-cpu-baseline > $out/bench_c3.json 2> /dev/null
+python $R/bench.py --full --config c4 --global-draws 64 --steps 50 --no-cpu-baseline > $out/bench_c4_64.json 2> /dev/null
+python $R/bench.py --full --config c5 --global-draws 128 --steps 20 --no-cpu-baseline > $out/bench_c5_128.json 2> /dev/null
+python $R/bench.py --full --config c3 --steps 20 --no-cpu-baseline > $out/bench_c3.json 2> /dev/null
