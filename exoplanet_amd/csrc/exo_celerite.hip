@@ -35,6 +35,8 @@
 #include <math.h>
 #include <stdint.h>
 
+#include <utility>
+
 #include "../../include/exoplanet_amd.h"
 #include "exo_celerite_core.hpp"
 #include "exo_celerite_group.hpp"
@@ -2337,6 +2339,59 @@ inline bool gp_args_ok(int64_t n, int64_t n_diag, int32_t n_real, int32_t n_comp
          (n_diag == 1 || n_diag == n_draw) && n_chunks >= 0;
 }
 
+template <int V>
+using IntK = std::integral_constant<int, V>;
+// The state width as a compile-time constant: f(IntK<J>{}) for Lo <= J <= Hi; false (nothing called) outside that range.
+// Every width of the range is instantiated, so a call site's range is the set of kernels it compiles.
+template <int Lo, class F, int... I>
+bool with_J_seq(int J, F&& f, std::integer_sequence<int, I...>) {
+  return ((J == Lo + I ? (f(IntK<Lo + I>{}), true) : false) || ...);
+}
+template <int Lo, int Hi, class F>
+bool with_J(int J, F&& f) {
+  return with_J_seq<Lo>(J, f, std::make_integer_sequence<int, Hi - Lo + 1>{});
+}
+
+#ifndef EXO_GP_MIXED_ONE_LAUNCH
+#define EXO_GP_MIXED_ONE_LAUNCH 1
+#endif
+// The one-lane kernels' compile-time constants: f(J, NR, SP) -- IntK's -- for every layout variant NR the draws of a call may
+// need (layout_vote), SP the series' kind (SeriesRowT: 1 a sparse model, 0 otherwise).  J = 1: one real term; J = 2: two real
+// terms or one pair slot -- complex, or, with per-draw kinds, either: mixed(SP), the variants in one launch, or
+// (EXO_GP_MIXED_ONE_LAUNCH = 0) f for all three one after the other (a wave returns at once from the variants it did not vote
+// for); J > 2: run-time flags (J = 4 with no real term: a layout of its own too, split_layouts).  false: J > 8.
+template <class F, class Mixed>
+bool with_layouts(const Coefs& cf, const Series& rs, F&& f, Mixed&& mixed) {
+  auto by_layout = [&](auto sp) {
+    const int J = cf.J();
+    if (J == 1) {
+      f(IntK<1>{}, IntK<1>{}, sp);
+    } else if (J == 2) {
+      if (cf.n_real == 2) f(IntK<2>{}, IntK<2>{}, sp);
+      else if (!cf.kind) f(IntK<2>{}, IntK<0>{}, sp);
+      else if (EXO_GP_MIXED_ONE_LAUNCH) mixed(sp);
+      else { f(IntK<2>{}, IntK<0>{}, sp); f(IntK<2>{}, IntK<2>{}, sp); f(IntK<2>{}, IntK<-1>{}, sp); }
+    } else if (J == 4) {
+      if (split_layouts(4) && cf.n_real == 0) f(IntK<4>{}, IntK<0>{}, sp);
+      f(IntK<4>{}, IntK<-1>{}, sp);
+    } else {
+      return with_J<3, 8>(J, [&](auto jj) { f(jj, IntK<-1>{}, sp); });
+    }
+    return true;
+  };
+  return rs.sp.nseg ? by_layout(IntK<1>{}) : by_layout(IntK<0>{});
+}
+// the widest state of the one-lane tree kernel and of badj_prep: 8; every width when the LDS kernels for wide states are
+// switched off (EXO_GP_WIDE_LDS = 0)
+constexpr int kNarrowMaxJ = EXO_GP_WIDE_LDS ? kWideMinJ - 1 : EXO_GP_MAX_J;
+// the SEQUENTIAL kernels (and the O(N) utilities) take state widths up to EXO_GP_MAX_J = 16 (a draw on a DPP row of 16 lanes
+// above 8): celerite2, the reference's dependency (setup.py:36), has no limit, and two RotationTerms + an SHO term -- J = 10 --
+// is an ordinary stellar-variability model.
+static_assert(kLaneMaxJ <= 6, "the one-lane chunk kernels (chunk_adj: roles 0 .. J + 1 on a group of eight lanes) stop at 6");
+static_assert(kLaneMaxJ >= 2, "with_layouts: compile-time layouts for J <= 2; J > 2 takes run-time flags");
+// the scan trees on groups of eight lanes (celerite_tree_group_kernel): J = 3 .. 8
+constexpr bool group_trees(int J) { return EXO_GP_GROUP_TREES && J >= 3 && J <= 8; }
+
 }  // namespace
 
 extern "C" {
@@ -2366,138 +2421,6 @@ int32_t exo_celerite_default_chunks(int64_t n, int64_t n_draw, int32_t n_real, i
   return chunk_plan(n, n_draw, (int)J, (int32_t)(C < 2 ? 2 : C)).C;
 }
 
-#define EXO_GP_DISPATCH_VOID(J_, CALL) \
-  switch (J_) {                        \
-    case 1: { constexpr int JJ = 1; CALL; } break; \
-    case 2: { constexpr int JJ = 2; CALL; } break; \
-    case 3: { constexpr int JJ = 3; CALL; } break; \
-    case 4: { constexpr int JJ = 4; CALL; } break; \
-    case 5: { constexpr int JJ = 5; CALL; } break; \
-    case 6: { constexpr int JJ = 6; CALL; } break; \
-    case 7: { constexpr int JJ = 7; CALL; } break; \
-    case 8: { constexpr int JJ = 8; CALL; } break; \
-    case 9: { constexpr int JJ = 9; CALL; } break; \
-    case 10: { constexpr int JJ = 10; CALL; } break; \
-    case 11: { constexpr int JJ = 11; CALL; } break; \
-    case 12: { constexpr int JJ = 12; CALL; } break; \
-    case 13: { constexpr int JJ = 13; CALL; } break; \
-    case 14: { constexpr int JJ = 14; CALL; } break; \
-    case 15: { constexpr int JJ = 15; CALL; } break; \
-    case 16: { constexpr int JJ = 16; CALL; } break; \
-    default: break;                                \
-  }
-// the ONE-LANE tree kernel: state widths 1 .. 8; 9 .. 16 only when the LDS kernel for wide states is switched off (EXO_GP_WIDE_LDS = 0)
-#if EXO_GP_WIDE_LDS
-#define EXO_GP_DISPATCH_TREE(J_, CALL) \
-  switch (J_) {                        \
-    case 1: { constexpr int JJ = 1; CALL; } break; \
-    case 2: { constexpr int JJ = 2; CALL; } break; \
-    case 3: { constexpr int JJ = 3; CALL; } break; \
-    case 4: { constexpr int JJ = 4; CALL; } break; \
-    case 5: { constexpr int JJ = 5; CALL; } break; \
-    case 6: { constexpr int JJ = 6; CALL; } break; \
-    case 7: { constexpr int JJ = 7; CALL; } break; \
-    case 8: { constexpr int JJ = 8; CALL; } break; \
-    default: break;                                \
-  }
-#else
-#define EXO_GP_DISPATCH_TREE(J_, CALL) EXO_GP_DISPATCH_VOID(J_, CALL)
-#endif
-#define EXO_GP_DISPATCH_GROUP(J_, CALL) \
-  switch (J_) {                         \
-    case 3: { constexpr int JJ = 3; CALL; } break; \
-    case 4: { constexpr int JJ = 4; CALL; } break; \
-    case 5: { constexpr int JJ = 5; CALL; } break; \
-    case 6: { constexpr int JJ = 6; CALL; } break; \
-    case 7: { constexpr int JJ = 7; CALL; } break; \
-    case 8: { constexpr int JJ = 8; CALL; } break; \
-    default: break;                                \
-  }
-#define EXO_GP_DISPATCH_LANE(J_, CALL) \
-  switch (J_) {                        \
-    case 1: { constexpr int JJ = 1; CALL; } break; \
-    case 2: { constexpr int JJ = 2; CALL; } break; \
-    case 3: { constexpr int JJ = 3; CALL; } break; \
-    case 4: { constexpr int JJ = 4; CALL; } break; \
-    case 5: { constexpr int JJ = 5; CALL; } break; \
-    case 6: { constexpr int JJ = 6; CALL; } break; \
-    default: break;                                \
-  }
-static_assert(kLaneMaxJ <= 6, "EXO_GP_DISPATCH_LANE lists the state widths of the one-lane path");
-#define EXO_GP_DISPATCH_NEWTON(J_, CALL) \
-  switch (J_) {                          \
-    case 3: { constexpr int JJ = 3; CALL; } break; \
-    case 4: { constexpr int JJ = 4; CALL; } break; \
-    case 5: { constexpr int JJ = 5; CALL; } break; \
-    case 6: { constexpr int JJ = 6; CALL; } break; \
-    default: break;                                \
-  }
-#define EXO_GP_DISPATCH(J_, CALL) \
-  switch (J_) {                   \
-    case 1: { constexpr int JJ = 1; CALL; } break; \
-    case 2: { constexpr int JJ = 2; CALL; } break; \
-    case 3: { constexpr int JJ = 3; CALL; } break; \
-    case 4: { constexpr int JJ = 4; CALL; } break; \
-    case 5: { constexpr int JJ = 5; CALL; } break; \
-    case 6: { constexpr int JJ = 6; CALL; } break; \
-    case 7: { constexpr int JJ = 7; CALL; } break; \
-    case 8: { constexpr int JJ = 8; CALL; } break; \
-    case 9: { constexpr int JJ = 9; CALL; } break; \
-    case 10: { constexpr int JJ = 10; CALL; } break; \
-    case 11: { constexpr int JJ = 11; CALL; } break; \
-    case 12: { constexpr int JJ = 12; CALL; } break; \
-    case 13: { constexpr int JJ = 13; CALL; } break; \
-    case 14: { constexpr int JJ = 14; CALL; } break; \
-    case 15: { constexpr int JJ = 15; CALL; } break; \
-    case 16: { constexpr int JJ = 16; CALL; } break; \
-    default: return EXO_ERR_INVALID_ARGUMENT;      \
-  }
-// kernels whose wide instantiations exist only when the LDS kernels for wide states are switched off (EXO_GP_WIDE_LDS = 0)
-#if EXO_GP_WIDE_LDS
-#define EXO_GP_DISPATCH_LE8(J_, CALL) \
-  switch (J_) {                       \
-    case 1: { constexpr int JJ = 1; CALL; } break; \
-    case 2: { constexpr int JJ = 2; CALL; } break; \
-    case 3: { constexpr int JJ = 3; CALL; } break; \
-    case 4: { constexpr int JJ = 4; CALL; } break; \
-    case 5: { constexpr int JJ = 5; CALL; } break; \
-    case 6: { constexpr int JJ = 6; CALL; } break; \
-    case 7: { constexpr int JJ = 7; CALL; } break; \
-    case 8: { constexpr int JJ = 8; CALL; } break; \
-    default: return EXO_ERR_INVALID_ARGUMENT;      \
-  }
-#else
-#define EXO_GP_DISPATCH_LE8(J_, CALL) EXO_GP_DISPATCH(J_, CALL)
-#endif
-// the SEQUENTIAL kernels (and the O(N) utilities) take state widths up to EXO_GP_MAX_J = 16 (a draw on a DPP row of 16 lanes
-// above 8): celerite2, the reference's dependency (setup.py:36), has no limit, and two RotationTerms + an SHO term -- J = 10 --
-// is an ordinary stellar-variability model.  The time-parallel path stops at 8 (kChunkMaxJ): wider states run the recurrences
-// cadence by cadence, correct and slow.
-#define EXO_GP_DISPATCH_SEQ(J_, CALL) \
-  switch (J_) {                       \
-    case 1: { constexpr int JJ = 1; CALL; } break; \
-    case 2: { constexpr int JJ = 2; CALL; } break; \
-    case 3: { constexpr int JJ = 3; CALL; } break; \
-    case 4: { constexpr int JJ = 4; CALL; } break; \
-    case 5: { constexpr int JJ = 5; CALL; } break; \
-    case 6: { constexpr int JJ = 6; CALL; } break; \
-    case 7: { constexpr int JJ = 7; CALL; } break; \
-    case 8: { constexpr int JJ = 8; CALL; } break; \
-    case 9: { constexpr int JJ = 9; CALL; } break; \
-    case 10: { constexpr int JJ = 10; CALL; } break; \
-    case 11: { constexpr int JJ = 11; CALL; } break; \
-    case 12: { constexpr int JJ = 12; CALL; } break; \
-    case 13: { constexpr int JJ = 13; CALL; } break; \
-    case 14: { constexpr int JJ = 14; CALL; } break; \
-    case 15: { constexpr int JJ = 15; CALL; } break; \
-    case 16: { constexpr int JJ = 16; CALL; } break; \
-    default: return EXO_ERR_INVALID_ARGUMENT;      \
-  }
-static_assert(kLaneMaxJ >= 2, "EXO_GP_LAYOUTS lists compile-time layouts for J <= 2; J > 2 takes run-time flags");
-// CALL with `JJ` and `NR` for every layout variant the draws of a call may need (layout_vote):
-// J = 1: one real term; J = 2: two real terms or one pair slot -- complex, or, with per-draw kinds,
-// either (three launches: waves return at once from the variants they did not vote for); J > 2:
-// run-time flags.
 // J = 2 with per-draw pair kinds: which draw a lane of the *_mixed_kernel launches works on.  A wave runs ONE layout, the one
 // all its draws share, or the run-time layout (half again as many instructions) -- and the step waits for its slowest wave: a
 // batch with 1 % of its draws on the other side of Q = 1/2 cost 1.84 x a clean one for the sake of ONE mixed wave.  So the
@@ -2608,41 +2531,6 @@ __global__ __launch_bounds__(kWave, EXO_VJP1_WAVES) void celerite_chunk1_vjp_mix
 
 }  // extern "C++"
 
-#ifndef EXO_GP_MIXED_ONE_LAUNCH
-#define EXO_GP_MIXED_ONE_LAUNCH 1
-#endif
-#define EXO_GP_LAYOUTS(J_, CF, CALL, MIXED)                                             \
-  switch (J_) {                                                                         \
-    case 1: { constexpr int JJ = 1, NR = 1; CALL; } break;                              \
-    case 2:                                                                             \
-      if ((CF).n_real == 2) { constexpr int JJ = 2, NR = 2; CALL; }                     \
-      else if (!(CF).kind) { constexpr int JJ = 2, NR = 0; CALL; }                      \
-      else if (EXO_GP_MIXED_ONE_LAUNCH) { MIXED; }   /* per-draw kinds: the three variants in one launch */ \
-      else {            /* ... or one after the other: a wave returns at once from the variants it did not vote for */ \
-        { constexpr int JJ = 2, NR = 0; CALL; }                                         \
-        { constexpr int JJ = 2, NR = 2; CALL; }                                         \
-        { constexpr int JJ = 2, NR = -1; CALL; }                                        \
-      }                                                                                 \
-      break;                                                                            \
-    case 3: { constexpr int JJ = 3, NR = -1; CALL; } break;                             \
-    case 4:                                                                             \
-      if (split_layouts(4) && (CF).n_real == 0) { constexpr int JJ = 4, NR = 0; CALL; }   \
-      { constexpr int JJ = 4, NR = -1; CALL; }                                          \
-      break;                                                                            \
-    case 5: { constexpr int JJ = 5, NR = -1; CALL; } break;                             \
-    case 6: { constexpr int JJ = 6, NR = -1; CALL; } break;                             \
-    case 7: { constexpr int JJ = 7, NR = -1; CALL; } break;                             \
-    case 8: { constexpr int JJ = 8, NR = -1; CALL; } break;                             \
-    default: return EXO_ERR_INVALID_ARGUMENT;                                           \
-  }
-
-// the series' kind is a compile-time constant of the one-lane kernels (SeriesRowT): SP = 1 a sparse model, 0 otherwise
-#define EXO_GP_BY_SERIES(RS, NAME)                                                                        \
-  {                                                                                                       \
-    const int rc_ = (RS).sp.nseg ? NAME(std::integral_constant<int, 1>{}) : NAME(std::integral_constant<int, 0>{}); \
-    if (rc_ != EXO_OK) return rc_;                                                                        \
-  }
-
 // ---- the adjoint scan beside the forward chunk kernel (EXO_GP_PREPARE_ADJOINT, include/exoplanet_amd.h) -------------------------
 // What the reverse call does before its chunk kernel -- adjoint elements (badj_prep), the robust route's own (chunk_adj), the
 // scan (B') as a tree: 14-26 short launches, each an item's dependent latency, 0.13-0.17 ms at the C5 shape -- needs nothing of
@@ -2679,6 +2567,74 @@ static SideStream* side_stream() {
   }
   return (ss.fork && ss.join) ? &ss : nullptr;
 }
+// the second stream, ordered behind everything issued on `st` so far; nullptr: none to be had
+static SideStream* fork_side(hipStream_t st) {
+  SideStream* q = side_stream();
+  if (q && (hipEventRecord(q->fork, st) != hipSuccess || hipStreamWaitEvent(q->s, q->fork, 0) != hipSuccess)) {
+    (void)hipGetLastError();
+    q = nullptr;
+  }
+  return q;
+}
+
+extern "C++" {   // (templates: the entry points below are extern "C")
+// a level of the scan trees on groups of eight lanes (J = 3 .. 8) -- also a level of the fine elements' pairwise composition
+template <bool ADJ, bool DOWN>
+static void launch_tree_group(const TreeOp& op, int J, int64_t n_draw, double* state, hipStream_t st) {
+  const dim3 ggrid((unsigned)(((int64_t)op.n_item * n_draw + kScanBlock / 8 - 1) / (kScanBlock / 8)));
+  with_J<3, 8>(J, [&](auto jj) {
+    hipLaunchKernelGGL((celerite_tree_group_kernel<decltype(jj)::value, ADJ, DOWN>), ggrid, dim3(kScanBlock), 0, st, op, state);
+  });
+}
+
+// The scan trees: (B) (ADJ = false: the entering states) and (B') (ADJ = true: the adjoint states, over positions
+// p = C - 1 - chunk).  A launch per level (tree_scan); J <= 2 two levels per launch (tree_scan4); J = 3 .. 8 on groups of eight
+// lanes, the top levels as one serial chain (tree_scan_top); J >= 9 a block per item, matrices in LDS (celerite_tree_wide_kernel).
+// seed(): the caller's -- the initial state at ws.tree_state(ws.tree_top()).
+template <bool ADJ, class Seed>
+static void launch_scan_tree(const ChunkWs& ws, int J, int64_t n_draw, double* state, hipStream_t st, Seed&& seed) {
+  const dim3 block(kWave);
+  auto level = [&](const TreeOp& op, bool down) {
+    exo::with_flag(down, [&](auto dn) {
+      constexpr bool DOWN = decltype(dn)::value;
+      const dim3 tgrid((unsigned)(((int64_t)op.n_item * n_draw + kWave - 1) / kWave));
+      if (group_trees(J)) {
+        launch_tree_group<ADJ, DOWN>(op, J, n_draw, state, st);
+      } else if (EXO_GP_WIDE_LDS && J >= kWideMinJ) {
+        hipLaunchKernelGGL((celerite_tree_wide_kernel<ADJ, DOWN>), dim3((unsigned)((int64_t)op.n_item * n_draw)), dim3(256), 0, st, op,
+                           state);
+      } else if (!ADJ && !DOWN && J >= 3 && J <= 8) {
+        // composing two filtering elements keeps ~5 J x J matrices alive around the solve: one lane per
+        // item spills 2 KB at J = 6 and crawls (76 us per level); a wave per item with the tiles in LDS
+        hipLaunchKernelGGL(celerite_compose_lds_kernel, dim3((unsigned)(op.n_item * n_draw)), block, 0, st, op, state);
+      } else {
+        with_J<1, kNarrowMaxJ>(J, [&](auto jj) {
+          hipLaunchKernelGGL((celerite_tree_kernel<decltype(jj)::value, ADJ, DOWN>), tgrid, block, 0, st, op, state);
+        });
+      }
+    });
+  };
+  if (EXO_GP_TREE4 && J <= 2) {
+    auto level_pair = [&](const TreeOp& a, const TreeOp& b, bool down) {
+      const dim3 tgrid((unsigned)(((int64_t)b.n_item * n_draw + kWave - 1) / kWave));
+      with_J<1, 2>(J, [&](auto jj) {
+        exo::with_flag(down, [&](auto dn) {
+          hipLaunchKernelGGL((celerite_tree4_kernel<decltype(jj)::value, ADJ, decltype(dn)::value>), tgrid, block, 0, st, a, b, state);
+        });
+      });
+    };
+    tree_scan4(ws, J, ADJ, level, level_pair, seed);
+  } else {
+    auto serial = [&](const TreeOp& op) {
+      const dim3 sgrid((unsigned)((n_draw + kScanBlock / 8 - 1) / (kScanBlock / 8)));
+      with_J<3, 8>(J, [&](auto jj) {
+        hipLaunchKernelGGL((celerite_tree_serial_group_kernel<decltype(jj)::value, ADJ>), sgrid, dim3(kScanBlock), 0, st, op, state);
+      });
+    };
+    tree_scan_top(ws, J, ADJ, group_trees(J) ? tree_serial_level(ws, J) : ws.tree_top(), level, seed, serial);
+  }
+}
+}  // extern "C++"
 
 // gloglike == nullptr: for a cotangent of one (the forward call's; ChunkGeom::prep)
 // parts: 1 = the adjoint elements (badj_prep, chunk_adj), 2 = the scan over them, 3 = both
@@ -2695,66 +2651,32 @@ static int celerite_adjoint_scan(const double* t, Series resid, const double* di
                          n_draw, J, wstate, cg, cf.row);
     } else if (EXO_GP_GROUP_TREES && J >= EXO_GP_BADJ_GROUP_MIN_J && J <= 8) {
       const dim3 ggrid((unsigned)(((int64_t)(cg.C - 1) * n_draw + kScanBlock / 8 - 1) / (kScanBlock / 8)));
-      EXO_GP_DISPATCH_GROUP(J, hipLaunchKernelGGL((celerite_badj_prep_group_kernel<JJ>), ggrid, dim3(kScanBlock), 0, st, gloglike, n, n_draw,
-                                                  wstate, cg, cf.row))
-    } else {
-      EXO_GP_DISPATCH_LE8(J, hipLaunchKernelGGL((celerite_badj_prep_kernel<JJ>), dim3(per_draw.x, (unsigned)(cg.C - 1)), block,
-                                                0, st, gloglike, n, n_draw, wstate, cg, cf.row))
+      with_J<3, 8>(J, [&](auto jj) {
+        hipLaunchKernelGGL((celerite_badj_prep_group_kernel<decltype(jj)::value>), ggrid, dim3(kScanBlock), 0, st, gloglike, n, n_draw,
+                           wstate, cg, cf.row);
+      });
+    } else if (!with_J<1, kNarrowMaxJ>(J, [&](auto jj) {
+                 hipLaunchKernelGGL((celerite_badj_prep_kernel<decltype(jj)::value>), dim3(per_draw.x, (unsigned)(cg.C - 1)), block, 0,
+                                    st, gloglike, n, n_draw, wstate, cg, cf.row);
+               })) {
+      return EXO_ERR_INVALID_ARGUMENT;
     }
     if (cg.lane) {
       // draws flagged kFlagRobust: those inputs once more, from the chunks' own reverse recurrences (chunk_adj_lane)
-      EXO_GP_DISPATCH_LANE(J, hipLaunchKernelGGL((celerite_chunk_adj_kernel<JJ>), dim3((unsigned)(cg.C - 1), (unsigned)((n_draw + kAdjDraws - 1) / kAdjDraws)), block, 0,
-                                                 st, t, resid, diag, n_diag, n, cf, n_draw, gloglike, wstate, cg))
+      with_J<1, kLaneMaxJ>(J, [&](auto jj) {
+        hipLaunchKernelGGL((celerite_chunk_adj_kernel<decltype(jj)::value>),
+                           dim3((unsigned)(cg.C - 1), (unsigned)((n_draw + kAdjDraws - 1) / kAdjDraws)), block, 0, st, t, resid, diag,
+                           n_diag, n, cf, n_draw, gloglike, wstate, cg);
+      });
     }
   }
   if (parts & 2) {
-    {
-      // (B') as a tree over positions p = C - 1 - chunk: adjoint elements of chunks C - 1 .. 1, zero initial adjoint
-      bool ok = true;
-      auto launch = [&](const TreeOp& op, bool down) {
-                  const dim3 tgrid((unsigned)(((int64_t)op.n_item * n_draw + kWave - 1) / kWave));
-                  const dim3 ggrid((unsigned)(((int64_t)op.n_item * n_draw + kScanBlock / 8 - 1) / (kScanBlock / 8)));
-                  if (EXO_GP_GROUP_TREES && J >= 3 && J <= 8) {
-                    if (down) {
-                      EXO_GP_DISPATCH_GROUP(J, hipLaunchKernelGGL((celerite_tree_group_kernel<JJ, true, true>), ggrid, dim3(kScanBlock), 0, st, op, wstate))
-                    } else {
-                      EXO_GP_DISPATCH_GROUP(J, hipLaunchKernelGGL((celerite_tree_group_kernel<JJ, true, false>), ggrid, dim3(kScanBlock), 0, st, op, wstate))
-                    }
-                  } else if (EXO_GP_WIDE_LDS && J >= kWideMinJ) {
-                    const dim3 wgrid((unsigned)((int64_t)op.n_item * n_draw));
-                    if (down) hipLaunchKernelGGL((celerite_tree_wide_kernel<true, true>), wgrid, dim3(256), 0, st, op, wstate);
-                    else hipLaunchKernelGGL((celerite_tree_wide_kernel<true, false>), wgrid, dim3(256), 0, st, op, wstate);
-                  } else if (down) {
-                    EXO_GP_DISPATCH_TREE(J, hipLaunchKernelGGL((celerite_tree_kernel<JJ, true, true>), tgrid, block, 0, st, op, wstate))
-                  } else {
-                    EXO_GP_DISPATCH_TREE(J, hipLaunchKernelGGL((celerite_tree_kernel<JJ, true, false>), tgrid, block, 0, st, op, wstate))
-                  }
-                };
-      auto seed = [&]() {
-                  ok = exo::zero_fill_async(wstate + ws.tree_state(ws.tree_top()), (int64_t)ws.B() * n_draw, st);   // (never a memset node: exo_math.hpp)
-                };
-      if (EXO_GP_TREE4 && J <= 2) {
-        tree_scan4(ws, J, true, launch,
-                   [&](const TreeOp& a, const TreeOp& b, bool down) {
-                     const dim3 tgrid((unsigned)(((int64_t)b.n_item * n_draw + kWave - 1) / kWave));
-                     if (J == 1) {
-                       if (down) hipLaunchKernelGGL((celerite_tree4_kernel<1, true, true>), tgrid, block, 0, st, a, b, wstate);
-                       else hipLaunchKernelGGL((celerite_tree4_kernel<1, true, false>), tgrid, block, 0, st, a, b, wstate);
-                     } else {
-                       if (down) hipLaunchKernelGGL((celerite_tree4_kernel<2, true, true>), tgrid, block, 0, st, a, b, wstate);
-                       else hipLaunchKernelGGL((celerite_tree4_kernel<2, true, false>), tgrid, block, 0, st, a, b, wstate);
-                     }
-                   },
-                   seed);
-      } else {
-        tree_scan_top(ws, J, true, (EXO_GP_GROUP_TREES && J >= 3 && J <= 8) ? tree_serial_level(ws, J) : ws.tree_top(), launch, seed,
-                      [&](const TreeOp& op) {
-                        const dim3 sgrid((unsigned)((n_draw + kScanBlock / 8 - 1) / (kScanBlock / 8)));
-                        EXO_GP_DISPATCH_GROUP(J, hipLaunchKernelGGL((celerite_tree_serial_group_kernel<JJ, true>), sgrid, dim3(kScanBlock), 0, st, op, wstate))
-                      });
-      }
-      if (!ok) return EXO_ERR_LAUNCH;
-    }
+    // (B') as a tree over positions p = C - 1 - chunk: adjoint elements of chunks C - 1 .. 1, zero initial adjoint
+    bool ok = true;
+    launch_scan_tree<true>(ws, J, n_draw, wstate, st, [&]() {
+      ok = exo::zero_fill_async(wstate + ws.tree_state(ws.tree_top()), (int64_t)ws.B() * n_draw, st);   // (never a memset node: exo_math.hpp)
+    });
+    if (!ok) return EXO_ERR_LAUNCH;
   }
   return launch_status();
 }
@@ -2780,15 +2702,6 @@ static int celerite_fwd(const double* t, Series resid, const double* diag, int64
     const ChunkGeom cg = chunk_plan(n, n_draw, J, n_chunks);
     const double* only_flagged = nullptr;
     int n_slice = 0;
-    SideStream* ss = nullptr;
-    auto fork_side = [&]() -> SideStream* {   // the second stream, ordered behind everything issued on `st` so far
-      SideStream* q = side_stream();
-      if (q && (hipEventRecord(q->fork, st) != hipSuccess || hipStreamWaitEvent(q->s, q->fork, 0) != hipSuccess)) {
-        (void)hipGetLastError();
-        q = nullptr;
-      }
-      return q;
-    };
     if (cg.C <= 1) {
       const int64_t n_el = n * n_draw * J;
       hipLaunchKernelGGL(celerite_prep_kernel, dim3((unsigned)((n_el + 255) / 256)), dim3(256), 0, st, t, n, cf, n_draw,
@@ -2799,8 +2712,10 @@ static int celerite_fwd(const double* t, Series resid, const double* diag, int64
       // recurrences per chunk, sum of the partials
       const ChunkWs ws = chunk_ws(n, n_draw, J, cg);
       const dim3 per_draw((unsigned)((n_draw + kWave - 1) / kWave));
-      EXO_GP_DISPATCH(J, hipLaunchKernelGGL((celerite_flag_kernel<JJ>), per_draw, block, 0, st, cf, n_draw,
-                                            state + ws.off_flag()))
+      if (!with_J<1, EXO_GP_MAX_J>(J, [&](auto jj) {
+            hipLaunchKernelGGL((celerite_flag_kernel<decltype(jj)::value>), per_draw, block, 0, st, cf, n_draw, state + ws.off_flag());
+          }))
+        return EXO_ERR_INVALID_ARGUMENT;
       const dim3 egrid(per_draw.x, (unsigned)cg.C), cgrid(grid.x, (unsigned)cg.C);
 #ifndef EXO_ELEM_LG_MIN_J
 #define EXO_ELEM_LG_MIN_J 7
@@ -2817,18 +2732,22 @@ static int celerite_fwd(const double* t, Series resid, const double* diag, int64
         hipLaunchKernelGGL(celerite_sparse_order_kernel, dim3(1), dim3(256), 0, st, resid.sp, n, n_draw, cg,
                            reinterpret_cast<int32_t*>(state + ws.off_order()));
       if (J >= EXO_ELEM_LG_MIN_J) {   // the one-lane element kernel is as fast up to J = 6 and does not fit beyond
-        EXO_GP_DISPATCH(J, hipLaunchKernelGGL((celerite_elem_lg_kernel<JJ>), cgrid_f, block, 0, st, t, resid, diag, n_diag,
-                                              n, cf, n_draw, state, cge, flag_at))
-      } else {
-        auto launch_elem = [&](auto sp_tag) -> int {
-          constexpr int SP = decltype(sp_tag)::value;
-          EXO_GP_LAYOUTS(J, cf, hipLaunchKernelGGL((celerite_elem_kernel<JJ, NR, SP>), egrid_f, block, 0, st, t, resid, diag,
-                                                   n_diag, n, cf, n_draw, state, cge, flag_at),
-                         hipLaunchKernelGGL(celerite_elem_mixed_kernel<SP>, dim3(egrid_f.x + 1, egrid_f.y, 2), block, 0, st, t, resid, diag,
-                                            n_diag, n, cf, n_draw, state, cge, flag_at))
-          return EXO_OK;
-        };
-        EXO_GP_BY_SERIES(resid, launch_elem)
+        if (!with_J<1, EXO_GP_MAX_J>(J, [&](auto jj) {
+              hipLaunchKernelGGL((celerite_elem_lg_kernel<decltype(jj)::value>), cgrid_f, block, 0, st, t, resid, diag, n_diag, n, cf,
+                                 n_draw, state, cge, flag_at);
+            }))
+          return EXO_ERR_INVALID_ARGUMENT;
+      } else if (!with_layouts(
+                     cf, resid,
+                     [&](auto jj, auto nr, auto sp) {
+                       hipLaunchKernelGGL((celerite_elem_kernel<decltype(jj)::value, decltype(nr)::value, decltype(sp)::value>), egrid_f,
+                                          block, 0, st, t, resid, diag, n_diag, n, cf, n_draw, state, cge, flag_at);
+                     },
+                     [&](auto sp) {
+                       hipLaunchKernelGGL(celerite_elem_mixed_kernel<decltype(sp)::value>, dim3(egrid_f.x + 1, egrid_f.y, 2), block, 0,
+                                          st, t, resid, diag, n_diag, n, cf, n_draw, state, cge, flag_at);
+                     })) {
+        return EXO_ERR_INVALID_ARGUMENT;
       }
       for (int f = cg.fine; f >= 1; --f) {
         TreeOp op{};
@@ -2836,11 +2755,10 @@ static int celerite_fwd(const double* t, Series resid, const double* diag, int64
         op.src_elem = ws.off_fine(f); op.src_n = op.src_len = cg.C << f;
         op.dst_elem = f > 1 ? ws.off_fine(f - 1) : ws.elem(0, 0, 0);
         op.n_item = cg.C << (f - 1);
-        if (EXO_GP_GROUP_TREES && EXO_GP_FINE_GROUP && J >= 3 && J <= 8) {
+        if (EXO_GP_FINE_GROUP && group_trees(J)) {
           // the scan trees' own item kernel (eight lanes per composition, 32 draws per block): the wave-per-composition LDS kernel
           // took 227 us for the 32 768 compositions of the C5 shape at J = 8, a level of the tree 26 us for 16 384
-          const dim3 ggrid((unsigned)(((int64_t)op.n_item * n_draw + kScanBlock / 8 - 1) / (kScanBlock / 8)));
-          EXO_GP_DISPATCH_GROUP(J, hipLaunchKernelGGL((celerite_tree_group_kernel<JJ, false, false>), ggrid, dim3(kScanBlock), 0, st, op, state))
+          launch_tree_group<false, false>(op, J, n_draw, state, st);
         } else {
           hipLaunchKernelGGL(celerite_compose_lds_kernel, dim3((unsigned)(op.n_item * n_draw)), block, 0, st, op, state);
         }
@@ -2848,116 +2766,80 @@ static int celerite_fwd(const double* t, Series resid, const double* diag, int64
       // after the element kernel: it may flag more draws (measurement variance too small)
       hipLaunchKernelGGL(celerite_prep_flagged_kernel, dim3(8, (unsigned)n_draw), dim3(256), 0, st, t, n, cf, n_draw, J,
                          state, state + ws.off_flag());
-      {
-        // (B) as a tree: compose up to one position, seed it with the initial state, apply back down -- a launch per level
-        int rc = EXO_OK;
-        auto launch = [&](const TreeOp& op, bool down) {
-                    const dim3 tgrid((unsigned)(((int64_t)op.n_item * n_draw + kWave - 1) / kWave));
-                    const dim3 ggrid((unsigned)(((int64_t)op.n_item * n_draw + kScanBlock / 8 - 1) / (kScanBlock / 8)));
-                    if (EXO_GP_GROUP_TREES && J >= 3 && J <= 8) {
-                      if (down) {
-                        EXO_GP_DISPATCH_GROUP(J, hipLaunchKernelGGL((celerite_tree_group_kernel<JJ, false, true>), ggrid, dim3(kScanBlock), 0, st, op, state))
-                      } else {
-                        EXO_GP_DISPATCH_GROUP(J, hipLaunchKernelGGL((celerite_tree_group_kernel<JJ, false, false>), ggrid, dim3(kScanBlock), 0, st, op, state))
-                      }
-                    } else if (EXO_GP_WIDE_LDS && J >= kWideMinJ) {   // a block per item, matrices in LDS (celerite_tree_wide_kernel)
-                      const dim3 wgrid((unsigned)((int64_t)op.n_item * n_draw));
-                      if (down) hipLaunchKernelGGL((celerite_tree_wide_kernel<false, true>), wgrid, dim3(256), 0, st, op, state);
-                      else hipLaunchKernelGGL((celerite_tree_wide_kernel<false, false>), wgrid, dim3(256), 0, st, op, state);
-                    } else if (down) {
-                      EXO_GP_DISPATCH_TREE(J, hipLaunchKernelGGL((celerite_tree_kernel<JJ, false, true>), tgrid, block, 0, st, op, state))
-                    } else if (J >= 3 && J <= 8) {
-                      // composing two filtering elements keeps ~5 J x J matrices alive around the solve: one lane per
-                      // item spills 2 KB at J = 6 and crawls (76 us per level); a wave per item with the tiles in LDS
-                      hipLaunchKernelGGL(celerite_compose_lds_kernel, dim3((unsigned)(op.n_item * n_draw)), block, 0,
-                                         st, op, state);
-                    } else {
-                      EXO_GP_DISPATCH_TREE(J, hipLaunchKernelGGL((celerite_tree_kernel<JJ, false, false>), tgrid, block, 0, st, op, state))
-                    }
-                  };
-        auto seed = [&]() {
-                    EXO_GP_DISPATCH_VOID(J, hipLaunchKernelGGL((celerite_scan_init_kernel<JJ>), grid, block, 0, st, t, cf, n_draw,
-                                                               state + ws.tree_state(ws.tree_top())))
-                  };
-        if (EXO_GP_TREE4 && J <= 2) {
-          tree_scan4(ws, J, false, launch,
-                     [&](const TreeOp& a, const TreeOp& b, bool down) {
-                       const dim3 tgrid((unsigned)(((int64_t)b.n_item * n_draw + kWave - 1) / kWave));
-                       if (J == 1) {
-                         if (down) hipLaunchKernelGGL((celerite_tree4_kernel<1, false, true>), tgrid, block, 0, st, a, b, state);
-                         else hipLaunchKernelGGL((celerite_tree4_kernel<1, false, false>), tgrid, block, 0, st, a, b, state);
-                       } else {
-                         if (down) hipLaunchKernelGGL((celerite_tree4_kernel<2, false, true>), tgrid, block, 0, st, a, b, state);
-                         else hipLaunchKernelGGL((celerite_tree4_kernel<2, false, false>), tgrid, block, 0, st, a, b, state);
-                       }
-                     },
-                     seed);
-        } else {
-          tree_scan_top(ws, J, false, (EXO_GP_GROUP_TREES && J >= 3 && J <= 8) ? tree_serial_level(ws, J) : ws.tree_top(), launch, seed,
-                        [&](const TreeOp& op) {
-                          const dim3 sgrid((unsigned)((n_draw + kScanBlock / 8 - 1) / (kScanBlock / 8)));
-                          EXO_GP_DISPATCH_GROUP(J, hipLaunchKernelGGL((celerite_tree_serial_group_kernel<JJ, false>), sgrid, dim3(kScanBlock), 0, st, op, state))
-                        });
-        }
-        if (rc != EXO_OK) return rc;
-      }
-      if (cg.lane) {
-        // draws flagged kFlagRobust: their entering states once more -- Newton iterations from the trees' (J <= 2: the elements
-        // applied one after the other)
-        const dim3 rgrid((unsigned)(J >= 3 ? (n_draw + kWave / 8 - 1) / (kWave / 8) : per_draw.x));
-        if (EXO_GP_ROBUST_NEWTON && J >= 3) {
-          EXO_GP_DISPATCH_NEWTON(J, hipLaunchKernelGGL((celerite_robust_newton_kernel<JJ>), dim3((unsigned)n_draw), dim3(kNewtonBlock), 0, st,
-                                                       n, cg, n_draw, state))
-        } else {
-          EXO_GP_DISPATCH_LANE(J, hipLaunchKernelGGL((celerite_robust_scan_kernel<JJ>), rgrid, block, 0, st, t, cf, n, cg, n_draw,
-                                                     state))
-        }
-        // (fwd_st, fwd_cg: the stream and the draws -- ChunkGeom::which -- of this launch)
-        hipStream_t fwd_st = st;
-        ChunkGeom fwd_cg = cg;
-        auto launch_fwd = [&](auto sp_tag) -> int {
-          constexpr int SP = decltype(sp_tag)::value;
-          EXO_GP_LAYOUTS(J, cf, hipLaunchKernelGGL((celerite_chunk1_fwd_kernel<(JJ <= kLaneMaxJ ? JJ : 1), NR, SP>), egrid, block, 0,
-                                                   fwd_st, t, resid, diag, n_diag, n, cf, n_draw, state, fwd_cg),
-                         hipLaunchKernelGGL(celerite_chunk1_fwd_mixed_kernel<SP>, dim3(egrid.x + 1, egrid.y, 2), block, 0, fwd_st, t, resid, diag,
-                                            n_diag, n, cf, n_draw, state, fwd_cg))
-          return EXO_OK;
+      // (B) as a tree: compose up to one position, seed it with the initial state, apply back down
+      launch_scan_tree<false>(ws, J, n_draw, state, st, [&]() {
+        with_J<1, EXO_GP_MAX_J>(J, [&](auto jj) {
+          hipLaunchKernelGGL((celerite_scan_init_kernel<decltype(jj)::value>), grid, block, 0, st, t, cf, n_draw,
+                             state + ws.tree_state(ws.tree_top()));
+        });
+      });
+      // the recurrences per chunk -- and, with want_prep, the adjoint scan for a cotangent of one, on a second stream where there
+      // is one: `ss`, joined below on every way out of chunk_recurrences (an unjoined fork invalidates a stream capture)
+      SideStream* ss = nullptr;
+      auto chunk_recurrences = [&]() -> int {
+        ChunkGeom fwd_cg = cg;   // (the draws of the one-lane launch: ChunkGeom::which)
+        auto launch_fwd = [&]() {
+          return with_layouts(
+              cf, resid,
+              [&](auto jj, auto nr, auto sp) {
+                constexpr int JJ = decltype(jj)::value;
+                hipLaunchKernelGGL((celerite_chunk1_fwd_kernel<(JJ <= kLaneMaxJ ? JJ : 1), decltype(nr)::value, decltype(sp)::value>),
+                                   egrid, block, 0, st, t, resid, diag, n_diag, n, cf, n_draw, state, fwd_cg);
+              },
+              [&](auto sp) {
+                hipLaunchKernelGGL(celerite_chunk1_fwd_mixed_kernel<decltype(sp)::value>, dim3(egrid.x + 1, egrid.y, 2), block, 0, st, t,
+                                   resid, diag, n_diag, n, cf, n_draw, state, fwd_cg);
+              });
         };
-        if (want_prep) {
-          // the adjoint elements first, on the caller's stream: badj_prep and chunk_adj take a SIMD's whole register file (482 /
-          // 512 registers at J = 6), so beside the forward chunk kernel -- a resident wave on every SIMD -- they would only wait
-          // for it, the scan behind them.  chunk_adj reads the forward checkpoints of the draws on the robust route: their
-          // recurrences run now (ChunkGeom::which = 1; no such draw: two launches that return at once), everybody else's beside
-          // the scan.
-          int rc;
-          fwd_cg.which = 1;
-          EXO_GP_BY_SERIES(resid, launch_fwd)
-          rc = celerite_adjoint_scan(t, resid, diag, n_diag, n, cf, n_draw, nullptr, state, cg, st, 1);
-          if (rc != EXO_OK) return rc;
-          fwd_cg.which = 2;
-          ss = fork_side();
-          rc = celerite_adjoint_scan(t, resid, diag, n_diag, n, cf, n_draw, nullptr, state, cg, ss ? ss->s : st, 2);
-          if (rc != EXO_OK) return rc;
+        if (cg.lane) {
+          // draws flagged kFlagRobust: their entering states once more -- Newton iterations from the trees' (J <= 2: the elements
+          // applied one after the other)
+          const dim3 rgrid((unsigned)(J >= 3 ? (n_draw + kWave / 8 - 1) / (kWave / 8) : per_draw.x));
+          if (EXO_GP_ROBUST_NEWTON && J >= 3) {
+            with_J<3, kLaneMaxJ>(J, [&](auto jj) {
+              hipLaunchKernelGGL((celerite_robust_newton_kernel<decltype(jj)::value>), dim3((unsigned)n_draw), dim3(kNewtonBlock), 0,
+                                 st, n, cg, n_draw, state);
+            });
+          } else {
+            with_J<1, kLaneMaxJ>(J, [&](auto jj) {
+              hipLaunchKernelGGL((celerite_robust_scan_kernel<decltype(jj)::value>), rgrid, block, 0, st, t, cf, n, cg, n_draw, state);
+            });
+          }
         }
-        EXO_GP_BY_SERIES(resid, launch_fwd)
-      } else {
         if (want_prep) {
-          // lane-group kernels: J = 7, 8 -- badj_prep fills the register file: first, on the caller's stream; J >= 9 -- a
-          // block per item, 81 registers: with the scan on the second stream
+          // The adjoint elements first, on the caller's stream: badj_prep and chunk_adj take a SIMD's whole register file (482 /
+          // 512 registers at J = 6; J = 7, 8: the lane-group badj_prep), so beside the forward chunk kernel -- a resident wave on
+          // every SIMD -- they would only wait for it, the scan behind them.  chunk_adj reads the forward checkpoints of the draws
+          // on the robust route: their recurrences run now (ChunkGeom::which = 1; no such draw: two launches that return at once),
+          // everybody else's beside the scan.  J >= 9: badj_prep is a block per item, 81 registers: with the scan on the second
+          // stream.
           const bool wide = EXO_GP_WIDE_LDS && J >= kWideMinJ;
-          int rc = EXO_OK;
-          if (!wide) rc = celerite_adjoint_scan(t, resid, diag, n_diag, n, cf, n_draw, nullptr, state, cg, st, 1);
-          if (rc != EXO_OK) return rc;
-          ss = fork_side();
-          rc = celerite_adjoint_scan(t, resid, diag, n_diag, n, cf, n_draw, nullptr, state, cg, ss ? ss->s : st, wide ? 3 : 2);
+          if (cg.lane) {
+            fwd_cg.which = 1;
+            if (!launch_fwd()) return EXO_ERR_INVALID_ARGUMENT;
+            fwd_cg.which = 2;
+          }
+          if (!wide) {
+            const int rc = celerite_adjoint_scan(t, resid, diag, n_diag, n, cf, n_draw, nullptr, state, cg, st, 1);
+            if (rc != EXO_OK) return rc;
+          }
+          ss = fork_side(st);
+          const int rc = celerite_adjoint_scan(t, resid, diag, n_diag, n, cf, n_draw, nullptr, state, cg, ss ? ss->s : st, wide ? 3 : 2);
           if (rc != EXO_OK) return rc;
         }
-        EXO_GP_DISPATCH(J, hipLaunchKernelGGL((celerite_chunk_fwd_kernel<JJ>), cgrid, block, 0, st, t, resid, diag, n_diag,
-                                              n, cf, n_draw, state, cg))
-      }
-      if (ss) {   // join: the sums below (and the caller) wait for the second stream
-        if (hipEventRecord(ss->join, ss->s) != hipSuccess || hipStreamWaitEvent(st, ss->join, 0) != hipSuccess) return EXO_ERR_LAUNCH;
-      }   // (no second stream to be had: the scan went in line, before the chunk kernel -- the reverse call expects it done)
+        if (cg.lane) return launch_fwd() ? EXO_OK : EXO_ERR_INVALID_ARGUMENT;
+        const bool launched = with_J<1, EXO_GP_MAX_J>(J, [&](auto jj) {
+          hipLaunchKernelGGL((celerite_chunk_fwd_kernel<decltype(jj)::value>), cgrid, block, 0, st, t, resid, diag, n_diag, n, cf, n_draw,
+                             state, cg);
+        });
+        return launched ? EXO_OK : EXO_ERR_INVALID_ARGUMENT;
+      };
+      const int rc = chunk_recurrences();
+      // join: the sums below (and the caller) wait for the second stream.  (No second stream to be had: the scan went in line,
+      // before the chunk kernel -- the reverse call expects it done.)
+      const bool joined = !ss || (hipEventRecord(ss->join, ss->s) == hipSuccess && hipStreamWaitEvent(st, ss->join, 0) == hipSuccess);
+      if (rc != EXO_OK) return rc;
+      if (!joined) return EXO_ERR_LAUNCH;
       {
         const int S = chunk_sum_slices(cg.C, 3, n_draw, 16);   // (the last kernel's lanes add the S partials themselves)
         hipLaunchKernelGGL(celerite_chunk_slice_sum_kernel, dim3(per_draw.x, 3, (unsigned)S), block, 0, st, state + ws.off_part(), 3,
@@ -2967,11 +2849,16 @@ static int celerite_fwd(const double* t, Series resid, const double* diag, int64
       if (launch_status() != EXO_OK) return EXO_ERR_LAUNCH;
       only_flagged = state + ws.off_flag();
     }
-    EXO_GP_DISPATCH_SEQ(J, hipLaunchKernelGGL((celerite_fwd_kernel<JJ, true>), grid, block, 0, st, t, resid, diag, n_diag, n,
-                                          cf, n_draw, loglike, state, only_flagged, cg, n_slice))
-  } else {
-    EXO_GP_DISPATCH_SEQ(J, hipLaunchKernelGGL((celerite_fwd_kernel<JJ, false>), grid, block, 0, st, t, resid, diag, n_diag, n,
-                                          cf, n_draw, loglike, state, (const double*)nullptr, ChunkGeom{}, 0))
+    if (!with_J<1, EXO_GP_MAX_J>(J, [&](auto jj) {
+          hipLaunchKernelGGL((celerite_fwd_kernel<decltype(jj)::value, true>), grid, block, 0, st, t, resid, diag, n_diag, n, cf, n_draw,
+                             loglike, state, only_flagged, cg, n_slice);
+        }))
+      return EXO_ERR_INVALID_ARGUMENT;
+  } else if (!with_J<1, EXO_GP_MAX_J>(J, [&](auto jj) {
+               hipLaunchKernelGGL((celerite_fwd_kernel<decltype(jj)::value, false>), grid, block, 0, st, t, resid, diag, n_diag, n, cf,
+                                  n_draw, loglike, state, (const double*)nullptr, ChunkGeom{}, 0);
+             })) {
+    return EXO_ERR_INVALID_ARGUMENT;
   }
   return launch_status();
 }
@@ -3007,19 +2894,23 @@ static int celerite_vjp(const double* t, Series resid, const double* diag, int64
       if (rc != EXO_OK) return rc;
     }
     if (cg.lane) {
-      auto launch_vjp = [&](auto sp_tag) -> int {
-        constexpr int SP = decltype(sp_tag)::value;
-        EXO_GP_LAYOUTS(J, cf, hipLaunchKernelGGL((celerite_chunk1_vjp_kernel<(JJ <= kLaneMaxJ ? JJ : 1), NR, SP>), egrid, block, 0,
-                                                 st, t, resid, diag, n_diag, n, cf, n_draw, gloglike, wstate, cg, gresid,
-                                                 gdiag, gsign),
-                       hipLaunchKernelGGL(celerite_chunk1_vjp_mixed_kernel<SP>, dim3(egrid.x + 1, egrid.y, 2), block, 0, st, t, resid, diag,
-                                          n_diag, n, cf, n_draw, gloglike, wstate, cg, gresid, gdiag, gsign))
-        return EXO_OK;
-      };
-      EXO_GP_BY_SERIES(resid, launch_vjp)
-    } else {
-      EXO_GP_DISPATCH(J, hipLaunchKernelGGL((celerite_chunk_vjp_kernel<JJ>), cgrid, block, 0, st, t, n, cf, n_draw,
-                                            gloglike, wstate, cg, gresid, gdiag, gsign, resid))
+      if (!with_layouts(
+              cf, resid,
+              [&](auto jj, auto nr, auto sp) {
+                constexpr int JJ = decltype(jj)::value;
+                hipLaunchKernelGGL((celerite_chunk1_vjp_kernel<(JJ <= kLaneMaxJ ? JJ : 1), decltype(nr)::value, decltype(sp)::value>), egrid,
+                                   block, 0, st, t, resid, diag, n_diag, n, cf, n_draw, gloglike, wstate, cg, gresid, gdiag, gsign);
+              },
+              [&](auto sp) {
+                hipLaunchKernelGGL(celerite_chunk1_vjp_mixed_kernel<decltype(sp)::value>, dim3(egrid.x + 1, egrid.y, 2), block, 0, st, t,
+                                   resid, diag, n_diag, n, cf, n_draw, gloglike, wstate, cg, gresid, gdiag, gsign);
+              }))
+        return EXO_ERR_INVALID_ARGUMENT;
+    } else if (!with_J<1, EXO_GP_MAX_J>(J, [&](auto jj) {
+                 hipLaunchKernelGGL((celerite_chunk_vjp_kernel<decltype(jj)::value>), cgrid, block, 0, st, t, n, cf, n_draw, gloglike,
+                                    wstate, cg, gresid, gdiag, gsign, resid);
+               })) {
+      return EXO_ERR_INVALID_ARGUMENT;
     }
     {
       const int K = 4 * J + 1, S = chunk_sum_slices(cg.C, K, n_draw);
@@ -3035,9 +2926,11 @@ static int celerite_vjp(const double* t, Series resid, const double* diag, int64
     if (launch_status() != EXO_OK) return EXO_ERR_LAUNCH;
     only_flagged = state + ws.off_flag();
   }
-  EXO_GP_DISPATCH_SEQ(J, hipLaunchKernelGGL((celerite_vjp_kernel<JJ>), grid, block, 0, st, t, diag, n_diag, n, cf, n_draw,
-                                        gloglike, state, gresid, gdiag, gdiag_sum, gcoef_real, gcoef_complex,
-                                        only_flagged, gsign, resid, cg))
+  if (!with_J<1, EXO_GP_MAX_J>(J, [&](auto jj) {
+        hipLaunchKernelGGL((celerite_vjp_kernel<decltype(jj)::value>), grid, block, 0, st, t, diag, n_diag, n, cf, n_draw, gloglike,
+                           state, gresid, gdiag, gdiag_sum, gcoef_real, gcoef_complex, only_flagged, gsign, resid, cg);
+      }))
+    return EXO_ERR_INVALID_ARGUMENT;
   return launch_status();
 }
 
@@ -3171,8 +3064,11 @@ int exo_celerite_dot_tril_f64(const double* t, const double* diag, int64_t n_dia
     return EXO_ERR_INVALID_ARGUMENT;
   const Coefs cf{coef_real, coef_complex, pair_kind, n_real, n_complex, n > 0 ? t : nullptr};
   const dim3 grid((unsigned)((n_draw + kWave - 1) / kWave)), block(kWave);
-  EXO_GP_DISPATCH_SEQ(cf.J(), hipLaunchKernelGGL((celerite_dot_tril_kernel<JJ>), grid, block, 0, (hipStream_t)stream, t, diag,
-                                             n_diag, n, cf, n_draw, x, z))
+  if (!with_J<1, EXO_GP_MAX_J>(cf.J(), [&](auto jj) {
+        hipLaunchKernelGGL((celerite_dot_tril_kernel<decltype(jj)::value>), grid, block, 0, (hipStream_t)stream, t, diag, n_diag, n, cf,
+                           n_draw, x, z);
+      }))
+    return EXO_ERR_INVALID_ARGUMENT;
   return launch_status();
 }
 
@@ -3185,8 +3081,11 @@ int exo_celerite_predict_f64(const double* t, int64_t n, const double* alpha, co
     return EXO_ERR_INVALID_ARGUMENT;
   const Coefs cf{coef_real, coef_complex, pair_kind, n_real, n_complex, n > 0 ? t : nullptr};
   const dim3 grid((unsigned)((n_draw + kWave - 1) / kWave)), block(kWave);
-  EXO_GP_DISPATCH_SEQ(cf.J(), hipLaunchKernelGGL((celerite_predict_kernel<JJ>), grid, block, 0, (hipStream_t)stream, t, n, alpha,
-                                             cf, n_draw, tq, m, mu))
+  if (!with_J<1, EXO_GP_MAX_J>(cf.J(), [&](auto jj) {
+        hipLaunchKernelGGL((celerite_predict_kernel<decltype(jj)::value>), grid, block, 0, (hipStream_t)stream, t, n, alpha, cf, n_draw,
+                           tq, m, mu);
+      }))
+    return EXO_ERR_INVALID_ARGUMENT;
   return launch_status();
 }
 

@@ -27,6 +27,7 @@
 #define EXO_WAVE_ANY(c) (c)
 #else
 #include <hip/hip_runtime.h>
+#include <type_traits>
 #define EXO_HD __device__ __forceinline__
 // 64-wide wavefront votes (gfx950): uniform branch conditions
 #define EXO_WAVE_ALL(c) (__all((int)(c)))
@@ -679,6 +680,13 @@ inline bool zero_fill_async(double* p, int64_t n, hipStream_t st) {
   if (n <= 0) return true;
   hipLaunchKernelGGL(zero_fill_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, p, n);
   return hipGetLastError() == hipSuccess;
+}
+
+// f(std::true_type{}) or f(std::false_type{}): a run-time flag as a kernel's template argument
+template <class F>
+inline void with_flag(bool b, F&& f) {
+  if (b) f(std::true_type{});
+  else f(std::false_type{});
 }
 #endif
 

@@ -2528,26 +2528,23 @@ inline Workspace carve(void* base, int64_t n_draw, int bpd, int tpb, int n_plane
 
 constexpr uint32_t kFlagNoFlux = 0x80000000u;  // internal: scan kernel must not touch flux
 
-// scan kernel dispatch on (secondary, exact fp64 classification requested)
-#define EXO_LAUNCH_SCAN_V(VEC, TTV, FLAGS, ...)                                                           \
-  do {                                                                                                    \
-    const bool sec_ = (FLAGS) & EXO_FLAG_SECONDARY, exact_ = (FLAGS) & EXO_FLAG_EXACT_SCAN;               \
-    if (sec_ && exact_) hipLaunchKernelGGL((transit_scan_kernel<true, false, VEC, TTV>), __VA_ARGS__);    \
-    else if (sec_) hipLaunchKernelGGL((transit_scan_kernel<true, true, VEC, TTV>), __VA_ARGS__);          \
-    else if (exact_) hipLaunchKernelGGL((transit_scan_kernel<false, false, VEC, TTV>), __VA_ARGS__);      \
-    else hipLaunchKernelGGL((transit_scan_kernel<false, true, VEC, TTV>), __VA_ARGS__);                   \
-  } while (0)
-// 16-B loads of t: pairs must not straddle the end (even n_cad) and t must be 16-B aligned.
-// The timing-variation path (HAS_TTV) has one variant: per-cadence table lookups dwarf the loads.
-#define EXO_LAUNCH_SCAN(N_CAD, T, HAS_TTV, FLAGS, ...)                                         \
-  do {                                                                                         \
-    if (HAS_TTV)                                                                               \
-      EXO_LAUNCH_SCAN_V(false, true, FLAGS, __VA_ARGS__);                                      \
-    else if (((N_CAD) & 1) == 0 && (reinterpret_cast<uintptr_t>(T) & 15) == 0)                 \
-      EXO_LAUNCH_SCAN_V(true, false, FLAGS, __VA_ARGS__);                                      \
-    else                                                                                       \
-      EXO_LAUNCH_SCAN_V(false, false, FLAGS, __VA_ARGS__);                                     \
-  } while (0)
+// scan kernel launch on (secondary, exact fp64 classification requested) and the loads of t: VEC -- 16-B loads, pairs must
+// not straddle the end (even n_cad) and t must be 16-B aligned.  The timing-variation path (TTV) has one variant: per-cadence
+// table lookups dwarf the loads.
+template <class... Args>
+inline void launch_scan(uint32_t flags, bool has_ttv, dim3 grid, hipStream_t st, const double* t, int64_t n_cad, Args... args) {
+  auto launch = [&](auto vec, auto ttv) {
+    exo::with_flag(flags & EXO_FLAG_SECONDARY, [&](auto sec) {
+      exo::with_flag(flags & EXO_FLAG_EXACT_SCAN, [&](auto exact) {
+        hipLaunchKernelGGL((transit_scan_kernel<decltype(sec)::value, !decltype(exact)::value, decltype(vec)::value, decltype(ttv)::value>),
+                           grid, dim3(kBlock), 0, st, t, n_cad, args...);
+      });
+    });
+  };
+  if (has_ttv) launch(std::false_type{}, std::true_type{});
+  else if ((n_cad & 1) == 0 && (reinterpret_cast<uintptr_t>(t) & 15) == 0) launch(std::true_type{}, std::false_type{});
+  else launch(std::false_type{}, std::false_type{});
+}
 
 // the windows of the scan kernel's first test: not needed when the caller asks for the exact
 // fp64 scan of every cadence
@@ -2650,21 +2647,23 @@ struct Chi2Args {
   int64_t n_ivar;
   double* chi2;
 };
-template <bool G, bool SEC>
-inline void launch_runs_kernel(bool ldelay, dim3 hgrid, hipStream_t st, const double* t, int64_t n_cad, const double* texp,
-                               int64_t n_texp, const double* stencil_dt, const double* stencil_w, int32_t n_sub,
-                               const double* params, const double* ld, int32_t n_planet, uint32_t flags, int n_ev,
-                               const RunLists& rl, const double* gflux, const double* gsparse, double* vals, int32_t* vcad,
-                               double* fill, double* partial, const FinishArgs& fin) {
-  const Ttv no_ttv{nullptr, nullptr, nullptr, 0};
-  if (ldelay)
-    hipLaunchKernelGGL((transit_runs_kernel<G, SEC, true>), hgrid, dim3(kBlock), 0, st, t, n_cad, texp, n_texp, stencil_dt,
-                       stencil_w, (int)n_sub, params, ld, (int)n_planet, flags, n_ev, rl, gflux, gsparse, vals, vcad, fill,
-                       partial, (int64_t)0, no_ttv, fin);
-  else
-    hipLaunchKernelGGL((transit_runs_kernel<G, SEC, false>), hgrid, dim3(kBlock), 0, st, t, n_cad, texp, n_texp, stencil_dt,
-                       stencil_w, (int)n_sub, params, ld, (int)n_planet, flags, n_ev, rl, gflux, gsparse, vals, vcad, fill,
-                       partial, (int64_t)0, no_ttv, fin);
+// the arguments of transit_runs_kernel that every launch of a sweep shares
+struct RunsCommon {
+  dim3 grid;
+  hipStream_t st;
+  const double *t, *texp, *stencil_dt, *stencil_w, *params, *ld;
+  int64_t n_cad, n_texp;
+  int n_sub, n_planet, n_ev;
+  uint32_t flags;
+  RunLists rl;
+  Ttv ttv;   // the sweep's timing tables (edges == nullptr: none)
+};
+template <bool G, bool SEC, bool LDELAY = false, bool CHI2 = false, bool TTV = false, bool JAC = false>
+inline void launch_runs(const RunsCommon& a, const double* gflux, const double* gsparse, double* vals, int32_t* vcad, double* fill,
+                        double* partial, const FinishArgs& fin, int64_t chi2_nw = 0) {
+  hipLaunchKernelGGL((transit_runs_kernel<G, SEC, LDELAY, CHI2, TTV, JAC>), a.grid, dim3(kBlock), 0, a.st, a.t, a.n_cad, a.texp,
+                     a.n_texp, a.stencil_dt, a.stencil_w, a.n_sub, a.params, a.ld, a.n_planet, a.flags, a.n_ev, a.rl, gflux, gsparse,
+                     vals, vcad, fill, partial, chi2_nw, a.ttv, fin);
 }
 inline int launch_runs_sweep(const double* t, int64_t n_cad, const double* texp, int64_t n_texp, const double* stencil_dt,
                              const double* stencil_w, int32_t n_sub, const double* params, const double* ld,
@@ -2711,96 +2710,78 @@ inline int launch_runs_sweep(const double* t, int64_t n_cad, const double* texp,
   // the values are kept when somebody reads them: the dense output's last kernel, or the caller (sparse)
   double* vals = (flux || sparse) ? w.vals : nullptr;
   double* fill = sparse ? nullptr : flux;
-  const dim3 hgrid((unsigned)w.hb, (unsigned)n_draw);
   const bool ldelay = flags & EXO_FLAG_LIGHT_DELAY;
+  const Ttv no_ttv{nullptr, nullptr, nullptr, 0};
+  const RunsCommon ra{dim3((unsigned)w.hb, (unsigned)n_draw), st, t, texp, stencil_dt, stencil_w, params, ld, n_cad, n_texp, (int)n_sub,
+                      (int)n_planet, n_ev, flags, w.rl, has_ttv ? *ttv : no_ttv};
   // a draw that is one block's work is finished by that block (gradients from its partials, values to their cadences):
   // no transit_finish_kernel launch
   // (not with a cadence-major flux: a draw's values land in lines other blocks zero-fill -- after the sweep, then)
   const bool cmaj = flags & EXO_FLAG_CADENCE_MAJOR;
   const bool fold = !(cmaj && flux) && w.hb == 1;
   const FinishArgs fin{gparams, gld, chi2 ? chi2->chi2 : flux_dot, fold ? 1 : 0, w.done}, no_fin{nullptr, nullptr, nullptr, 0, nullptr};
-#define EXO_LAUNCH_RUNS(G, GFLUX, GSP, VALS, VCAD, FILL, PARTIAL, FIN)                                                    \
-  if (secondary)                                                                                                          \
-    launch_runs_kernel<G, true>(ldelay, hgrid, st, t, n_cad, texp, n_texp, stencil_dt, stencil_w, n_sub, params, ld,      \
-                                n_planet, flags, n_ev, w.rl, GFLUX, GSP, VALS, VCAD, FILL, PARTIAL, FIN);                  \
-  else                                                                                                                    \
-    launch_runs_kernel<G, false>(ldelay, hgrid, st, t, n_cad, texp, n_texp, stencil_dt, stencil_w, n_sub, params, ld,     \
-                                 n_planet, flags, n_ev, w.rl, GFLUX, GSP, VALS, VCAD, FILL, PARTIAL, FIN)
+  // the sweeps without timing tables, Jacobian or fused likelihood: occultations and light delay as the flags say
+  auto plain = [&](auto g, const double* gf, const double* gsp, double* v, int32_t* vc, double* fl, double* part, const FinishArgs& f) {
+    exo::with_flag(secondary, [&](auto sec) {
+      exo::with_flag(ldelay, [&](auto ldl) {
+        launch_runs<decltype(g)::value, decltype(sec)::value, decltype(ldl)::value>(ra, gf, gsp, v, vc, fl, part, f);
+      });
+    });
+  };
   if (chi2 && n_planet == 1 && !secondary && n_sub == 1) {
     // one planet, one sample per cadence: the cotangent of a cadence's flux needs nothing but that flux -- value and
     // gradient in ONE evaluation per solved cadence (the misfit comes out of the "dot" slot of the partials)
     if (has_ttv)
-      hipLaunchKernelGGL((transit_runs_kernel<true, false, false, true, true>), hgrid, block, 0, st, t, n_cad, texp, n_texp,
-                         stencil_dt, stencil_w, (int)n_sub, params, ld, (int)n_planet, flags, n_ev, w.rl, chi2->obs, chi2->ivar,
-                         nullptr, nullptr, nullptr, w.partial, chi2->n_ivar, *ttv, fin);
+      launch_runs<true, false, false, true, true>(ra, chi2->obs, chi2->ivar, nullptr, nullptr, nullptr, w.partial, fin, chi2->n_ivar);
     else if (ldelay)
-      hipLaunchKernelGGL((transit_runs_kernel<true, false, true, true>), hgrid, block, 0, st, t, n_cad, texp, n_texp, stencil_dt,
-                         stencil_w, (int)n_sub, params, ld, (int)n_planet, flags, n_ev, w.rl, chi2->obs, chi2->ivar, nullptr,
-                         nullptr, nullptr, w.partial, chi2->n_ivar, Ttv{nullptr, nullptr, nullptr, 0}, fin);
+      launch_runs<true, false, true, true>(ra, chi2->obs, chi2->ivar, nullptr, nullptr, nullptr, w.partial, fin, chi2->n_ivar);
     else
-      hipLaunchKernelGGL((transit_runs_kernel<true, false, false, true>), hgrid, block, 0, st, t, n_cad, texp, n_texp, stencil_dt,
-                         stencil_w, (int)n_sub, params, ld, (int)n_planet, flags, n_ev, w.rl, chi2->obs, chi2->ivar, nullptr,
-                         nullptr, nullptr, w.partial, chi2->n_ivar, Ttv{nullptr, nullptr, nullptr, 0}, fin);
+      launch_runs<true, false, false, true>(ra, chi2->obs, chi2->ivar, nullptr, nullptr, nullptr, w.partial, fin, chi2->n_ivar);
     if (launch_status() != EXO_OK) return EXO_ERR_LAUNCH;
     if (fold) return EXO_OK;
     hipLaunchKernelGGL(transit_finish_kernel, dim3((unsigned)n_draw), dim3(n_draw <= 256 ? 1024 : kBlock), 0, st, w.partial, w.hb,
                        (int)n_planet, secondary, gparams, gld, chi2->chi2, n_cad, flags, n_ev, w.rl, nullptr, w.vcad, nullptr,
-                       nullptr, 0, nullptr, has_ttv ? *ttv : Ttv{nullptr, nullptr, nullptr, 0});
+                       nullptr, 0, nullptr, ra.ttv);
     return launch_status();
   }
   if (has_ttv && chi2) {
     // value sweep into the sparse output, residuals + cotangents on it, gradient sweep reading them (gshift included)
-    hipLaunchKernelGGL((transit_runs_kernel<false, false, false, false, true>), hgrid, block, 0, st, t, n_cad, texp, n_texp,
-                       stencil_dt, stencil_w, (int)n_sub, params, ld, (int)n_planet, flags, n_ev, w.rl, nullptr, nullptr, w.vals,
-                       w.vcad, nullptr, nullptr, (int64_t)0, *ttv, no_fin);
+    launch_runs<false, false, false, false, true>(ra, nullptr, nullptr, w.vals, w.vcad, nullptr, nullptr, no_fin);
     hipLaunchKernelGGL(transit_residual_kernel, dim3(kResidualBlocks, (unsigned)n_draw), block, 0, st, n_cad, (int)n_planet,
                        n_ev, w.rl, w.vals, w.vcad, chi2->obs, chi2->ivar, chi2->n_ivar, w.gvals, w.chi2_part);
-    hipLaunchKernelGGL((transit_runs_kernel<true, false, false, false, true>), hgrid, block, 0, st, t, n_cad, texp, n_texp,
-                       stencil_dt, stencil_w, (int)n_sub, params, ld, (int)n_planet, flags, n_ev, w.rl, nullptr, w.gvals, nullptr,
-                       nullptr, nullptr, w.partial, (int64_t)0, *ttv, no_fin);
+    launch_runs<true, false, false, false, true>(ra, nullptr, w.gvals, nullptr, nullptr, nullptr, w.partial, no_fin);
   } else if (has_ttv) {
     // (transits only, no light delay: runs_path)
     if (grad)
-      hipLaunchKernelGGL((transit_runs_kernel<true, false, false, false, true>), hgrid, block, 0, st, t, n_cad, texp, n_texp,
-                         stencil_dt, stencil_w, (int)n_sub, params, ld, (int)n_planet, flags, n_ev, w.rl, gflux, nullptr, vals,
-                         fill ? w.vcad : nullptr, fill, w.partial, (int64_t)0, *ttv, fin);
+      launch_runs<true, false, false, false, true>(ra, gflux, nullptr, vals, fill ? w.vcad : nullptr, fill, w.partial, fin);
     else
-      hipLaunchKernelGGL((transit_runs_kernel<false, false, false, false, true>), hgrid, block, 0, st, t, n_cad, texp, n_texp,
-                         stencil_dt, stencil_w, (int)n_sub, params, ld, (int)n_planet, flags, n_ev, w.rl, nullptr, nullptr, vals,
-                         fill ? w.vcad : nullptr, fill, nullptr, (int64_t)0, *ttv, fin);
+      launch_runs<false, false, false, false, true>(ra, nullptr, nullptr, vals, fill ? w.vcad : nullptr, fill, nullptr, fin);
   } else if (chi2) {
-    EXO_LAUNCH_RUNS(false, nullptr, nullptr, w.vals, w.vcad, nullptr, nullptr, no_fin);
+    plain(std::false_type{}, nullptr, nullptr, w.vals, w.vcad, nullptr, nullptr, no_fin);
     hipLaunchKernelGGL(transit_residual_kernel, dim3(kResidualBlocks, (unsigned)n_draw), block, 0, st, n_cad, (int)n_planet,
                        n_ev, w.rl, w.vals, w.vcad, chi2->obs, chi2->ivar, chi2->n_ivar, w.gvals, w.chi2_part);
-    EXO_LAUNCH_RUNS(true, nullptr, w.gvals, nullptr, nullptr, nullptr, w.partial, no_fin);
+    plain(std::true_type{}, nullptr, w.gvals, nullptr, nullptr, nullptr, w.partial, no_fin);
   } else if (gvals) {
     // (the values stay as the forward sweep left them: the GP's reverse pass has read them, nobody reads them again)
-    EXO_LAUNCH_RUNS(true, nullptr, gvals, nullptr, nullptr, nullptr, w.partial, fin);
+    plain(std::true_type{}, nullptr, gvals, nullptr, nullptr, nullptr, w.partial, fin);
   } else if (grad) {
-    EXO_LAUNCH_RUNS(true, gflux, nullptr, vals, fill ? w.vcad : nullptr, fill, w.partial, fin);
+    plain(std::true_type{}, gflux, nullptr, vals, fill ? w.vcad : nullptr, fill, w.partial, fin);
   } else if (jac) {
     // value sweep that leaves every solved cadence's row of derivatives (transit_runs_kernel<.., JAC>; the cadence index
     // is written whatever the output: the contraction gathers the cotangent through it)
-    const Ttv no_ttv{nullptr, nullptr, nullptr, 0};
-    if (secondary)
-      hipLaunchKernelGGL((transit_runs_kernel<true, true, false, false, false, true>), hgrid, block, 0, st, t, n_cad, texp, n_texp,
-                         stencil_dt, stencil_w, (int)n_sub, params, ld, (int)n_planet, flags, n_ev, w.rl, nullptr, nullptr, vals,
-                         w.vcad, fill, jac, (int64_t)0, no_ttv, fin);
-    else
-      hipLaunchKernelGGL((transit_runs_kernel<true, false, false, false, false, true>), hgrid, block, 0, st, t, n_cad, texp, n_texp,
-                         stencil_dt, stencil_w, (int)n_sub, params, ld, (int)n_planet, flags, n_ev, w.rl, nullptr, nullptr, vals,
-                         w.vcad, fill, jac, (int64_t)0, no_ttv, fin);
+    exo::with_flag(secondary, [&](auto sec) {
+      launch_runs<true, decltype(sec)::value, false, false, false, true>(ra, nullptr, nullptr, vals, w.vcad, fill, jac, fin);
+    });
   } else {
-    EXO_LAUNCH_RUNS(false, nullptr, nullptr, vals, fill ? w.vcad : nullptr, fill, nullptr, fin);
+    plain(std::false_type{}, nullptr, nullptr, vals, fill ? w.vcad : nullptr, fill, nullptr, fin);
   }
-#undef EXO_LAUNCH_RUNS
   if (launch_status() != EXO_OK) return EXO_ERR_LAUNCH;
   const bool three_sweeps = chi2 != nullptr;   // (the single-pass likelihood returned above)
   if ((grad || fill) && (!fold || three_sweeps))
     hipLaunchKernelGGL(transit_finish_kernel, dim3((unsigned)n_draw), dim3(n_draw <= 256 ? 1024 : kBlock), 0, st,
                        grad ? w.partial : nullptr, w.hb, (int)n_planet, secondary, gparams, gld, flux_dot, n_cad, flags, n_ev,
                        w.rl, chi2 ? nullptr : vals, w.vcad, fill, chi2 ? w.chi2_part : nullptr, kResidualBlocks,
-                       chi2 ? chi2->chi2 : nullptr, (has_ttv && grad) ? *ttv : Ttv{nullptr, nullptr, nullptr, 0});
+                       chi2 ? chi2->chi2 : nullptr, grad ? ra.ttv : no_ttv);
   return launch_status();
 }
 
@@ -3167,6 +3148,59 @@ int exo_transit_sparse_scatter_f64(const void* workspace, int64_t workspace_byte
   return launch_status();
 }
 
+// A sweep after the entry points' own checks: the run-enumeration path where it applies (runs_path), else the list path --
+// windows, scan, heavy kernel and, with a gradient (gflux != nullptr), the reduce kernel.  ttv.edges == nullptr: no timing
+// variations; flux == nullptr: no values (the list path's scan skips the fill).
+static int transit_sweep(const double* t, int64_t n_cad, const double* texp, int64_t n_texp, const double* stencil_dt,
+                         const double* stencil_w, int32_t n_sub, const double* params, const double* ld, int64_t n_draw,
+                         int32_t n_planet, uint32_t flags, const Ttv& ttv, const double* gflux, double* flux, double* gparams,
+                         double* gld, double* flux_dot, void* workspace, int64_t workspace_bytes, hipStream_t st, void* ev_start,
+                         void* ev_stop) {
+  const bool has_ttv = ttv.edges != nullptr;
+  if ((flags & EXO_FLAG_CADENCE_MAJOR) && (flags & EXO_FLAG_PER_PLANET)) return EXO_ERR_INVALID_ARGUMENT;
+  if (runs_path(has_ttv, n_texp, flags)) {
+    const RunWs rw = carve_runs(workspace, n_cad, n_draw, n_planet);
+    if (!workspace || workspace_bytes < rw.bytes) return EXO_ERR_WORKSPACE;
+    if (ev_start) (void)hipEventRecord((hipEvent_t)ev_start, st);
+    const int rc = launch_runs_sweep(t, n_cad, texp, n_texp, stencil_dt, stencil_w, n_sub, params, ld, n_draw, n_planet,
+                                     flags, gflux, flux, gparams, gld, flux_dot, rw, st, nullptr, &ttv);
+    if (ev_stop) (void)hipEventRecord((hipEvent_t)ev_stop, st);
+    return rc;
+  }
+  if (flags & (EXO_FLAG_SPARSE | EXO_FLAG_LIGHT_DELAY | EXO_FLAG_CADENCE_MAJOR)) return EXO_ERR_INVALID_ARGUMENT;   // run-enumeration path only
+  int bpd, tpb;
+  transit_geometry(n_cad, n_draw, &bpd, &tpb);
+  const Workspace w = carve(workspace, n_draw, bpd, tpb, n_planet);
+  if (!workspace || workspace_bytes < w.bytes) return EXO_ERR_WORKSPACE;
+  const bool grad = gflux != nullptr, secondary = flags & EXO_FLAG_SECONDARY;
+  if (ev_start) (void)hipEventRecord((hipEvent_t)ev_start, st);
+  launch_windows(params, n_draw, n_planet, flags, w.windows, st);
+  const ScanPlan sp = scan_plan(flags, bpd, n_draw, n_planet, n_texp, flux != nullptr);
+  launch_scan(flags, has_ttv, sp.grid, st, t, n_cad, texp, n_texp, stencil_dt, n_sub, params, n_planet, sp.flags, tpb, bpd, n_draw,
+              sp.n_classify, flux, w.counts, w.list, w.windows, ttv);
+  if (launch_status() != EXO_OK) return EXO_ERR_LAUNCH;
+  const int merge = heavy_merge(n_draw, bpd);
+  const int nhb = (bpd + merge - 1) / merge;
+  const double* hwin = ((flags & EXO_FLAG_EXACT_SCAN) && !(flags & EXO_FLAG_WINDOW)) ? nullptr : w.windows;
+  exo::with_flag(grad, [&](auto g) {
+    exo::with_flag(secondary, [&](auto sec) {
+      exo::with_flag(has_ttv, [&](auto tv) {
+        hipLaunchKernelGGL((transit_heavy_kernel<decltype(g)::value, decltype(sec)::value, decltype(tv)::value>),
+                           dim3((unsigned)nhb, (unsigned)n_draw), dim3(kBlock), 0, st, t, n_cad, texp, n_texp, stencil_dt, stencil_w,
+                           n_sub, params, ld, n_planet, flags, tpb, bpd, merge, w.counts, w.list, gflux, flux,
+                           grad ? w.partial : nullptr, hwin, ttv);
+      });
+    });
+  });
+  if (grad) {
+    if (launch_status() != EXO_OK) return EXO_ERR_LAUNCH;
+    hipLaunchKernelGGL(transit_vjp_reduce_kernel, dim3((unsigned)n_draw), dim3(kBlock), 0, st, w.partial, nhb, n_planet, secondary,
+                       gparams, gld, flux_dot);
+  }
+  if (ev_stop) (void)hipEventRecord((hipEvent_t)ev_stop, st);
+  return launch_status();
+}
+
 // forward sweep; ttv.edges == nullptr: no timing variations
 static int transit_fwd(const double* t, int64_t n_cad, const double* texp, int64_t n_texp, const double* stencil_dt,
                        const double* stencil_w, int32_t n_sub, const double* params, const double* ld,
@@ -3176,48 +3210,8 @@ static int transit_fwd(const double* t, int64_t n_cad, const double* texp, int64
   if (n_cad == 0 || n_draw == 0) return EXO_OK;
   if (!t || !params || !ld || (!flux && !(flags & EXO_FLAG_SPARSE)) || (n_texp > 0 && (!texp || !stencil_dt || !stencil_w)))
     return EXO_ERR_INVALID_ARGUMENT;
-  const bool has_ttv = ttv.edges != nullptr;
-  hipStream_t st = (hipStream_t)stream;
-  if ((flags & EXO_FLAG_CADENCE_MAJOR) && (flags & EXO_FLAG_PER_PLANET)) return EXO_ERR_INVALID_ARGUMENT;
-  if (runs_path(has_ttv, n_texp, flags)) {
-    const RunWs rw = carve_runs(workspace, n_cad, n_draw, n_planet);
-    if (!workspace || workspace_bytes < rw.bytes) return EXO_ERR_WORKSPACE;
-    if (ev_start) (void)hipEventRecord((hipEvent_t)ev_start, st);
-    const int rc = launch_runs_sweep(t, n_cad, texp, n_texp, stencil_dt, stencil_w, n_sub, params, ld, n_draw, n_planet,
-                                     flags, nullptr, flux, nullptr, nullptr, nullptr, rw, st, nullptr, &ttv);
-    if (ev_stop) (void)hipEventRecord((hipEvent_t)ev_stop, st);
-    return rc;
-  }
-  if (flags & (EXO_FLAG_SPARSE | EXO_FLAG_LIGHT_DELAY | EXO_FLAG_CADENCE_MAJOR)) return EXO_ERR_INVALID_ARGUMENT;   // run-enumeration path only
-  int bpd, tpb;
-  transit_geometry(n_cad, n_draw, &bpd, &tpb);
-  const Workspace w = carve(workspace, n_draw, bpd, tpb, n_planet);
-  if (!workspace || workspace_bytes < w.bytes) return EXO_ERR_WORKSPACE;
-  const dim3 block(kBlock);
-  const bool secondary = flags & EXO_FLAG_SECONDARY;
-  if (ev_start) (void)hipEventRecord((hipEvent_t)ev_start, st);
-  launch_windows(params, n_draw, n_planet, flags, w.windows, st);
-  const ScanPlan sp = scan_plan(flags, bpd, n_draw, n_planet, n_texp, true);
-  EXO_LAUNCH_SCAN(n_cad, t, has_ttv, flags, sp.grid, block, 0, st, t, n_cad, texp, n_texp, stencil_dt, n_sub, params,
-                  n_planet, sp.flags, tpb, bpd, n_draw, sp.n_classify, flux, w.counts, w.list, w.windows, ttv);
-  if (launch_status() != EXO_OK) return EXO_ERR_LAUNCH;
-  const int merge = heavy_merge(n_draw, bpd);
-  const dim3 hgrid((unsigned)((bpd + merge - 1) / merge), (unsigned)n_draw);
-  const double* hwin = ((flags & EXO_FLAG_EXACT_SCAN) && !(flags & EXO_FLAG_WINDOW)) ? nullptr : w.windows;
-#define EXO_LAUNCH_HEAVY_FWD(SEC, TTV)                                                                             \
-  hipLaunchKernelGGL((transit_heavy_kernel<false, SEC, TTV>), hgrid, block, 0, st, t, n_cad, texp, n_texp,         \
-                     stencil_dt, stencil_w, n_sub, params, ld, n_planet, flags, tpb, bpd, merge, w.counts, w.list, \
-                     nullptr, flux, nullptr, hwin, ttv)
-  if (has_ttv) {
-    if (secondary) EXO_LAUNCH_HEAVY_FWD(true, true);
-    else EXO_LAUNCH_HEAVY_FWD(false, true);
-  } else {
-    if (secondary) EXO_LAUNCH_HEAVY_FWD(true, false);
-    else EXO_LAUNCH_HEAVY_FWD(false, false);
-  }
-#undef EXO_LAUNCH_HEAVY_FWD
-  if (ev_stop) (void)hipEventRecord((hipEvent_t)ev_stop, st);
-  return launch_status();
+  return transit_sweep(t, n_cad, texp, n_texp, stencil_dt, stencil_w, n_sub, params, ld, n_draw, n_planet, flags, ttv, nullptr, flux,
+                       nullptr, nullptr, nullptr, workspace, workspace_bytes, (hipStream_t)stream, ev_start, ev_stop);
 }
 
 // value + VJP sweep; ttv.edges == nullptr: no timing variations
@@ -3231,11 +3225,10 @@ static int transit_vjp(const double* t, int64_t n_cad, const double* texp, int64
   if (!params || !ld || !gparams || !gld || (n_cad > 0 && (!t || !gflux)) ||
       (n_texp > 0 && (!texp || !stencil_dt || !stencil_w)))
     return EXO_ERR_INVALID_ARGUMENT;
-  const bool has_ttv = ttv.edges != nullptr;
   const bool secondary = flags & EXO_FLAG_SECONDARY;
   hipStream_t st = (hipStream_t)stream;
   // the bins are accumulated into: start from zero
-  if (has_ttv && !exo::zero_fill_async(ttv.gshift, (int64_t)(n_draw * n_planet * (ttv.n_edge + 1)), st))
+  if (ttv.edges && !exo::zero_fill_async(ttv.gshift, (int64_t)(n_draw * n_planet * (ttv.n_edge + 1)), st))
     return EXO_ERR_LAUNCH;
   if (n_cad == 0) {
     if (!exo::zero_fill_async(gparams, (int64_t)(n_draw * n_planet * EXO_NPAR), st))
@@ -3245,51 +3238,9 @@ static int transit_vjp(const double* t, int64_t n_cad, const double* texp, int64
                ? EXO_OK : EXO_ERR_LAUNCH;
   }
   if (n_planet * kNG + 7 > kBlock) return EXO_ERR_INVALID_ARGUMENT;
-  if ((flags & EXO_FLAG_CADENCE_MAJOR) && (flags & EXO_FLAG_PER_PLANET)) return EXO_ERR_INVALID_ARGUMENT;
-  if (runs_path(has_ttv, n_texp, flags)) {
-    const RunWs rw = carve_runs(workspace, n_cad, n_draw, n_planet);
-    if (!workspace || workspace_bytes < rw.bytes) return EXO_ERR_WORKSPACE;
-    if (ev_start) (void)hipEventRecord((hipEvent_t)ev_start, st);
-    const int rc = launch_runs_sweep(t, n_cad, texp, n_texp, stencil_dt, stencil_w, n_sub, params, ld, n_draw, n_planet,
-                                     flags, gflux, flux_out, gparams, gld, flux_dot, rw, st, nullptr, &ttv);
-    if (ev_stop) (void)hipEventRecord((hipEvent_t)ev_stop, st);
-    return rc;
-  }
-  if (flags & (EXO_FLAG_SPARSE | EXO_FLAG_LIGHT_DELAY | EXO_FLAG_CADENCE_MAJOR)) return EXO_ERR_INVALID_ARGUMENT;   // run-enumeration path only
-  int bpd, tpb;
-  transit_geometry(n_cad, n_draw, &bpd, &tpb);
-  const Workspace w = carve(workspace, n_draw, bpd, tpb, n_planet);
-  if (!workspace || workspace_bytes < w.bytes) return EXO_ERR_WORKSPACE;
-  const dim3 block(kBlock);
-  // the forward value is a by-product; without a destination the scan kernel skips the fill
-  double* flux_dst = flux_out;
-  if (ev_start) (void)hipEventRecord((hipEvent_t)ev_start, st);
-  launch_windows(params, n_draw, n_planet, flags, w.windows, st);
-  const ScanPlan sp = scan_plan(flags, bpd, n_draw, n_planet, n_texp, flux_dst != nullptr);
-  EXO_LAUNCH_SCAN(n_cad, t, has_ttv, flags, sp.grid, block, 0, st, t, n_cad, texp, n_texp, stencil_dt, n_sub, params,
-                  n_planet, sp.flags, tpb, bpd, n_draw, sp.n_classify, flux_dst, w.counts, w.list, w.windows, ttv);
-  if (launch_status() != EXO_OK) return EXO_ERR_LAUNCH;
-  const int merge = heavy_merge(n_draw, bpd);
-  const int nhb = (bpd + merge - 1) / merge;
-  const double* hwin = ((flags & EXO_FLAG_EXACT_SCAN) && !(flags & EXO_FLAG_WINDOW)) ? nullptr : w.windows;
-  const dim3 hgrid((unsigned)nhb, (unsigned)n_draw);
-#define EXO_LAUNCH_HEAVY_VJP(SEC, TTV)                                                                             \
-  hipLaunchKernelGGL((transit_heavy_kernel<true, SEC, TTV>), hgrid, block, 0, st, t, n_cad, texp, n_texp,          \
-                     stencil_dt, stencil_w, n_sub, params, ld, n_planet, flags, tpb, bpd, merge, w.counts, w.list, \
-                     gflux, flux_dst, w.partial, hwin, ttv)
-  if (has_ttv) {
-    if (secondary) EXO_LAUNCH_HEAVY_VJP(true, true);
-    else EXO_LAUNCH_HEAVY_VJP(false, true);
-  } else {
-    if (secondary) EXO_LAUNCH_HEAVY_VJP(true, false);
-    else EXO_LAUNCH_HEAVY_VJP(false, false);
-  }
-#undef EXO_LAUNCH_HEAVY_VJP
-  if (launch_status() != EXO_OK) return EXO_ERR_LAUNCH;
-  hipLaunchKernelGGL(transit_vjp_reduce_kernel, dim3((unsigned)n_draw), dim3(kBlock), 0, st, w.partial, nhb,
-                     n_planet, secondary, gparams, gld, flux_dot);
-  if (ev_stop) (void)hipEventRecord((hipEvent_t)ev_stop, st);
-  return launch_status();
+  // (the forward value is a by-product: flux_out == nullptr, none)
+  return transit_sweep(t, n_cad, texp, n_texp, stencil_dt, stencil_w, n_sub, params, ld, n_draw, n_planet, flags, ttv, gflux,
+                       flux_out, gparams, gld, flux_dot, workspace, workspace_bytes, st, ev_start, ev_stop);
 }
 
 static bool ttv_args_ok(const double* edges, const double* shift, int32_t n_edge) {
