@@ -6,7 +6,7 @@ import torch
 from .. import _lib
 from ..ops import SparseLightCurve, _dev, _ptr, _stream, is_cadence_major
 from ..orbits.keplerian import as_tensor
-from .terms import Term
+from .terms import Term, TermSum
 
 __all__ = ["GaussianProcess", "celerite_loglike", "celerite_loglike_sparse"]
 
@@ -300,6 +300,42 @@ def _known_sorted(t):
     return known_sorted(t, unknown=True)
 
 
+def _inverse(t, resid, diag, real, cplx, kind):
+    """(K + diag)^-1 resid per draw (detached), resid (D, N): minus the gradient of the log-likelihood with respect to
+    resid -- one forward and one reverse pass of the recurrences"""
+    with torch.enable_grad():
+        r = resid.detach().requires_grad_(True)
+        ll = celerite_loglike(t.detach(), r, diag.detach().contiguous(), real.detach(), cplx.detach(), pair_kind=kind)
+        (g,) = torch.autograd.grad(ll.sum(), r)
+    return -g
+
+
+# GaussianProcess.predict(return_var=True): the draws go to exo_celerite_predict_var_f64 in slices whose workspace
+# ((N + M) (J + 1) doubles per draw: 16.8 MB at J = 6 and N = M = 150 000) stays within this many bytes -- slices of a
+# multiple of 64 draws (a wave) where one fits
+PREDICT_VAR_WORK_BYTES = 2 << 30
+# GaussianProcess.predict(return_cov=True): the transient arrays of one block of query times -- K2(t, t*) and its solve,
+# (D, N, block) each, and the likelihood's state for the D x block right-hand sides -- stay within this many bytes
+PREDICT_COV_WORK_BYTES = 1 << 30
+
+
+def _k2_dense(real, cplx, kind, tau):
+    """k(tau) of the terms of coefficient arrays real (D, Jr, 2), cplx (D, Jc, 4), kind (D, Jc) or None, at time
+    differences tau (A, B) -> (D, A, B)"""
+    tau = tau.abs().unsqueeze(0)
+    k = torch.zeros((real.shape[0],) + tuple(tau.shape[1:]), dtype=torch.float64, device=tau.device)
+    col = lambda x: x.reshape(-1, 1, 1)
+    for j in range(real.shape[1]):
+        k = k + col(real[:, j, 0]) * torch.exp(-col(real[:, j, 1]) * tau)
+    for s in range(cplx.shape[1]):
+        a, b, c, d = (col(cplx[:, s, i]) for i in range(4))
+        term = torch.exp(-c * tau) * (a * torch.cos(d * tau) + b * torch.sin(d * tau))
+        if kind is not None:      # (a1, c1, a2, c2): two real terms
+            term = torch.where(col(kind[:, s]) != 0, a * torch.exp(-b * tau) + c * torch.exp(-d * tau), term)
+        k = k + term
+    return k
+
+
 class GaussianProcess:
     """``GaussianProcess(kernel, t=t, diag=..., yerr=..., mean=...)`` then
     ``log_likelihood(y)``; modelled on celerite2.GaussianProcess.
@@ -434,12 +470,7 @@ class GaussianProcess:
         """alpha = (K + diag)^-1 (y - mean), per draw (detached).  It is minus the gradient of the
         log-likelihood with respect to y, i.e. one forward + one reverse pass of the recurrences."""
         t, _, resid, real, cplx, squeeze, _, kind = self._prepare(y)
-        with torch.enable_grad():
-            r = resid.detach().requires_grad_(True)
-            ll = celerite_loglike(t.detach(), r, self._diag.detach().contiguous(), real.detach(), cplx.detach(),
-                                  pair_kind=kind)
-            (g,) = torch.autograd.grad(ll.sum(), r)
-        alpha = -g
+        alpha = _inverse(t, resid, self._diag, real, cplx, kind)
         return alpha[0] if squeeze else alpha
 
     def dot_tril(self, x):
@@ -486,32 +517,81 @@ class GaussianProcess:
             out.append(z)
         return out[0] if size is None else torch.stack(out)
 
-    def predict(self, y, t=None, *, include_mean=True):
-        """Conditional mean of the process given ``y`` (celerite2's ``GaussianProcess.predict``
-        without the variance), detached.  At the data times (``t=None``) it is
-        ``y - diag * alpha``; at other times ``K(t, t_data) alpha`` by the O(N + M) forward / backward
-        recurrences of exo_celerite_predict_f64 (``t`` sorted)."""
+    def _component(self, kernel, n_real, n_complex):
+        """the slot mask of a component -- ``kernel`` one of the kernel's terms or a TermSum of some of them, compared by
+        identity after TermSum's flattening -- as (real slots, pair slots) lists of bools, in the order pair_coefficients lays
+        the slots out: every term's own slots, term after term (the fused layout of a sum of SHO terms is the same: one pair
+        slot per term, in order)"""
+        terms = self.kernel.terms if isinstance(self.kernel, TermSum) else (self.kernel,)
+        parts = kernel.terms if isinstance(kernel, TermSum) else (kernel,)
+        if not isinstance(kernel, Term) or not parts or not all(any(p is q for q in terms) for p in parts):
+            raise ValueError("kernel must be the GaussianProcess's kernel, one of its terms or a TermSum of some of them")
+        keep_real, keep_pair = [], []
+        with torch.no_grad():
+            for q in terms:
+                ar, _, pairs, _ = q.pair_coefficients()
+                sel = any(p is q for p in parts)
+                keep_real += [sel] * ar.shape[-1]
+                keep_pair += [sel] * pairs.shape[-2]
+        if len(keep_real) != n_real or len(keep_pair) != n_complex:
+            raise ValueError("kernel: the terms' slots do not match the kernel's coefficients")
+        return keep_real, keep_pair
+
+    def predict(self, y, t=None, *, return_cov=False, return_var=False, include_mean=True, kernel=None):
+        """Conditional distribution of the process given ``y`` (celerite2's ``GaussianProcess.predict``), detached.
+
+        The mean ``mu``: at the data times (``t=None``) ``y - diag * alpha``; at other times ``K(t, t_data) alpha`` by the
+        O(N + M) forward / backward recurrences of exo_celerite_predict_f64 (``t`` sorted), alpha = (K + diag)^-1 (y - mean);
+        (D, M), or (M,) when neither ``y``, the kernel nor the diagonal has a draw dimension; M = N for ``t=None``.
+
+        ``return_var=True``: ``(mu, var)``, ``var`` shaped like ``mu``: the variance of the latent process (no white noise) at
+        the query times, in the units of ``y`` squared -- ``k(0) - K(t*, t) (K + diag)^-1 K(t, t*)`` by a Kalman filter and
+        its smoother, O((N + M) J^2) per draw (exo_celerite_predict_var_f64; the draws go in slices whose workspace stays within
+        PREDICT_VAR_WORK_BYTES).  ``return_cov=True``: ``(mu, cov)``, ``cov`` (D, M, M) or (M, M): dense, the same expression
+        with the solve by the likelihood's recurrences for blocks of query times (the transient arrays within
+        PREDICT_COV_WORK_BYTES) and an fp64 matmul per block -- meant for a modest number of query times.  Not both.
+
+        ``kernel``: one component of the process -- the GaussianProcess's kernel, one of its terms, or a TermSum of some of
+        them, compared by identity after TermSum's flattening (a RotationTerm inside the kernel is its two SHO terms, so the
+        RotationTerm selects both); anything else raises ValueError.  ``mu`` is then ``K2(t*, t) alpha`` (at the data times as
+        well) and ``var`` / ``cov`` are those of the component, K2 the kernel restricted to the selected terms; K + diag keeps
+        every term.  The mean model is added to ``mu`` with ``include_mean`` either way."""
+        if return_cov and return_var:
+            raise ValueError("only one of return_cov and return_var can be True")
+        if kernel is self.kernel:
+            kernel = None
         tt, mean, resid, real, cplx, squeeze, _, kind = self._prepare(y)
+        keep = None if kernel is None else self._component(kernel, real.shape[1], cplx.shape[1])
         alpha = self.apply_inverse(y)
         alpha2 = alpha if alpha.dim() == 2 else alpha.unsqueeze(0)
-        if t is None:
+        if keep is None:
+            comp = (real.detach(), cplx.detach(), kind)
+        else:
+            ir = torch.tensor([j for j, k in enumerate(keep[0]) if k], dtype=torch.long, device=tt.device)
+            ic = torch.tensor([j for j, k in enumerate(keep[1]) if k], dtype=torch.long, device=tt.device)
+            comp = (real.detach()[:, ir].contiguous(), cplx.detach()[:, ic].contiguous(),
+                    None if kind is None else kind[:, ic].contiguous())
+        if t is None and keep is None:
             mu = resid.detach() - self._diag.detach() * alpha2
             tq = tt
         else:
-            tq = as_tensor(t, tt)
-            if tq.dim() != 1:
-                raise ValueError("dimension mismatch: t must be 1-D")
-            if tq.numel() > 1 and bool((tq[1:] < tq[:-1]).any()):
-                raise ValueError("the input coordinates must be sorted")
+            if t is None:
+                tq = tt
+            else:
+                tq = as_tensor(t, tt)
+                if tq.dim() != 1:
+                    raise ValueError("dimension mismatch: t must be 1-D")
+                if tq.numel() > 1 and bool((tq[1:] < tq[:-1]).any()):
+                    raise ValueError("the input coordinates must be sorted")
             tq = _dev(tq.detach(), "t")
             D = alpha2.shape[0]
             al = _dev(alpha2.detach(), "alpha")
-            re, cx = _dev(real.detach(), "coef_real"), _dev(cplx.detach(), "coef_complex")
+            re, cx = _dev(comp[0], "coef_real"), _dev(comp[1], "coef_complex")
             mu = torch.empty(D, tq.shape[0], dtype=torch.float64, device=tt.device)
             lib = _lib.load()
             with torch.cuda.device(tt.device):
                 _lib.check(lib.exo_celerite_predict_f64(_ptr(tt), tt.shape[0], _ptr(al), _ptr(re), re.shape[1], _ptr(cx),
-                                                        cx.shape[1], _ptr(kind), D, _ptr(tq), tq.shape[0], _ptr(mu),
+                                                        cx.shape[1], _ptr(comp[2]), D, _ptr(tq), tq.shape[0], _ptr(mu),
                                                         _stream(tt)), "exo_celerite_predict_f64")
         if include_mean:
             m = self._mean_at(tq, tt)
@@ -520,4 +600,66 @@ class GaussianProcess:
             if isinstance(m, torch.Tensor) and m.dim() >= 1 and m.shape[-1] == tt.shape[0] and t is not None:
                 raise ValueError("a tabulated mean cannot be evaluated at new times: pass a callable mean")
             mu = mu + (m.detach() if isinstance(m, torch.Tensor) else m)
-        return mu[0] if squeeze else mu
+        mu = mu[0] if squeeze else mu
+        if not (return_var or return_cov):
+            return mu
+        real, cplx = _dev(real.detach(), "coef_real"), _dev(cplx.detach(), "coef_complex")
+        if return_var:
+            mask = None if keep is None else torch.tensor(keep[0] + keep[1], dtype=torch.int32, device=tt.device)
+            out = self._predict_var(tt, tq, real, cplx, kind, mask, alpha2.shape[0])
+        else:
+            out = self._predict_cov(tt, tq, real, cplx, kind, comp, alpha2.shape[0])
+        return mu, (out[0] if squeeze else out)
+
+    def _predict_var(self, tt, tq, real, cplx, kind, mask, D):
+        """(D, M): exo_celerite_predict_var_f64, the draws in slices of at most PREDICT_VAR_WORK_BYTES of workspace"""
+        lib = _lib.load()
+        N, M, nr, nc = tt.shape[0], tq.shape[0], real.shape[1], cplx.shape[1]
+        var = _buffer(D, M, device=tt.device)
+        step = max(1, min(D, PREDICT_VAR_WORK_BYTES // (8 * lib.exo_celerite_predict_var_work_doubles(N, M, nr, nc, 1))))
+        if step >= 64:
+            step -= step % 64
+        nwork = lib.exo_celerite_predict_var_work_doubles(N, M, nr, nc, step)
+        work = _buffer(nwork, device=tt.device)
+        diag = _dev(self._diag.detach(), "diag")
+        with torch.cuda.device(tt.device):
+            for d0 in range(0, D, step):
+                d1 = min(D, d0 + step)
+                dg = diag if diag.shape[0] == 1 else diag[d0:d1]
+                kd = None if kind is None else kind[d0:d1]
+                _lib.check(lib.exo_celerite_predict_var_f64(_ptr(tt), _ptr(dg), dg.shape[0], N, _ptr(real[d0:d1]), nr,
+                                                            _ptr(cplx[d0:d1]), nc, _ptr(kd), _ptr(mask), d1 - d0, _ptr(tq), M,
+                                                            _ptr(var[d0:d1]), _ptr(work), nwork, _stream(tt)),
+                           "exo_celerite_predict_var_f64")
+        return var
+
+    def _predict_cov(self, tt, tq, real, cplx, kind, comp, D):
+        """(D, M, M): K2(t*, t*) - K2(t*, t) (K + diag)^-1 K2(t, t*), dense; (K + diag)^-1 by the likelihood's recurrences
+        applied to blocks of columns of K2(t, t*), the D x block columns of a block as the draws of one call"""
+        N, M = tt.shape[0], tq.shape[0]
+        cov = _k2_dense(*comp, tq[:, None] - tq[None, :])
+        if M == 0:
+            return cov
+        diag = self._diag.detach()
+        lib = _lib.load()
+        # bytes per query time of a block: its column of K2(t, t*), the right-hand side and the solution (D x N each), and the
+        # likelihood's state for D right-hand sides
+        per = 8 * (3 * D * N + lib.exo_celerite_state_doubles(N, D, real.shape[1], cplx.shape[1], 0))
+        blk = int(max(1, min(M, PREDICT_COV_WORK_BYTES // per)))
+        whole = 8 * D * N * M <= PREDICT_COV_WORK_BYTES      # K2(t, t*) for every query time at once
+        k_all = _k2_dense(*comp, tt[:, None] - tq[None, :]) if whole else None
+        for c0 in range(0, M, blk):
+            c1 = min(M, c0 + blk)
+            B = c1 - c0
+            kc = k_all[:, :, c0:c1] if whole else _k2_dense(*comp, tt[:, None] - tq[None, c0:c1])
+            rep = lambda x: x.repeat_interleave(B, 0).contiguous()
+            x = _inverse(tt, kc.transpose(1, 2).reshape(D * B, N), diag if diag.shape[0] == 1 else rep(diag), rep(real),
+                         rep(cplx), None if kind is None else rep(kind)).reshape(D, B, N)
+            if whole:
+                cov[:, :, c0:c1] -= torch.matmul(k_all.transpose(1, 2), x.transpose(1, 2))
+                continue
+            for r0 in range(0, M, blk):
+                r1 = min(M, r0 + blk)
+                kr = kc if r0 == c0 else _k2_dense(*comp, tt[:, None] - tq[None, r0:r1])
+                cov[:, r0:r1, c0:c1] -= torch.matmul(kr.transpose(1, 2), x.transpose(1, 2))
+        return cov

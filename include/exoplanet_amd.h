@@ -45,8 +45,9 @@ extern "C" {
  *     loglike, gloglike, the cotangents written back: all in the caller's order, nothing to permute); exo_sparse_model_order.
  * 13: the MERGED sparse model -- exo_sparse_merge_workspace_bytes, exo_sparse_merge_layout, exo_sparse_model_merge_f64,
  *     exo_sparse_model_merged, exo_sparse_model_merge_vjp_f64: several lists per draw (planets, occultations) as one.
- * 14: EXO_GP_PREPARE_ADJOINT, a flag or-ed into n_chunks of a celerite pair (the adjoint scan beside the forward chunk kernel). */
-#define EXO_ABI_VERSION 14
+ * 14: EXO_GP_PREPARE_ADJOINT, a flag or-ed into n_chunks of a celerite pair (the adjoint scan beside the forward chunk kernel).
+ * 15: the predictive variance -- exo_celerite_predict_var_work_doubles, exo_celerite_predict_var_f64. */
+#define EXO_ABI_VERSION 15
 int32_t exo_abi_version(void);
 
 /* ---------------------------------------------------------------------------
@@ -630,6 +631,37 @@ int exo_celerite_predict_f64(const double* t, int64_t n, const double* alpha, co
                              int32_t n_real, const double* coef_complex, int32_t n_complex,
                              const int32_t* pair_kind, int64_t n_draw, const double* tq, int64_t m,
                              double* mu, void* stream);
+
+/* ---------------------------------------------------------------------------
+ * Predictive variance (ABI 15; celerite2's GaussianProcess.predict(return_var=True), optionally of a
+ * component of the kernel):
+ *   var[d][q] = k2(0) - k2(tq[q], t) (K + diag)^-1 k2(t, tq[q])
+ * k2: the kernel restricted to the terms whose slot_mask entry is nonzero -- slot_mask (int32) holds one
+ * entry per real slot, then one per pair slot (a pair slot of kind 1 holds two real terms, selected
+ * together); NULL: every term, k2 = k.  K + diag always uses every term.  The latent process: no
+ * white noise at the query times.  t [n] and tq [m] sorted; var [n_draw][m].  Coefficients, pair
+ * kinds and diag as for exo_celerite_loglike_fwd_f64 (n >= 1).
+ * One lane per draw, O((n + m) J^2), sequential in time.  With A = K + diag = L diag(d) L^T, S_i the
+ * state entering cadence i and E(tau) = diag(exp(-c tau)):
+ *   forward:   d_i = diag_i + sum a - U_i^T S_i U_i,  W_i = (V_i - S_i U_i) / d_i,
+ *              S+_i = S_i + d_i W_i W_i^T,  S_(i+1) = E(t_(i+1) - t_i) S+_i E(t_(i+1) - t_i)
+ *   backward:  B_n = 0,  X = E(t_(i+1) - t_i) B_(i+1) E(t_(i+1) - t_i)  (0 at the last cadence),
+ *              B_i = U_i U_i^T / d_i + (I - W_i U_i^T)^T X (I - W_i U_i^T)
+ *   query t* after the last cadence k with t_k <= t* (k = -1: none), U*, V* of the predicted terms only:
+ *              S* = E(t* - t_k) S+_k E(t* - t_k) (0 for k = -1),  r* = V* - S* U*,
+ *              B* = E(t_(k+1) - t*) B_(k+1) E(t_(k+1) - t*) (0 for k = n - 1),
+ *              var = k2(0) - U*^T S* U* - r*^T B* r*
+ * work: device scratch of exo_celerite_predict_var_work_doubles(n, m, n_real, n_complex, n_draw) =
+ * (n + m) (J + 1) n_draw doubles (J = n_real + 2 n_complex), laid out [row][quantity][draw]; its content
+ * before the call does not matter (EXO_ERR_WORKSPACE: too small).  A draw whose factorisation meets
+ * d <= 0 (the matrix is not positive definite) gets NaN at every query time, as dot_tril does.
+ * ------------------------------------------------------------------------- */
+int64_t exo_celerite_predict_var_work_doubles(int64_t n, int64_t m, int32_t n_real, int32_t n_complex, int64_t n_draw);
+int exo_celerite_predict_var_f64(const double* t, const double* diag, int64_t n_diag, int64_t n,
+                                 const double* coef_real, int32_t n_real, const double* coef_complex,
+                                 int32_t n_complex, const int32_t* pair_kind, const int32_t* slot_mask,
+                                 int64_t n_draw, const double* tq, int64_t m, double* var, double* work,
+                                 int64_t work_doubles, void* stream);
 
 /* ---------------------------------------------------------------------------
  * Record packing: the O(planets) algebra of KeplerianOrbit.__init__
