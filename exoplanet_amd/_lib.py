@@ -10,7 +10,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # EXOPLANET_AMD_LIB selects another in-tree build of the same ABI (A/B measurements)
 LIB_PATH = os.environ.get("EXOPLANET_AMD_LIB") or os.path.join(_HERE, "lib", "libexoplanet_amd.so")
-ABI_VERSION = 15
+ABI_VERSION = 16
 
 _c_dp = ctypes.c_void_p  # device pointers travel as integers
 _i64 = ctypes.c_int64
@@ -130,6 +130,13 @@ _SIGNATURES = {
     # work_doubles, stream
     "exo_celerite_predict_var_f64": (ctypes.c_int, [_c_dp, _c_dp, _i64, _i64, _c_dp, _i32, _c_dp, _i32, _c_dp, _c_dp, _i64,
                                                     _c_dp, _i64, _c_dp, _c_dp, _i64, _c_dp]),
+    "exo_bls_workspace_bytes": (_i64, [_i64, _i64, _i64, _i64]),
+    # t, y, yerr, n_yerr, n, n_series, periods, n_period, min_bins, max_bins, duration_bins (host), n_duration, delta,
+    # oversample, objective, out, workspace, workspace_bytes, stream
+    "exo_bls_power_f64": (ctypes.c_int, [_c_dp, _c_dp, _c_dp, _i64, _i64, _i64, _c_dp, _i64, _i64, _i64, _c_dp, _i32,
+                                         ctypes.c_double, _i32, _i32, _c_dp, _c_dp, _i64, _c_dp]),
+    # t, y, yerr, n_yerr, n, n_series, frequencies, n_frequency, power, workspace, workspace_bytes, stream
+    "exo_lomb_scargle_power_f64": (ctypes.c_int, [_c_dp, _c_dp, _c_dp, _i64, _i64, _i64, _c_dp, _i64, _c_dp, _c_dp, _i64, _c_dp]),
     "exo_radial_velocity_fwd_f64": (ctypes.c_int, [_c_dp, _i64, _c_dp, _i64, _i32, _c_dp, _c_dp]),
     "exo_radial_velocity_vjp_f64": (ctypes.c_int, [_c_dp, _i64, _c_dp, _i64, _i32, _c_dp, _c_dp, _c_dp]),
     "exo_orbit_vector_fwd_f64": (ctypes.c_int, [_c_dp, _i64, _c_dp, _i64, _i32, _u32, _c_dp, _c_dp]),

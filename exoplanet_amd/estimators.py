@@ -1,0 +1,412 @@
+"""Period search and the other pre-fit estimators of the reference's ``exoplanet.estimators``: where ``period0`` and ``t00``
+come from.  The two periodograms are HIP kernels (csrc/exo_estimators.hip) and are computed exactly on an unthinned grid, for
+many series on one time axis at once; the glue around them keeps the reference's names, arguments, defaults and dictionary
+keys.  Definitions: DESIGN.md section 9.
+
+Low level (device tensors in and out, float64): :func:`bls_power`, :func:`lomb_scargle_power`, and the grids
+:func:`bls_autoperiod`, :func:`lomb_scargle_autofrequency` (host arithmetic).
+
+High level (numpy arrays or tensors in, numpy out, ``peaks`` hold Python floats): :func:`bls_estimator`,
+:func:`lomb_scargle_estimator`, :func:`autocorr_estimator`, :func:`find_peaks`, :func:`estimate_semi_amplitude`,
+:func:`estimate_minimum_mass`.  Plain numbers throughout: days, m/s and solar masses in, m/s and Jupiter masses out.
+
+Synchronisation: ``periods``, ``durations`` and ``frequencies`` given as numpy arrays (or lists) never leave the host -- the grid
+sizes and the choice of kernel need them there -- and their device copies are cached, so that a call repeated with the same grid
+enqueues kernels only and can be captured into a graph after one eager call.  Given as device tensors they are copied to the
+host once per call, which waits for the stream; that is the only synchronisation in this module's low-level functions.
+
+Run-to-run differences: the box search sums each phase bin with fp64 atomic adds, whose order is not fixed; ``power`` and the
+other outputs may differ in their last bits between two runs on the same input (and a near-tie between two boxes may then
+resolve differently).  The Lomb-Scargle sums have a fixed order and are bitwise reproducible.
+"""
+import collections
+import ctypes
+
+import numpy as np
+import torch
+
+from . import _lib
+
+__all__ = [
+    "bls_power", "lomb_scargle_power", "bls_autoperiod", "lomb_scargle_autofrequency", "find_peaks", "bls_estimator",
+    "lomb_scargle_estimator", "autocorr_function", "autocorr_estimator", "estimate_semi_amplitude", "estimate_minimum_mass",
+]
+
+MAX_DURATIONS = 16      # EXO_BLS_MAX_DURATIONS
+_OBJECTIVES = {None: 0, "likelihood": 0, "snr": 1}
+BLS_FIELDS = ("power", "depth", "depth_err", "depth_snr", "log_likelihood", "duration", "transit_time")
+
+
+class BLSResult(dict):
+    """the outputs of :func:`bls_power`, by key and by attribute: ``period`` and the seven of ``BLS_FIELDS``"""
+
+    __getattr__ = dict.__getitem__
+
+
+# ---- arguments ---------------------------------------------------------------------------------------------------------------
+
+def _device_series(t, y, yerr):
+    """-> t (N,), y (B, N), yerr None / (1, N) / (B, N), all contiguous float64 on t's device, and whether y was batched"""
+    for name, x in (("t", t), ("y", y)):
+        if not isinstance(x, torch.Tensor):
+            raise ValueError(f"{name} must be a torch.Tensor on a ROCm device")
+        if not x.is_cuda:
+            raise ValueError(f"{name} lives on {x.device}: the estimators run HIP kernels on a ROCm device; there is no CPU fallback")
+    if t.ndim != 1 or t.numel() < 1:
+        raise ValueError(f"t must have shape (N,), got {tuple(t.shape)}")
+    n = t.numel()
+    if y.ndim not in (1, 2) or y.shape[-1] != n:
+        raise ValueError(f"y must have shape (N,) or (B, N) with N = {n}, got {tuple(y.shape)}")
+    batched = y.ndim == 2
+    t = t.to(torch.float64).contiguous()
+    y = y.to(device=t.device, dtype=torch.float64).reshape(-1, n).contiguous()
+    if y.shape[0] < 1:
+        raise ValueError("y holds no series")
+    if yerr is not None:
+        if isinstance(yerr, torch.Tensor) and not yerr.is_cuda and yerr.ndim > 0:
+            raise ValueError(f"yerr lives on {yerr.device}: there is no CPU fallback")
+        if not isinstance(yerr, torch.Tensor) or yerr.ndim == 0:
+            yerr = torch.full((1, n), float(yerr), dtype=torch.float64, device=t.device)
+        if yerr.shape not in ((n,), (1, n), tuple(y.shape)):
+            raise ValueError(f"yerr must be a scalar or have shape (N,) or that of y, got {tuple(yerr.shape)}")
+        yerr = yerr.to(device=t.device, dtype=torch.float64).reshape(-1, n).contiguous()
+    return t, y, yerr, batched
+
+
+_grid_cache = collections.OrderedDict()
+
+
+def _grid(x, name, device):
+    """-> (host float64 array, device tensor) of a 1-D grid.  Host input: the device copy is cached by content."""
+    if isinstance(x, torch.Tensor):
+        if x.ndim != 1:
+            raise ValueError(f"{name} must be one-dimensional")
+        dev = x.to(device=device, dtype=torch.float64).contiguous()
+        return dev.cpu().numpy(), dev
+    host = np.ascontiguousarray(np.atleast_1d(np.asarray(x, dtype=np.float64)))
+    if host.ndim != 1:
+        raise ValueError(f"{name} must be one-dimensional")
+    key = (str(device), host.shape, hash(host.tobytes()))
+    hit = _grid_cache.get(key)
+    if hit is not None and np.array_equal(hit[0], host):
+        _grid_cache.move_to_end(key)
+        return hit
+    dev = torch.as_tensor(host, device=device)
+    _grid_cache[key] = (host.copy(), dev)
+    while len(_grid_cache) > 16:
+        _grid_cache.popitem(last=False)
+    return host, dev
+
+
+def _stream(t):
+    return torch.cuda.current_stream(t.device).cuda_stream
+
+
+def _workspace(nbytes, device):
+    return torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=device)
+
+
+# ---- the periodograms ----------------------------------------------------------------------------------------------------------
+
+def bls_plan(periods, durations, oversample):
+    """host arithmetic of a box search: delta, the boxes' widths in bins, and every period's bin count"""
+    periods, durations = np.asarray(periods, dtype=np.float64), np.asarray(durations, dtype=np.float64)
+    if int(oversample) != oversample or oversample < 1:
+        raise ValueError(f"oversample must be an integer >= 1, got {oversample}")
+    if periods.size and not np.all(periods > 0):
+        raise ValueError("periods must be positive")
+    if durations.size < 1 or not np.all(durations > 0):
+        raise ValueError("durations must be positive (and at least one is needed)")
+    if durations.size > MAX_DURATIONS:
+        raise ValueError(f"at most {MAX_DURATIONS} durations per call")
+    if periods.size and durations.max() >= periods.min():
+        raise ValueError("the longest duration must be shorter than the shortest period")
+    delta = float(durations.min()) / int(oversample)
+    m = np.round(durations / delta).astype(np.int32)
+    n_bins = np.ceil(periods / delta).astype(np.int64) + int(oversample)
+    return delta, m, n_bins
+
+
+def bls_power(t, y, yerr=None, *, periods, durations, oversample=10, objective="likelihood"):
+    """Box-least-squares periodogram (the binned method) of ``y`` (N,) or (B, N) at times ``t`` (N,), any order.
+
+    ``yerr``: None (unit weights), a scalar, (N,) or (B, N).  ``periods`` (P,), ``durations`` (K,): numpy arrays or device
+    tensors (see the module docstring).  Returns a :class:`BLSResult` of (P,) or (B, P) device tensors: ``power`` -- the
+    maximum over durations and phases of the objective, the box's log likelihood (``"likelihood"``) or the depth's signal to
+    noise (``"snr"``) -- and ``depth, depth_err, depth_snr, log_likelihood, duration, transit_time`` of that box, plus ``period``.
+    A period with no admissible box (no weight inside or none outside every box) has ``power = -inf`` and NaN elsewhere."""
+    if objective not in _OBJECTIVES:
+        raise ValueError(f"unknown objective {objective!r}: 'likelihood' or 'snr'")
+    t, y, yerr, batched = _device_series(t, y, yerr)
+    p_host, p_dev = _grid(periods, "periods", t.device)
+    d_host = np.atleast_1d(_np(durations))
+    if d_host.ndim != 1:
+        raise ValueError("durations must be one-dimensional")
+    delta, m, n_bins = bls_plan(p_host, d_host, oversample)
+    B, N, P = y.shape[0], y.shape[1], p_host.size
+    out = torch.empty((7, B, P), dtype=torch.float64, device=t.device)
+    if P:
+        lib = _lib.load()
+        lo, hi = int(n_bins.min()), int(n_bins.max())
+        nbytes = lib.exo_bls_workspace_bytes(N, B, P, hi)
+        if nbytes < 0:
+            raise ValueError("bls_power: invalid sizes")
+        ws = _workspace(nbytes, t.device)
+        _lib.check(lib.exo_bls_power_f64(t.data_ptr(), y.data_ptr(), 0 if yerr is None else yerr.data_ptr(),
+                                         0 if yerr is None else yerr.shape[0], N, B, p_dev.data_ptr(), P, lo, hi,
+                                         m.ctypes.data_as(ctypes.c_void_p), m.size, delta, int(oversample), _OBJECTIVES[objective],
+                                         out.data_ptr(), ws.data_ptr(), ws.numel() * 8, _stream(t)), "exo_bls_power_f64")
+    res = BLSResult(period=p_dev)
+    for i, k in enumerate(BLS_FIELDS):
+        res[k] = out[i] if batched else out[i, 0]
+    return res
+
+
+def lomb_scargle_power(t, y, yerr=None, *, frequencies):
+    """Floating-mean Lomb-Scargle periodogram, exact sums, "psd" normalisation: ``(chi2_0 - chi2(f)) / 2`` with ``chi2(f)`` the
+    weighted least-squares misfit of ``a sin(2 pi f t) + b cos(2 pi f t) + c``.  ``y`` (N,) or (B, N) -> (F,) or (B, F)."""
+    t, y, yerr, batched = _device_series(t, y, yerr)
+    f_host, f_dev = _grid(frequencies, "frequencies", t.device)
+    B, N, F = y.shape[0], y.shape[1], f_host.size
+    out = torch.empty((B, F), dtype=torch.float64, device=t.device)
+    if F:
+        lib = _lib.load()
+        ws = _workspace(lib.exo_bls_workspace_bytes(N, B, 0, 0), t.device)
+        _lib.check(lib.exo_lomb_scargle_power_f64(t.data_ptr(), y.data_ptr(), 0 if yerr is None else yerr.data_ptr(),
+                                                  0 if yerr is None else yerr.shape[0], N, B, f_dev.data_ptr(), F, out.data_ptr(),
+                                                  ws.data_ptr(), ws.numel() * 8, _stream(t)), "exo_lomb_scargle_power_f64")
+    return out if batched else out[0]
+
+
+def _span(t):
+    t = t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t, dtype=np.float64)
+    return float(t.max() - t.min())
+
+
+def bls_autoperiod(t, durations, minimum_period=None, maximum_period=None, minimum_n_transit=3, frequency_factor=1.0):
+    """The box search's period grid, even in frequency with step ``frequency_factor * min(durations) / T^2``, from
+    ``maximum_period`` (default ``T / (minimum_n_transit - 1)``) down to ``minimum_period`` (default ``2 max(durations)``);
+    returned shortest period first.  A numpy array."""
+    durations = np.atleast_1d(np.asarray(durations, dtype=np.float64))
+    if not np.all(durations > 0):
+        raise ValueError("durations must be positive")
+    T = _span(t)
+    if not T > 0:
+        raise ValueError("the times span no baseline")
+    if minimum_n_transit < 2:
+        raise ValueError("minimum_n_transit must be at least 2")
+    df = frequency_factor * durations.min() / T ** 2
+    if maximum_period is None:
+        maximum_period = T / (minimum_n_transit - 1)
+    if minimum_period is None:
+        minimum_period = 2.0 * durations.max()
+    if not 0 < minimum_period <= maximum_period:
+        raise ValueError("need 0 < minimum_period <= maximum_period")
+    f_hi, f_lo = 1.0 / minimum_period, 1.0 / maximum_period
+    n = 1 + int(np.round((f_hi - f_lo) / df))
+    return 1.0 / (f_hi - df * np.arange(n))
+
+
+def lomb_scargle_autofrequency(t, samples_per_peak=5, nyquist_factor=5, minimum_frequency=None, maximum_frequency=None):
+    """The periodogram's frequency grid: step ``1 / (T samples_per_peak)`` from ``minimum_frequency`` (default half a step) to
+    ``maximum_frequency`` (default ``nyquist_factor`` times the mean Nyquist frequency ``N / 2T``).  A numpy array."""
+    T = _span(t)
+    if not T > 0:
+        raise ValueError("the times span no baseline")
+    n_t = t.numel() if isinstance(t, torch.Tensor) else np.asarray(t).size
+    df = 1.0 / (T * samples_per_peak)
+    if minimum_frequency is None:
+        minimum_frequency = 0.5 * df
+    if maximum_frequency is None:
+        maximum_frequency = nyquist_factor * 0.5 * n_t / T
+    n = 1 + int(np.round((maximum_frequency - minimum_frequency) / df))
+    return minimum_frequency + df * np.arange(n)
+
+
+# ---- the reference's estimators -------------------------------------------------------------------------------------------------
+
+def _np(x):
+    return x.detach().cpu().numpy().astype(np.float64) if isinstance(x, torch.Tensor) else np.asarray(x, dtype=np.float64)
+
+
+def _device_of(*xs):
+    for x in xs:
+        if isinstance(x, torch.Tensor) and x.is_cuda:
+            return x.device
+    if not torch.cuda.is_available():
+        raise ValueError("the estimators run on a ROCm device and none is available; there is no CPU fallback")
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+def _to(x, device):
+    return None if x is None else torch.as_tensor(x, dtype=torch.float64, device=device)
+
+
+def find_peaks(freq, power, max_peaks=0):
+    """Local maxima of a periodogram, highest first, each refined by the parabola through the three ``log(power)`` samples
+    around it.  ``max_peaks = 0``: the highest peak as a dictionary ``index, log_power, period, period_uncert`` (ValueError if
+    there is none); ``max_peaks > 0``: a list of at most that many."""
+    freq, power = _np(freq), _np(power)
+    inner = power[1:-1]
+    inds = np.arange(1, len(power) - 1)[(inner > power[:-2]) & (inner > power[2:])]
+    inds = inds[np.argsort(power[inds])][::-1]
+    peaks = []
+    for i in inds[: max(1, max_peaks)]:
+        w = np.linalg.solve(np.vander(freq[i - 1:i + 2], 3), np.log(power[i - 1:i + 2]))
+        sigma2 = -0.5 / w[0]
+        freq0 = w[1] * sigma2
+        peaks.append(dict(index=int(i + 1), log_power=float(w[2] + 0.5 * freq0 ** 2 / sigma2), period=float(1.0 / freq0),
+                          period_uncert=float(np.sqrt(sigma2 / freq0 ** 4))))
+    if max_peaks:
+        return peaks
+    if not peaks:
+        raise ValueError("no peaks were found")
+    return peaks[0]
+
+
+def bls_estimator(x, y, yerr=None, duration=0.2, min_period=None, max_period=None, objective=None, method=None, oversample=10,
+                  frequency_factor=None, minimum_n_transit=3):
+    """Estimate the period of a transit signal by box least squares.  Returns ``bls`` (the periodogram: numpy arrays under the
+    keys of :class:`BLSResult`), ``peaks`` (at most one, from ``find_peaks(1 / period, power)``) and ``peak_info``.
+
+    ``frequency_factor=None`` thins the grid as the reference does (doubled until there are no more periods than cadences), so
+    that results compare; ``frequency_factor=1.0`` searches the full grid.  ``method`` is accepted and ignored."""
+    dev = _device_of(x, y)
+    xh = _np(x)
+    x_ref = 0.5 * (xh.min() + xh.max())
+    durations = np.atleast_1d(np.asarray(duration, dtype=np.float64))
+    grid = lambda ff: bls_autoperiod(xh - x_ref, durations, minimum_period=min_period, maximum_period=max_period,
+                                     minimum_n_transit=minimum_n_transit, frequency_factor=ff)
+    if frequency_factor is None:
+        frequency_factor = 1.0
+        periods = grid(frequency_factor)
+        while len(periods) > len(xh):
+            frequency_factor *= 2
+            periods = grid(frequency_factor)
+    else:
+        periods = grid(frequency_factor)
+    yd = _to(y, dev)
+    res = bls_power(_to(xh - x_ref, dev), yd - torch.median(yd), _to(yerr, dev), periods=periods, durations=durations,
+                    oversample=oversample, objective="likelihood" if objective is None else objective)
+    pg = BLSResult((k, _np(v)) for k, v in res.items())
+    pg["transit_time"] = pg["transit_time"] + x_ref
+    pg["objective"] = "likelihood" if objective is None else objective
+    peaks = find_peaks(1.0 / pg["period"], pg["power"], max_peaks=1)
+    results = dict(bls=pg, peaks=peaks, peak_info=None)
+    if peaks:
+        ind = peaks[0]["index"]
+        results["peak_info"] = dict((k, float(v[ind])) for k, v in pg.items() if k != "objective")
+    return results
+
+
+def lomb_scargle_estimator(x, y, yerr=None, min_period=None, max_period=None, filter_period=None, max_peaks=2, **kwargs):
+    """Estimate the period of a series from its Lomb-Scargle periodogram on the automatic grid (``kwargs``: those of
+    :func:`lomb_scargle_autofrequency`).  Returns ``periodogram = (freq, power / len(x))`` and ``peaks``, found after the
+    optional high-pass weight ``1 / sqrt(1 + (f0 / f)^6)``, ``f0 = 1 / filter_period``."""
+    if min_period is not None:
+        kwargs["maximum_frequency"] = 1.0 / min_period
+    if max_period is not None:
+        kwargs["minimum_frequency"] = 1.0 / max_period
+    dev = _device_of(x, y)
+    xh = _np(x)
+    freq = lomb_scargle_autofrequency(xh, **kwargs)
+    power = _np(lomb_scargle_power(_to(xh, dev), _to(y, dev), _to(yerr, dev), frequencies=freq)) / len(xh)
+    power_est = np.array(power)
+    if filter_period is not None:
+        power = power / np.sqrt(1 + ((1.0 / filter_period) / freq) ** 6)
+    return dict(periodogram=(freq, power_est), peaks=find_peaks(freq, power, max_peaks=max_peaks))
+
+
+def autocorr_function(x):
+    """The normalised autocorrelation function of a 1-D series (by FFT, zero padded to twice the next power of two)"""
+    as_numpy = not isinstance(x, torch.Tensor)
+    x = torch.atleast_1d(torch.as_tensor(x, dtype=torch.float64))
+    if x.ndim != 1:
+        raise ValueError("invalid dimensions for 1D autocorrelation function")
+    n = 1
+    while n < x.numel():
+        n <<= 1
+    f = torch.fft.fft(x - x.mean(), n=2 * n)
+    acf = torch.fft.ifft(f * torch.conj(f))[: x.numel()].real
+    acf = acf / acf[0]
+    return acf.cpu().numpy() if as_numpy else acf
+
+
+def _interp(xx, x, y):
+    """numpy.interp for increasing x, in torch"""
+    i = torch.searchsorted(x, xx, right=True).clamp(1, x.numel() - 1)
+    x0, x1 = x[i - 1], x[i]
+    return y[i - 1] + (y[i] - y[i - 1]) * ((xx - x0) / (x1 - x0)).clamp(0.0, 1.0)
+
+
+def _gaussian_filter(a, sigma, truncate=4.0):
+    """a Gaussian of standard deviation ``sigma`` samples, cut at ``truncate`` sigma, edges reflected (d c b a | a b c d | d c b a)"""
+    if not sigma > 0:
+        return a
+    r = int(truncate * sigma + 0.5)
+    k = torch.exp(-0.5 * (torch.arange(-r, r + 1, dtype=a.dtype, device=a.device) / sigma) ** 2)
+    k = k / k.sum()
+    idx = torch.arange(-r, a.numel() + r, device=a.device)
+    period = 2 * a.numel()
+    idx = idx % period
+    idx = torch.where(idx >= a.numel(), period - 1 - idx, idx)
+    return torch.nn.functional.conv1d(a[idx][None, None], k[None, None])[0, 0]
+
+
+def autocorr_estimator(x, y, yerr=None, min_period=None, max_period=None, oversample=2.0, smooth=2.0, max_peaks=10):
+    """Estimate the period of a series from the first (or, if higher, second) peak of its autocorrelation function.  The
+    series is interpolated to an even grid ``oversample`` times finer than its closest cadences, and the function smoothed by
+    a Gaussian of ``smooth * min_period``.  Returns ``autocorr = (tau, acor)`` and ``peaks`` (one entry or none)."""
+    dev = _device_of(x, y)
+    x, y = _to(x, dev), _to(y, dev)
+    gap = float(torch.diff(x).min())
+    if min_period is None:
+        min_period = gap
+    if max_period is None:
+        max_period = float(x.max() - x.min())
+    dx = gap / float(oversample)
+    xx = torch.arange(float(x.min()), float(x.max()), dx, dtype=torch.float64, device=dev)
+    tau = _np(xx - x[0])
+    acor = _np(_gaussian_filter(autocorr_function(_interp(xx, x, y)), smooth * min_period / dx))
+    inds = np.arange(1, len(acor) - 1)[(acor[1:-1] > acor[:-2]) & (acor[1:-1] > acor[2:])]
+    inds = inds[tau[inds] >= min_period]
+    result = dict(autocorr=(tau, acor), peaks=[])
+    if len(inds) == 0 or tau[inds[0]] > max_period:
+        return result
+    if len(inds) > 1 and acor[inds[1]] > acor[inds[0]]:
+        inds = inds[1:]
+    if tau[inds[0]] > max_period:
+        return result
+    result["peaks"] = [dict(period=float(tau[inds[0]]), period_uncert=float("nan"))]
+    return result
+
+
+def _design_matrix(periods, t0s, x):
+    two_pi = 2 * np.pi
+    if t0s is not None:
+        cols = [torch.cos(two_pi * (x - (t0s[i] - 0.25 * periods[i])) / periods[i]) for i in range(len(periods))]
+    else:
+        cols = [fn(two_pi * x / periods[i]) for i in range(len(periods)) for fn in (torch.sin, torch.cos)]
+    return torch.stack(cols + [torch.ones_like(x)], dim=1)
+
+
+def estimate_semi_amplitude(periods, x, y, yerr=None, t0s=None):
+    """Estimate the radial-velocity semi-amplitude of each planet (m/s) by weighted linear least squares: a sine and a cosine per
+    period and a constant, or, with the reference transit times ``t0s``, one cosine of known phase per planet.  A numpy array."""
+    dev = _device_of(x, y)
+    periods = np.atleast_1d(_np(periods))
+    t0s = None if t0s is None else np.atleast_1d(_np(t0s))
+    x, y = torch.atleast_1d(_to(x, dev)), torch.atleast_1d(_to(y, dev))
+    ivar = torch.ones_like(y) if yerr is None else 1.0 / torch.atleast_1d(_to(yerr, dev)).expand_as(y) ** 2
+    D = _design_matrix(periods, t0s, x)
+    w = torch.linalg.solve(D.T @ (D * ivar[:, None]), D.T @ (y * ivar))[:-1]
+    K = w if t0s is not None else torch.sqrt(w[::2] ** 2 + w[1::2] ** 2)
+    return _np(K)
+
+
+def estimate_minimum_mass(periods, x, y, yerr=None, t0s=None, m_star=1):
+    """Estimate the minimum mass ``m sin i`` of each planet in Jupiter masses from :func:`estimate_semi_amplitude`, for a star of
+    ``m_star`` solar masses and circular orbits: ``K / 28.4329 m/s * m_star^(2/3) * (P / yr)^(1/3)``."""
+    periods = np.atleast_1d(_np(periods))
+    K = estimate_semi_amplitude(periods, x, y, yerr=yerr, t0s=t0s)
+    return K / 28.4329 * float(m_star) ** (2.0 / 3) * (periods / 365.25) ** (1.0 / 3)

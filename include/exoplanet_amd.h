@@ -46,8 +46,9 @@ extern "C" {
  * 13: the MERGED sparse model -- exo_sparse_merge_workspace_bytes, exo_sparse_merge_layout, exo_sparse_model_merge_f64,
  *     exo_sparse_model_merged, exo_sparse_model_merge_vjp_f64: several lists per draw (planets, occultations) as one.
  * 14: EXO_GP_PREPARE_ADJOINT, a flag or-ed into n_chunks of a celerite pair (the adjoint scan beside the forward chunk kernel).
- * 15: the predictive variance -- exo_celerite_predict_var_work_doubles, exo_celerite_predict_var_f64. */
-#define EXO_ABI_VERSION 15
+ * 15: the predictive variance -- exo_celerite_predict_var_work_doubles, exo_celerite_predict_var_f64.
+ * 16: period search -- exo_bls_workspace_bytes, exo_bls_power_f64, exo_lomb_scargle_power_f64. */
+#define EXO_ABI_VERSION 16
 int32_t exo_abi_version(void);
 
 /* ---------------------------------------------------------------------------
@@ -796,6 +797,34 @@ int exo_sho_coefficients_multi_f64(const double* const* amp, const double* const
 int exo_sho_coefficients_multi_vjp_f64(const double* const* amp, const double* const* freq, const double* const* damp,
                                        const uint32_t* flags, int32_t n_terms, double eps, int64_t n, const double* gcoef,
                                        double* const* gamp, double* const* gfreq, double* const* gdamp, void* stream);
+
+/* ---------------------------------------------------------------------------
+ * Period search (exoplanet_amd/estimators.py; definitions: DESIGN.md section 9).  n_series series y[n_series][n] on one time
+ * axis t[n] (any order); yerr: n_yerr = 0 (none, unit weights), 1 (one row for every series) or n_series rows.  Kernels
+ * on the caller's stream only; `workspace` (device, 8-byte aligned) carries everything between them.
+ *
+ * Box least squares, the binned method: bins of width delta = min(durations) / oversample over the folded time, boxes of
+ * duration_bins[k] bins (HOST array, n_duration <= EXO_BLS_MAX_DURATIONS entries >= 1, round(duration / delta) taken by the
+ * caller), every start.  periods[n_period] on the device; min_bins and max_bins bound ceil(p / delta) + oversample over them
+ * (computed by the caller with the same fp64 division): a period's histogram lives in LDS up to 3835 bins and in a slab of
+ * the workspace above that.  out[7][n_series][n_period]: power, depth, depth_err, depth_snr, log_likelihood, duration,
+ * transit_time at the first maximiser of the objective; no admissible box: -inf, then NaN.  The bin sums are fp64 atomic
+ * adds: their last bits may differ from run to run.
+ *
+ * Lomb-Scargle: the exact floating-mean periodogram, "psd" normalisation, power[n_series][n_frequency] =
+ * (chi2_0 - chi2(f)) / 2.  Its workspace: exo_bls_workspace_bytes(n, n_series, 0, 0).
+ * ------------------------------------------------------------------------- */
+#define EXO_BLS_MAX_DURATIONS 16
+#define EXO_BLS_LIKELIHOOD 0
+#define EXO_BLS_SNR 1
+int64_t exo_bls_workspace_bytes(int64_t n, int64_t n_series, int64_t n_period, int64_t max_bins);
+int exo_bls_power_f64(const double* t, const double* y, const double* yerr, int64_t n_yerr, int64_t n, int64_t n_series,
+                      const double* periods, int64_t n_period, int64_t min_bins, int64_t max_bins, const int32_t* duration_bins,
+                      int32_t n_duration, double delta, int32_t oversample, int32_t objective, double* out, void* workspace,
+                      int64_t workspace_bytes, void* stream);
+int exo_lomb_scargle_power_f64(const double* t, const double* y, const double* yerr, int64_t n_yerr, int64_t n, int64_t n_series,
+                               const double* frequencies, int64_t n_frequency, double* power, void* workspace,
+                               int64_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }
