@@ -15,8 +15,12 @@ the time array and the flux array; ``ttv=`` for a TTVOrbit's timing tables),
 run hand-written HIP kernels through the C ABI (include/exoplanet_amd.h); each
 has value + gradient (torch.autograd).  There is no CPU / eager fallback.
 """
+import ctypes
 import os
+import warnings
+from typing import NamedTuple, Optional
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -66,8 +70,6 @@ def vouch_sorted(t):
     if len(_VOUCHED) >= 16:
         # the table holds sixteen series (an entry keeps its time array alive): the OLDEST word is taken back, with a warning --
         # that series falls back to the sweep's own device check inside later captures (slower, never wrong)
-        import warnings
-
         oldest = next(iter(_VOUCHED))
         _VOUCHED.pop(oldest)
         warnings.warn("vouch_sorted: more than 16 vouched series; the oldest one's word has been released (release_sorted "
@@ -146,6 +148,50 @@ def _ptr(x):
     return 0 if x is None else x.data_ptr()
 
 
+def _call(name, device, *args):
+    """the library entry ``name`` on ``device`` (None: a host-side query, no device to select); a failure is reported
+    under the same ``name``"""
+    fn = getattr(_lib.load(), name)
+    if device is None:
+        status = fn(*args)
+    else:
+        with torch.cuda.device(device):
+            status = fn(*args)
+    _lib.check(status, name)
+
+
+def _ptr_array(xs, n):
+    """a host array of ``n`` pointers: those of ``xs`` (None: null), the rest null"""
+    return (ctypes.c_void_p * n)(*[_ptr(x) for x in xs])
+
+
+def _workspace_bytes(N, D, P):
+    return _lib.load().exo_transit_flux_workspace_bytes(N, D, P)
+
+
+def _workspace(N, D, P, device, zero=False):
+    """(a sweep's workspace, its size in bytes).  The size need not be a multiple of 8 and the tensor is float64 (the
+    values of a sparse sweep are views of it): one double more than the bytes round down to"""
+    nbytes = _workspace_bytes(N, D, P)
+    return (torch.zeros if zero else torch.empty)(max(nbytes // 8 + 1, 1), dtype=torch.float64, device=device), nbytes
+
+
+def _layout(name, N, D, P):
+    lay = (ctypes.c_int64 * 5)()
+    _call(name, None, N, D, P, lay)
+    return list(lay)
+
+
+def _sparse_layout(N, D, P):
+    """byte offsets of (run counts, runs, prefix sums, values) in a sparse sweep's workspace, and the runs a list can hold"""
+    return _layout("exo_transit_flux_sparse_layout", N, D, P)
+
+
+def _merge_layout(N, D, P):
+    """byte offsets of (segment counts, segments, value offsets, values) in a merge workspace, and the segments a draw can hold"""
+    return _layout("exo_sparse_merge_layout", N, D, P)
+
+
 def is_cadence_major(x):
     """a (D, N) float64 device tensor laid out [cadence][draw] -- the transposed view of a contiguous (N, D) array: what
     the light-curve sweep returns under FLAG_CADENCE_MAJOR and what the celerite kernels read (and write the cotangent
@@ -166,10 +212,7 @@ class _Kepler(torch.autograd.Function):
             raise ValueError("kepler: M and ecc must have the same shape (the caller broadcasts, keplerian.py:333)")
         sinf = torch.empty_like(M)
         cosf = torch.empty_like(M)
-        lib = _lib.load()
-        with torch.cuda.device(M.device):
-            _lib.check(lib.exo_kepler_f64(_ptr(M), _ptr(ecc), _ptr(sinf), _ptr(cosf), M.numel(), _stream(M)),
-                       "exo_kepler_f64")
+        _call("exo_kepler_f64", M.device, _ptr(M), _ptr(ecc), _ptr(sinf), _ptr(cosf), M.numel(), _stream(M))
         ctx.save_for_backward(sinf, cosf, ecc)
         return sinf, cosf
 
@@ -192,24 +235,24 @@ def kepler(M, ecc):
 # ------------------------------------------------------------------------------
 # quad_solution_vector
 # ------------------------------------------------------------------------------
+def _quad_sv(b, r, derivs):
+    """(s, ds/db, ds/dr) of exo_quad_solution_vector_f64; the derivatives are None unless ``derivs``"""
+    b = _dev(b, "b")
+    r = _dev(r, "r")
+    if b.shape != r.shape:
+        raise ValueError("quad_solution_vector: b and r must have the same shape")
+    s = torch.empty(b.shape + (3,), dtype=torch.float64, device=b.device)
+    dsdb = torch.empty_like(s) if derivs else None
+    dsdr = torch.empty_like(s) if derivs else None
+    _call("exo_quad_solution_vector_f64", b.device, _ptr(b), _ptr(r), _ptr(s), _ptr(dsdb), _ptr(dsdr), b.numel(), _stream(b))
+    return s, dsdb, dsdr
+
+
 class _QuadSV(torch.autograd.Function):
     @staticmethod
     def forward(ctx, b, r):
-        b = _dev(b, "b")
-        r = _dev(r, "r")
-        if b.shape != r.shape:
-            raise ValueError("quad_solution_vector: b and r must have the same shape")
         need = any(ctx.needs_input_grad)   # (not .requires_grad: forward runs under no_grad and .contiguous() may copy)
-        s = torch.empty(b.shape + (3,), dtype=torch.float64, device=b.device)
-        dsdb = torch.empty_like(s) if need else None
-        dsdr = torch.empty_like(s) if need else None
-        lib = _lib.load()
-        with torch.cuda.device(b.device):
-            _lib.check(
-                lib.exo_quad_solution_vector_f64(_ptr(b), _ptr(r), _ptr(s), _ptr(dsdb), _ptr(dsdr), b.numel(),
-                                                 _stream(b)),
-                "exo_quad_solution_vector_f64",
-            )
+        s, dsdb, dsdr = _quad_sv(b, r, need)
         if need:
             ctx.save_for_backward(dsdb, dsdr)
         return s
@@ -229,19 +272,7 @@ def quad_solution_vector(b, r):
 def quad_solution_vector_derivs(b, r):
     """(s, ds/db, ds/dr), each [..., 3], as plain tensors -- for callers that carry their own
     differentiation (the PyTensor Op of compat_pytensor.py)."""
-    b = _dev(b, "b")
-    r = _dev(r, "r")
-    if b.shape != r.shape:
-        raise ValueError("quad_solution_vector: b and r must have the same shape")
-    s = torch.empty(b.shape + (3,), dtype=torch.float64, device=b.device)
-    dsdb, dsdr = torch.empty_like(s), torch.empty_like(s)
-    lib = _lib.load()
-    with torch.cuda.device(b.device):
-        _lib.check(
-            lib.exo_quad_solution_vector_f64(_ptr(b), _ptr(r), _ptr(s), _ptr(dsdb), _ptr(dsdr), b.numel(), _stream(b)),
-            "exo_quad_solution_vector_f64",
-        )
-    return s, dsdb, dsdr
+    return _quad_sv(b, r, True)
 
 
 # ------------------------------------------------------------------------------
@@ -255,19 +286,65 @@ def contact_points(a, e, cosw, sinw, cosi, sini, L):
     Ml = torch.empty_like(ref)
     Mr = torch.empty_like(ref)
     flag = torch.empty(ref.shape, dtype=torch.int32, device=ref.device)
-    lib = _lib.load()
-    with torch.cuda.device(ref.device):
-        _lib.check(
-            lib.exo_contact_points_f64(*[_ptr(x) for x in args], _ptr(Ml), _ptr(Mr), _ptr(flag), ref.numel(),
-                                       _stream(ref)),
-            "exo_contact_points_f64",
-        )
+    _call("exo_contact_points_f64", ref.device, *[_ptr(x) for x in args], _ptr(Ml), _ptr(Mr), _ptr(flag), ref.numel(),
+          _stream(ref))
     return Ml, Mr, flag
 
 
 # ------------------------------------------------------------------------------
 # fused transit flux
 # ------------------------------------------------------------------------------
+class _Sweep(NamedTuple):
+    """what every light-curve sweep of the C ABI takes first (include/exoplanet_amd.h), validated by _transit_args"""
+    t: torch.Tensor
+    texp: Optional[torch.Tensor]
+    n_texp: int
+    sdt: Optional[torch.Tensor]
+    sw: Optional[torch.Tensor]
+    n_sub: int
+    params: torch.Tensor
+    ld: torch.Tensor
+    D: int
+    P: int
+    N: int
+
+    def head(self, flags):
+        """the twelve leading arguments of a sweep"""
+        return (_ptr(self.t), self.N, _ptr(self.texp), self.n_texp, _ptr(self.sdt), _ptr(self.sw), self.n_sub,
+                _ptr(self.params), _ptr(self.ld), self.D, self.P, flags)
+
+    def ttv(self, ttv):
+        """(edges (D, P, E), shift (D, P, E + 1), E) of a timing-variation table (include/exoplanet_amd.h); E = 0: none"""
+        if ttv is None:
+            return _NO_TTV
+        edges, shift = ttv
+        edges = _dev(edges, "ttv edges")
+        shift = _dev(shift, "ttv shift")
+        if edges.dim() != 3 or tuple(edges.shape[:2]) != (self.D, self.P) or edges.shape[2] < 1:
+            raise ValueError("ttv edges must be (n_draw, n_planet, n_edge >= 1)")
+        if tuple(shift.shape) != (self.D, self.P, edges.shape[2] + 1):
+            raise ValueError("ttv shift must be (n_draw, n_planet, n_edge + 1)")
+        return edges, shift, int(edges.shape[2])
+
+
+_NO_TTV = (None, None, 0)
+
+
+def _exposure_args(t, texp, stencil_dt, stencil_w):
+    """(texp, n_texp, stencil_dt, stencil_w, n_sub) of a sweep over the cadences ``t``"""
+    if texp is None:
+        return None, 0, None, None, 1
+    texp = _dev(texp, "texp").reshape(-1)
+    stencil_dt = _dev(stencil_dt, "stencil_dt")
+    stencil_w = _dev(stencil_w, "stencil_w")
+    n_texp, n_sub = texp.numel(), stencil_dt.numel()
+    if n_texp not in (1, t.numel()):
+        raise ValueError("texp must be a scalar or have one entry per cadence")
+    if stencil_w.numel() != n_sub or not 1 <= n_sub <= MAX_SUBEXP:
+        raise ValueError(f"stencil must have 1..{MAX_SUBEXP} points")
+    return texp, n_texp, stencil_dt, stencil_w, n_sub
+
+
 def _transit_args(t, texp, stencil_dt, stencil_w, params, ld, flags):
     t = _dev(t, "t")
     params = _dev(params, "params")
@@ -282,33 +359,31 @@ def _transit_args(t, texp, stencil_dt, stencil_w, params, ld, flags):
         raise ValueError(f"ld must be (n_draw, {nld})")
     if not 1 <= P <= MAX_PLANETS:
         raise ValueError(f"1 <= n_planet <= {MAX_PLANETS}")
-    if texp is None:
-        n_texp, n_sub = 0, 1
-        stencil_dt = stencil_w = None
-    else:
-        texp = _dev(texp, "texp").reshape(-1)
-        stencil_dt = _dev(stencil_dt, "stencil_dt")
-        stencil_w = _dev(stencil_w, "stencil_w")
-        n_texp, n_sub = texp.numel(), stencil_dt.numel()
-        if n_texp not in (1, t.numel()):
-            raise ValueError("texp must be a scalar or have one entry per cadence")
-        if stencil_w.numel() != n_sub or not 1 <= n_sub <= MAX_SUBEXP:
-            raise ValueError(f"stencil must have 1..{MAX_SUBEXP} points")
-    return t, texp, n_texp, stencil_dt, stencil_w, n_sub, params, ld, D, P
+    texp, n_texp, stencil_dt, stencil_w, n_sub = _exposure_args(t, texp, stencil_dt, stencil_w)
+    return _Sweep(t, texp, n_texp, stencil_dt, stencil_w, n_sub, params, ld, D, P, t.numel())
 
 
-def _ttv_args(ttv, D, P):
-    """(edges (D, P, E), shift (D, P, E + 1)) of a timing-variation table (include/exoplanet_amd.h)"""
-    if ttv is None:
-        return None, None, 0
-    edges, shift = ttv
-    edges = _dev(edges, "ttv edges")
-    shift = _dev(shift, "ttv shift")
-    if edges.dim() != 3 or tuple(edges.shape[:2]) != (D, P) or edges.shape[2] < 1:
-        raise ValueError("ttv edges must be (n_draw, n_planet, n_edge >= 1)")
-    if tuple(shift.shape) != (D, P, edges.shape[2] + 1):
-        raise ValueError("ttv shift must be (n_draw, n_planet, n_edge + 1)")
-    return edges, shift, int(edges.shape[2])
+def _flux_shape(N, D, P, flags):
+    return (D, N, P) if flags & FLAG_PER_PLANET else (D, N)
+
+
+def _flux_out(N, D, P, flags, device):
+    """the dense flux array a sweep writes: rows, or under FLAG_CADENCE_MAJOR (D, N) with the draws innermost"""
+    if flags & FLAG_CADENCE_MAJOR:
+        return torch.empty((N, D), dtype=torch.float64, device=device).t()
+    return torch.empty(_flux_shape(N, D, P, flags), dtype=torch.float64, device=device)
+
+
+def _cotangent_layout(gflux, flags, cm_sweep, transpose):
+    """(gflux, flags) for a sweep that reads a cotangent.  It is taken as it comes: cadence-major (the celerite kernels'
+    gradient of a cadence-major model) or rows.  Only the run-enumeration sweeps read it cadence-major
+    (include/exoplanet_amd.h; ``cm_sweep``: this is one): anything else gets rows.  Rows under FLAG_CADENCE_MAJOR are
+    transposed if the caller lets them be (``transpose``), otherwise the flag goes."""
+    if is_cadence_major(gflux) and cm_sweep:
+        return gflux, flags | FLAG_CADENCE_MAJOR
+    if flags & FLAG_CADENCE_MAJOR and transpose and cm_sweep:
+        return _dev(gflux, "gflux").t().contiguous().t(), flags
+    return _dev(gflux, "gflux"), flags & ~FLAG_CADENCE_MAJOR
 
 
 # the Jacobian route of _TransitFlux: on from this many samples per cadence (with one sample a cadence the rows cost as much
@@ -348,62 +423,61 @@ def _jac_fits(nbytes, device):
 _JAC_CALLS = [0]        # forward sweeps that took the route (tests look at it)
 
 
+def _use_jac(a, flags, wanted, n_edge=0, excluded=0):
+    """the Jacobian route (include/exoplanet_amd.h, exo_transit_flux_fwd_jac_f64): when the gradient will be asked for
+    (``wanted``) and a cadence is several samples, the value sweep keeps every solved cadence's row of derivatives and
+    backward() is a contraction instead of a second sweep.  Returns the doubles the rows take, None for the two-sweep route.
+    Per-cadence exposure times, per-planet / exact-scan / light-delay sweeps have no Jacobian form (without these exclusions
+    the library refuses -- ADVICE r5: fall back to the two-sweep route instead); what else rules it out is the caller's:
+    _TransitFlux passes its timing tables (``n_edge``) and FLAG_SPARSE (``excluded``), _TransitFluxSparse has neither."""
+    if not (_JAC_ROUTE[0] and wanted and a.n_sub >= _JAC_MIN_SUB and not n_edge and a.n_texp <= 1
+            and not flags & (FLAG_PER_PLANET | FLAG_EXACT_SCAN | FLAG_LIGHT_DELAY | excluded)):
+        return None
+    n_jac = _lib.load().exo_transit_flux_jac_doubles(a.N, a.D, a.P)
+    # (the memory question last: it is a driver call -- ADVICE r5)
+    return n_jac if _jac_fits(8 * n_jac, a.t.device) else None
+
+
+def _forward_sweep(a, flags, ttv, flux, ws, nbytes, n_jac=None):
+    """the value sweep: with timing tables, on the Jacobian route (``n_jac`` doubles of rows: allocated here and returned)
+    or plain.  ``flux`` None: a sparse sweep, the values stay in the workspace."""
+    edges, shift, n_edge = ttv
+    dev, tail = a.t.device, (_ptr(ws), nbytes, _stream(a.t))
+    if n_jac is not None:
+        _JAC_CALLS[0] += 1
+        jac = torch.empty(n_jac, dtype=torch.float64, device=dev)
+        _call("exo_transit_flux_fwd_jac_f64", dev, *a.head(flags), _ptr(flux), _ptr(jac), n_jac, *tail)
+        return jac
+    if n_edge:
+        _call("exo_transit_flux_ttv_fwd_f64", dev, *a.head(flags), _ptr(edges), _ptr(shift), n_edge, _ptr(flux), *tail)
+    else:
+        _call("exo_transit_flux_fwd_f64", dev, *a.head(flags), _ptr(flux), *tail)
+    return None
+
+
+def _jac_vjp(g, t, D, P, flags, jac, ws, nbytes, params, ld):
+    """(gparams, gld): the rows a Jacobian-route forward sweep left, contracted with the cotangent ``g``"""
+    gparams, gld = torch.empty_like(params), torch.empty_like(ld)
+    _call("exo_transit_flux_jac_vjp_f64", t.device, _ptr(g), t.numel(), D, P, flags, _ptr(jac), _ptr(ws), nbytes,
+          _ptr(gparams), _ptr(gld), 0, _stream(t))
+    return gparams, gld
+
+
 class _TransitFlux(torch.autograd.Function):
     @staticmethod
     def forward(ctx, t, texp, stencil_dt, stencil_w, params, ld, flags, ttv_edges, ttv_shift, grad_mode=True):
-        t, texp, n_texp, sdt, sw, n_sub, params, ld, D, P = _transit_args(
-            t, texp, stencil_dt, stencil_w, params, ld, flags)
-        flags |= _sorted_flag(t)
-        edges, shift, n_edge = _ttv_args(None if ttv_edges is None else (ttv_edges, ttv_shift), D, P)
-        N = t.numel()
-        shape = (D, N, P) if flags & FLAG_PER_PLANET else (D, N)
-        if flags & FLAG_CADENCE_MAJOR:
-            if flags & FLAG_PER_PLANET:
-                raise ValueError("FLAG_CADENCE_MAJOR is a layout of the summed flux")
-            flux = torch.empty((N, D), dtype=torch.float64, device=t.device).t()     # (D, N), draws innermost
-        else:
-            flux = torch.empty(shape, dtype=torch.float64, device=t.device)
-        lib = _lib.load()
-        nbytes = lib.exo_transit_flux_workspace_bytes(N, D, P)
-        ws = torch.empty(max(nbytes // 8 + 1, 1), dtype=torch.float64, device=t.device)
-        # the Jacobian route (include/exoplanet_amd.h, exo_transit_flux_fwd_jac_f64): when the gradient will be asked for and a
-        # cadence is several samples, the value sweep keeps every solved cadence's row of derivatives and backward() is a
-        # contraction instead of a second sweep
-        n_jac = lib.exo_transit_flux_jac_doubles(N, D, P)
-        # (the memory question last: it is a driver call -- ADVICE r5)
-        use_jac = (_JAC_ROUTE[0] and grad_mode and (ctx.needs_input_grad[4] or ctx.needs_input_grad[5])
-                   and n_sub >= _JAC_MIN_SUB and not n_edge and n_texp <= 1
-                   and not flags & (FLAG_PER_PLANET | FLAG_SPARSE | FLAG_EXACT_SCAN | FLAG_LIGHT_DELAY)
-                   and _jac_fits(8 * n_jac, t.device))
-        ctx.jac = None
-        if use_jac:
-            _JAC_CALLS[0] += 1
-            jac = torch.empty(n_jac, dtype=torch.float64, device=t.device)
-            with torch.cuda.device(t.device):
-                _lib.check(lib.exo_transit_flux_fwd_jac_f64(_ptr(t), N, _ptr(texp), n_texp, _ptr(sdt), _ptr(sw), n_sub, _ptr(params),
-                                                            _ptr(ld), D, P, flags, _ptr(flux), _ptr(jac), n_jac, _ptr(ws), nbytes,
-                                                            _stream(t)), "exo_transit_flux_fwd_jac_f64")
-            ctx.jac = (jac, ws, nbytes)
-            ctx.save_for_backward(t, texp, sdt, sw, params, ld, edges, shift)
-            ctx.meta = (n_texp, n_sub, D, P, flags)
-            return flux
-        with torch.cuda.device(t.device):
-            if n_edge:
-                _lib.check(
-                    lib.exo_transit_flux_ttv_fwd_f64(_ptr(t), N, _ptr(texp), n_texp, _ptr(sdt), _ptr(sw), n_sub,
-                                                     _ptr(params), _ptr(ld), D, P, flags, _ptr(edges), _ptr(shift),
-                                                     n_edge, _ptr(flux), _ptr(ws), nbytes, _stream(t)),
-                    "exo_transit_flux_ttv_fwd_f64",
-                )
-            else:
-                _lib.check(
-                    lib.exo_transit_flux_fwd_f64(_ptr(t), N, _ptr(texp), n_texp, _ptr(sdt), _ptr(sw), n_sub,
-                                                 _ptr(params), _ptr(ld), D, P, flags, _ptr(flux), _ptr(ws), nbytes,
-                                                 _stream(t)),
-                    "exo_transit_flux_fwd_f64",
-                )
-        ctx.save_for_backward(t, texp, sdt, sw, params, ld, edges, shift)
-        ctx.meta = (n_texp, n_sub, D, P, flags)
+        a = _transit_args(t, texp, stencil_dt, stencil_w, params, ld, flags)
+        flags |= _sorted_flag(a.t)
+        ttv = a.ttv(None if ttv_edges is None else (ttv_edges, ttv_shift))
+        if flags & FLAG_CADENCE_MAJOR and flags & FLAG_PER_PLANET:
+            raise ValueError("FLAG_CADENCE_MAJOR is a layout of the summed flux")
+        flux = _flux_out(a.N, a.D, a.P, flags, a.t.device)
+        ws, nbytes = _workspace(a.N, a.D, a.P, a.t.device)
+        n_jac = _use_jac(a, flags, grad_mode and (ctx.needs_input_grad[4] or ctx.needs_input_grad[5]), ttv[2], FLAG_SPARSE)
+        jac = _forward_sweep(a, flags, ttv, flux, ws, nbytes, n_jac)
+        ctx.jac = None if jac is None else (jac, ws, nbytes)
+        ctx.save_for_backward(a.t, a.texp, a.sdt, a.sw, a.params, a.ld, ttv[0], ttv[1])
+        ctx.meta = (a.n_texp, a.n_sub, a.D, a.P, flags)
         return flux
 
     @staticmethod
@@ -411,71 +485,39 @@ class _TransitFlux(torch.autograd.Function):
         t, texp, sdt, sw, params, ld, edges, shift = ctx.saved_tensors
         n_texp, n_sub, D, P, flags = ctx.meta
         if ctx.jac is not None:
-            jac, ws, nbytes = ctx.jac
-            N = t.numel()
-            if is_cadence_major(gflux):
-                flags |= FLAG_CADENCE_MAJOR
-            else:
-                flags &= ~FLAG_CADENCE_MAJOR
-                gflux = _dev(gflux, "gflux")
-            gparams, gld = torch.empty_like(params), torch.empty_like(ld)
-            with torch.cuda.device(t.device):
-                _lib.check(_lib.load().exo_transit_flux_jac_vjp_f64(_ptr(gflux), N, D, P, flags, _ptr(jac), _ptr(ws), nbytes,
-                                                                    _ptr(gparams), _ptr(gld), 0, _stream(t)),
-                           "exo_transit_flux_jac_vjp_f64")
+            gflux, flags = _cotangent_layout(gflux, flags, True, False)
+            gparams, gld = _jac_vjp(gflux, t, D, P, flags, *ctx.jac, params, ld)
             return None, None, None, None, gparams, gld, None, None, None, None
-        ttv = None if edges is None else (edges, shift)
-        _, gparams, gld, _, gshift = _vjp(t, texp, n_texp, sdt, sw, n_sub, params, ld, D, P, flags, gflux, False,
-                                          ttv=ttv)
+        a = _Sweep(t, texp, n_texp, sdt, sw, n_sub, params, ld, D, P, t.numel())
+        _, gparams, gld, _, gshift = _vjp(a, flags, gflux, False, ttv=None if edges is None else (edges, shift))
         return None, None, None, None, gparams, gld, None, None, gshift, None
 
 
-def _vjp(t, texp, n_texp, sdt, sw, n_sub, params, ld, D, P, flags, gflux, want_flux, events=(None, None), ttv=None):
-    N = t.numel()
-    flags |= _sorted_flag(t)
-    shape = (D, N, P) if flags & FLAG_PER_PLANET else (D, N)
+def _vjp(a, flags, gflux, want_flux, events=(None, None), ttv=None, ws=None):
+    """the value + VJP sweep -> (flux | SparseFlux | None, gparams, gld, dot, gshift | None).  ``ws``: a caller's
+    (workspace, its bytes)"""
+    N, D, P, dev = a.N, a.D, a.P, a.t.device
+    flags |= _sorted_flag(a.t)
+    shape = _flux_shape(N, D, P, flags)
     if isinstance(gflux, torch.Tensor) and tuple(gflux.shape) != shape:
         raise ValueError(f"gflux must have shape {shape}")
-    edges, shift, n_edge = _ttv_args(ttv, D, P)
-    # the cotangent as it comes: cadence-major (the celerite kernels' gradient of a cadence-major model) or rows.  Only the
-    # run-enumeration sweeps read it cadence-major (include/exoplanet_amd.h): anything else gets rows
-    cm_sweep = (n_texp <= 1 and not flags & (FLAG_EXACT_SCAN | FLAG_PER_PLANET)
+    edges, shift, n_edge = a.ttv(ttv)
+    cm_sweep = (a.n_texp <= 1 and not flags & (FLAG_EXACT_SCAN | FLAG_PER_PLANET)
                 and not (n_edge and flags & (FLAG_SECONDARY | FLAG_LIGHT_DELAY)))
-    if is_cadence_major(gflux) and cm_sweep:
-        flags |= FLAG_CADENCE_MAJOR
-    elif flags & FLAG_CADENCE_MAJOR and want_flux and cm_sweep:
-        gflux = _dev(gflux, "gflux").t().contiguous().t()
-    else:
-        flags &= ~FLAG_CADENCE_MAJOR
-        gflux = _dev(gflux, "gflux")
-    lib = _lib.load()
-    nbytes = lib.exo_transit_flux_workspace_bytes(N, D, P)
-    ws = torch.empty(max(nbytes // 8 + 1, 1), dtype=torch.float64, device=t.device)
-    gparams = torch.empty_like(params)
-    gld = torch.empty_like(ld)
-    dot = torch.empty(D, dtype=torch.float64, device=t.device)
-    flux = None
-    if want_flux and not flags & FLAG_SPARSE:
-        flux = (torch.empty((N, D), dtype=torch.float64, device=t.device).t() if flags & FLAG_CADENCE_MAJOR
-                else torch.empty(shape, dtype=torch.float64, device=t.device))
+    gflux, flags = _cotangent_layout(gflux, flags, cm_sweep, want_flux)
+    ws, nbytes = ws or _workspace(N, D, P, dev)
+    gparams = torch.empty_like(a.params)
+    gld = torch.empty_like(a.ld)
+    dot = torch.empty(D, dtype=torch.float64, device=dev)
+    flux = _flux_out(N, D, P, flags, dev) if want_flux and not flags & FLAG_SPARSE else None
     gshift = torch.empty_like(shift) if n_edge else None
-    with torch.cuda.device(t.device):
-        if n_edge:
-            _lib.check(
-                lib.exo_transit_flux_ttv_vjp_f64(_ptr(t), N, _ptr(texp), n_texp, _ptr(sdt), _ptr(sw), n_sub,
-                                                 _ptr(params), _ptr(ld), D, P, flags, _ptr(edges), _ptr(shift),
-                                                 n_edge, _ptr(gflux), _ptr(flux), _ptr(gparams), _ptr(gld),
-                                                 _ptr(gshift), _ptr(dot), _ptr(ws), nbytes, _stream(t)),
-                "exo_transit_flux_ttv_vjp_f64",
-            )
-        else:
-            _lib.check(
-                lib.exo_transit_flux_vjp_ev_f64(_ptr(t), N, _ptr(texp), n_texp, _ptr(sdt), _ptr(sw), n_sub,
-                                                _ptr(params), _ptr(ld), D, P, flags, _ptr(gflux), _ptr(flux),
-                                                _ptr(gparams), _ptr(gld), _ptr(dot), _ptr(ws), nbytes, _stream(t),
-                                                events[0], events[1]),
-                "exo_transit_flux_vjp_f64",
-            )
+    tail = (_ptr(ws), nbytes, _stream(a.t))
+    if n_edge:
+        _call("exo_transit_flux_ttv_vjp_f64", dev, *a.head(flags), _ptr(edges), _ptr(shift), n_edge, _ptr(gflux), _ptr(flux),
+              _ptr(gparams), _ptr(gld), _ptr(gshift), _ptr(dot), *tail)
+    else:
+        _call("exo_transit_flux_vjp_ev_f64", dev, *a.head(flags), _ptr(gflux), _ptr(flux), _ptr(gparams), _ptr(gld), _ptr(dot),
+              *tail, events[0], events[1])
     if flags & FLAG_SPARSE:
         flux = _sparse_from_ws(ws, N, D, P, flags)
     return flux, gparams, gld, dot, gshift
@@ -483,11 +525,7 @@ def _vjp(t, texp, n_texp, sdt, sw, n_sub, params, ld, D, P, flags, gflux, want_f
 
 def _sparse_from_ws(ws, N, D, P, flags):
     """the sweep's output lives in its workspace (include/exoplanet_amd.h, EXO_FLAG_SPARSE)"""
-    import ctypes
-
-    lay = (ctypes.c_int64 * 5)()
-    _lib.check(_lib.load().exo_transit_flux_sparse_layout(N, D, P, lay), "exo_transit_flux_sparse_layout")
-    return SparseFlux(ws, list(lay), N, D, P, 2 if flags & FLAG_SECONDARY else 1)
+    return SparseFlux(ws, _sparse_layout(N, D, P), N, D, P, 2 if flags & FLAG_SECONDARY else 1)
 
 
 def transit_flux(t, params, ld, texp=None, stencil_dt=None, stencil_w=None, flags=0, ttv=None):
@@ -514,9 +552,8 @@ def transit_flux_value_and_vjp(t, params, ld, gflux, texp=None, stencil_dt=None,
     ``events``: optional (hipEvent_t, hipEvent_t) handles (ints) recorded around
     the dominant kernel (profiling hook of the C ABI)."""
     flags = int(flags)
-    t, texp, n_texp, sdt, sw, n_sub, params, ld, D, P = _transit_args(t, texp, stencil_dt, stencil_w, params, ld,
-                                                                      flags)
-    out = _vjp(t, texp, n_texp, sdt, sw, n_sub, params, ld, D, P, flags, gflux, True, events, ttv=ttv)
+    a = _transit_args(t, texp, stencil_dt, stencil_w, params, ld, flags)
+    out = _vjp(a, flags, gflux, True, events, ttv=ttv)
     return out[:3] if ttv is None else out[:3] + (out[4],)
 
 
@@ -527,11 +564,9 @@ class _TransitFluxDot(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, t, texp, stencil_dt, stencil_w, params, ld, gflux, flags, events, ttv_edges, ttv_shift):
-        t, texp, n_texp, sdt, sw, n_sub, params, ld, D, P = _transit_args(
-            t, texp, stencil_dt, stencil_w, params, ld, flags)
+        a = _transit_args(t, texp, stencil_dt, stencil_w, params, ld, flags)
         ttv = None if ttv_edges is None else (ttv_edges, ttv_shift)
-        flux, gparams, gld, dot, gshift = _vjp(t, texp, n_texp, sdt, sw, n_sub, params, ld, D, P, flags, gflux, True,
-                                               events, ttv=ttv)
+        flux, gparams, gld, dot, gshift = _vjp(a, flags, gflux, True, events, ttv=ttv)
         ctx.save_for_backward(gparams, gld, gshift)
         ctx.set_materialize_grads(False)  # never build a (D, N) zero cotangent for the detached flux
         if isinstance(flux, SparseFlux):
@@ -563,6 +598,25 @@ def transit_flux_dot(t, params, ld, gflux, texp=None, stencil_dt=None, stencil_w
     return out
 
 
+def _chi2_launch(a, flags, ttv_edges, ttv_shift, obs, ivar):
+    """exo_transit_chi2[_ttv]_vjp_f64 -> (chi2 (D,), gparams, gld, gshift | None)"""
+    flags |= _sorted_flag(a.t)
+    edges, shift, n_edge = a.ttv(None if ttv_edges is None else (ttv_edges, ttv_shift))
+    dev = a.t.device
+    ws, nbytes = _workspace(a.N, a.D, a.P, dev)
+    chi2 = torch.empty(a.D, dtype=torch.float64, device=dev)
+    gparams = torch.empty_like(a.params)
+    gld = torch.empty_like(a.ld)
+    gshift = torch.empty_like(shift) if n_edge else None
+    data = (_ptr(obs), _ptr(ivar), ivar.numel(), _ptr(chi2), _ptr(gparams), _ptr(gld))
+    tail = (_ptr(ws), nbytes, _stream(a.t))
+    if n_edge:
+        _call("exo_transit_chi2_ttv_vjp_f64", dev, *a.head(flags), _ptr(edges), _ptr(shift), n_edge, *data, _ptr(gshift), *tail)
+    else:
+        _call("exo_transit_chi2_vjp_f64", dev, *a.head(flags), *data, *tail)
+    return chi2, gparams, gld, gshift
+
+
 class _TransitChi2(torch.autograd.Function):
     """chi2[d] = sum_n w_n ((f[d, n] - obs[n])^2 - obs[n]^2) over the cadences solved for draw d, and -- computed in the
     same call, like transit_flux_dot -- its gradient with respect to params and ld (exo_transit_chi2_vjp_f64)."""
@@ -574,37 +628,15 @@ class _TransitChi2(torch.autograd.Function):
             raise NotImplementedError(
                 "transit_chi2 is not differentiable with respect to obs / ivar: per-draw error bars go through "
                 "white_noise_loglike(yerr=(n_draw, 1) tensor), anything else through get_light_curve(total=True) and torch")
-        t, texp, n_texp, sdt, sw, n_sub, params, ld, D, P = _transit_args(t, texp, stencil_dt, stencil_w, params, ld, flags)
-        flags |= _sorted_flag(t)
-        edges, shift, n_edge = _ttv_args(None if ttv_edges is None else (ttv_edges, ttv_shift), D, P)
-        N = t.numel()
+        a = _transit_args(t, texp, stencil_dt, stencil_w, params, ld, flags)
         obs = _dev(obs, "obs")
         ivar = _dev(ivar, "ivar").reshape(-1)
-        if tuple(obs.shape) != (N,):
+        if tuple(obs.shape) != (a.N,):
             raise ValueError("obs must have shape (n_cad,)")
-        if ivar.numel() not in (1, N):
+        if ivar.numel() not in (1, a.N):
             raise ValueError("ivar must be a scalar or have one entry per cadence")
-        lib = _lib.load()
-        nbytes = lib.exo_transit_flux_workspace_bytes(N, D, P)
-        ws = torch.empty(max(nbytes // 8 + 1, 1), dtype=torch.float64, device=t.device)
-        chi2 = torch.empty(D, dtype=torch.float64, device=t.device)
-        gparams = torch.empty_like(params)
-        gld = torch.empty_like(ld)
-        gshift = torch.empty_like(shift) if n_edge else None
-        with torch.cuda.device(t.device):
-            if n_edge:
-                _lib.check(lib.exo_transit_chi2_ttv_vjp_f64(_ptr(t), N, _ptr(texp), n_texp, _ptr(sdt), _ptr(sw), n_sub,
-                                                            _ptr(params), _ptr(ld), D, P, flags, _ptr(edges), _ptr(shift),
-                                                            n_edge, _ptr(obs), _ptr(ivar), ivar.numel(), _ptr(chi2),
-                                                            _ptr(gparams), _ptr(gld), _ptr(gshift), _ptr(ws), nbytes,
-                                                            _stream(t)), "exo_transit_chi2_ttv_vjp_f64")
-                ctx.save_for_backward(gparams, gld, gshift)
-            else:
-                _lib.check(lib.exo_transit_chi2_vjp_f64(_ptr(t), N, _ptr(texp), n_texp, _ptr(sdt), _ptr(sw), n_sub, _ptr(params),
-                                                        _ptr(ld), D, P, flags, _ptr(obs), _ptr(ivar), ivar.numel(), _ptr(chi2),
-                                                        _ptr(gparams), _ptr(gld), _ptr(ws), nbytes, _stream(t)),
-                           "exo_transit_chi2_vjp_f64")
-                ctx.save_for_backward(gparams, gld)
+        chi2, gparams, gld, gshift = _chi2_launch(a, flags, ttv_edges, ttv_shift, obs, ivar)
+        ctx.save_for_backward(gparams, gld, *([] if gshift is None else [gshift]))
         return chi2
 
     @staticmethod
@@ -753,8 +785,6 @@ class SparseFlux:
         """(D, N) summed flux, or (D, N, P): rebuilt on the host (tests / plots)"""
         nrun, runs = self.nrun.cpu().numpy(), self.runs.cpu().numpy()
         pre, vals = self.pre_all.cpu().numpy(), self.vals.cpu().numpy()
-        import numpy as np
-
         out = np.zeros((self.n_draw, self.n_cad, self.n_planet))
         for d in range(self.n_draw):
             for p in range(self.n_planet):
@@ -774,50 +804,22 @@ def transit_flux_sparse(t, params, ld, gflux=None, texp=None, stencil_dt=None, s
     Needs sorted times, a scalar (or no) exposure time and no FLAG_EXACT_SCAN; ``ttv = (edges, shift)``:
     timing tables (transits only)."""
     flags = int(flags) | FLAG_SPARSE
-    t, texp, n_texp, sdt, sw, n_sub, params, ld, D, P = _transit_args(t, texp, stencil_dt, stencil_w, params, ld, flags)
-    flags |= _sorted_flag(t)
-    edges, shift, n_edge = _ttv_args(ttv, D, P)
-    if n_edge and flags & FLAG_SECONDARY:
+    a = _transit_args(t, texp, stencil_dt, stencil_w, params, ld, flags)
+    if ttv is not None and flags & FLAG_SECONDARY:
         raise ValueError("the sparse sweep takes timing tables for transits only")
-    N = t.numel()
-    lib = _lib.load()
-    nbytes = lib.exo_transit_flux_workspace_bytes(N, D, P)
+    N, D, P = a.N, a.D, a.P
     if ws is None:
-        ws = torch.empty(max(nbytes // 8 + 1, 1), dtype=torch.float64, device=t.device)
-    elif ws.dtype != torch.float64 or ws.numel() * 8 < nbytes or not ws.is_contiguous() or ws.device != t.device:
-        raise ValueError("ws: a contiguous float64 tensor of at least exo_transit_flux_workspace_bytes on the device of t")
-    import ctypes
-
-    lay = (ctypes.c_int64 * 5)()
-    _lib.check(lib.exo_transit_flux_sparse_layout(N, D, P, lay), "exo_transit_flux_sparse_layout")
-    n_ev = 2 if flags & FLAG_SECONDARY else 1
-    with torch.cuda.device(t.device):
-        if gflux is None:
-            if n_edge:
-                _lib.check(lib.exo_transit_flux_ttv_fwd_f64(_ptr(t), N, _ptr(texp), n_texp, _ptr(sdt), _ptr(sw), n_sub,
-                                                            _ptr(params), _ptr(ld), D, P, flags, _ptr(edges), _ptr(shift),
-                                                            n_edge, 0, _ptr(ws), nbytes, _stream(t)),
-                           "exo_transit_flux_ttv_fwd_f64")
-            else:
-                _lib.check(lib.exo_transit_flux_fwd_f64(_ptr(t), N, _ptr(texp), n_texp, _ptr(sdt), _ptr(sw), n_sub, _ptr(params),
-                                                        _ptr(ld), D, P, flags, 0, _ptr(ws), nbytes, _stream(t)),
-                           "exo_transit_flux_fwd_f64")
-            return SparseFlux(ws, list(lay), N, D, P, n_ev)
-        gflux = _dev(gflux, "gflux")
-        gparams, gld = torch.empty_like(params), torch.empty_like(ld)
-        dot = torch.empty(D, dtype=torch.float64, device=t.device)
-        if n_edge:
-            gshift = torch.empty_like(shift)
-            _lib.check(lib.exo_transit_flux_ttv_vjp_f64(_ptr(t), N, _ptr(texp), n_texp, _ptr(sdt), _ptr(sw), n_sub,
-                                                        _ptr(params), _ptr(ld), D, P, flags, _ptr(edges), _ptr(shift),
-                                                        n_edge, _ptr(gflux), 0, _ptr(gparams), _ptr(gld), _ptr(gshift),
-                                                        _ptr(dot), _ptr(ws), nbytes, _stream(t)),
-                       "exo_transit_flux_ttv_vjp_f64")
-            return SparseFlux(ws, list(lay), N, D, P, n_ev), gparams, gld, dot, gshift
-        _lib.check(lib.exo_transit_flux_vjp_f64(_ptr(t), N, _ptr(texp), n_texp, _ptr(sdt), _ptr(sw), n_sub, _ptr(params),
-                                                _ptr(ld), D, P, flags, _ptr(gflux), 0, _ptr(gparams), _ptr(gld), _ptr(dot),
-                                                _ptr(ws), nbytes, _stream(t)), "exo_transit_flux_vjp_f64")
-    return SparseFlux(ws, list(lay), N, D, P, n_ev), gparams, gld, dot
+        ws, nbytes = _workspace(N, D, P, a.t.device)
+    else:
+        nbytes = _workspace_bytes(N, D, P)
+        if ws.dtype != torch.float64 or ws.numel() * 8 < nbytes or not ws.is_contiguous() or ws.device != a.t.device:
+            raise ValueError("ws: a contiguous float64 tensor of at least exo_transit_flux_workspace_bytes on the device of t")
+    if gflux is None:
+        _forward_sweep(a, flags | _sorted_flag(a.t), a.ttv(ttv), None, ws, nbytes)
+        return _sparse_from_ws(ws, N, D, P, flags)
+    # (the cotangent in rows and no dense flux: the sweep reads it at the solved cadences only)
+    out = _vjp(a, flags, _dev(gflux, "gflux"), False, ttv=ttv, ws=(ws, nbytes))
+    return out[:4] if ttv is None else out
 
 
 # ------------------------------------------------------------------------------
@@ -847,41 +849,18 @@ class _TransitFluxSparse(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, t, texp, stencil_dt, stencil_w, params, ld, flags, box, grad_mode):
-        import ctypes
-
-        t, texp, n_texp, sdt, sw, n_sub, params, ld, D, P = _transit_args(t, texp, stencil_dt, stencil_w, params, ld, flags)
-        flags = (flags | FLAG_SPARSE | _sorted_flag(t)) & ~FLAG_CADENCE_MAJOR
-        N = t.numel()
-        lib = _lib.load()
-        nbytes = lib.exo_transit_flux_workspace_bytes(N, D, P)
-        ws = torch.empty(max(nbytes // 8 + 1, 1), dtype=torch.float64, device=t.device)
-        lay = (ctypes.c_int64 * 5)()
-        _lib.check(lib.exo_transit_flux_sparse_layout(N, D, P, lay), "exo_transit_flux_sparse_layout")
-        need = ctx.needs_input_grad[4] or ctx.needs_input_grad[5]
-        n_jac = lib.exo_transit_flux_jac_doubles(N, D, P)
+        a = _transit_args(t, texp, stencil_dt, stencil_w, params, ld, flags)
+        flags = (flags | FLAG_SPARSE | _sorted_flag(a.t)) & ~FLAG_CADENCE_MAJOR
+        N, D, P = a.N, a.D, a.P
+        ws, nbytes = _workspace(N, D, P, a.t.device)
+        off_vals = _sparse_layout(N, D, P)[3]
         # (grad_mode: torch.is_grad_enabled() of the CALLER -- inside forward() it is always off; under no_grad the rows of
         # derivatives would be written for nothing: ADVICE r4)
-        # the same exclusions as _TransitFlux (per-cadence exposure times, per-planet / exact-scan / light-delay sweeps have no
-        # Jacobian form: without them the library refuses -- ADVICE r5: fall back to the two-sweep route instead)
-        use_jac = (_JAC_ROUTE[0] and need and grad_mode and n_sub >= _JAC_MIN_SUB and n_texp <= 1
-                   and not flags & (FLAG_PER_PLANET | FLAG_EXACT_SCAN | FLAG_LIGHT_DELAY)
-                   and _jac_fits(8 * n_jac, t.device))
-        ctx.jac = None
-        with torch.cuda.device(t.device):
-            if use_jac:
-                _JAC_CALLS[0] += 1
-                jac = torch.empty(n_jac, dtype=torch.float64, device=t.device)
-                _lib.check(lib.exo_transit_flux_fwd_jac_f64(_ptr(t), N, _ptr(texp), n_texp, _ptr(sdt), _ptr(sw), n_sub, _ptr(params),
-                                                            _ptr(ld), D, P, flags, 0, _ptr(jac), n_jac, _ptr(ws), nbytes,
-                                                            _stream(t)), "exo_transit_flux_fwd_jac_f64")
-                ctx.jac = jac
-            else:
-                _lib.check(lib.exo_transit_flux_fwd_f64(_ptr(t), N, _ptr(texp), n_texp, _ptr(sdt), _ptr(sw), n_sub, _ptr(params),
-                                                        _ptr(ld), D, P, flags, 0, _ptr(ws), nbytes, _stream(t)),
-                           "exo_transit_flux_fwd_f64")
-        vals = ws[lay[3] // 8: lay[3] // 8 + D * P * N].view(D, P * N)
-        ctx.save_for_backward(t, texp, sdt, sw, params, ld)
-        ctx.meta = (n_texp, n_sub, D, P, flags, nbytes)
+        n_jac = _use_jac(a, flags, grad_mode and (ctx.needs_input_grad[4] or ctx.needs_input_grad[5]))
+        ctx.jac = _forward_sweep(a, flags, _NO_TTV, None, ws, nbytes, n_jac)
+        vals = ws[off_vals // 8: off_vals // 8 + D * P * N].view(D, P * N)
+        ctx.save_for_backward(a.t, a.texp, a.sdt, a.sw, a.params, a.ld)
+        ctx.meta = (a.n_texp, a.n_sub, D, P, flags, nbytes)
         ctx.ws = ws
         box.append(ws)      # (the workspace is not an autograd output -- `vals` is a view of it: the caller's box keeps it)
         return vals
@@ -895,18 +874,28 @@ class _TransitFluxSparse(torch.autograd.Function):
             return (None,) * 9
         if not gvals.is_contiguous() or tuple(gvals.shape) != (D, P * N):
             raise ValueError("the cotangent of a sparse light curve's values must be a contiguous (n_draw, n_planet * n_cad) array")
-        gparams, gld = torch.empty_like(params), torch.empty_like(ld)
-        lib = _lib.load()
-        with torch.cuda.device(t.device):
-            if ctx.jac is not None:
-                _lib.check(lib.exo_transit_flux_jac_vjp_f64(_ptr(gvals), N, D, P, flags, _ptr(ctx.jac), _ptr(ctx.ws), nbytes,
-                                                            _ptr(gparams), _ptr(gld), 0, _stream(t)), "exo_transit_flux_jac_vjp_f64")
-            else:
-                _lib.check(lib.exo_transit_flux_vjp_sparse_f64(_ptr(t), N, _ptr(texp), n_texp, _ptr(sdt), _ptr(sw), n_sub,
-                                                               _ptr(params), _ptr(ld), D, P, flags, _ptr(gvals), _ptr(gparams),
-                                                               _ptr(gld), 0, _ptr(ctx.ws), nbytes, 1, _stream(t)),
-                           "exo_transit_flux_vjp_sparse_f64")
+        if ctx.jac is not None:
+            gparams, gld = _jac_vjp(gvals, t, D, P, flags, ctx.jac, ctx.ws, nbytes, params, ld)
+        else:
+            gparams, gld = torch.empty_like(params), torch.empty_like(ld)
+            a = _Sweep(t, texp, n_texp, sdt, sw, n_sub, params, ld, D, P, N)
+            _call("exo_transit_flux_vjp_sparse_f64", t.device, *a.head(flags), _ptr(gvals), _ptr(gparams), _ptr(gld), 0,
+                  _ptr(ctx.ws), nbytes, 1, _stream(t))
         return None, None, None, None, gparams, gld, None, None, None
+
+
+def _expand_runs(lo, hi, count, vstart, draw):
+    """flat index lists (position in values.view(-1), cadence, draw) of every cadence in runs [lo, hi) -- tensors (..., K) of
+    which the first ``count`` (...,) of a row are live --, ``vstart`` the position of a run's first value, ``draw`` its draw
+    (broadcast against lo); built with torch ops"""
+    dev = lo.device
+    live = torch.arange(lo.shape[-1], device=dev) < count.unsqueeze(-1)
+    flat_len = torch.where(live, hi - lo, torch.zeros_like(lo)).reshape(-1)
+    total = int(flat_len.sum().item())
+    rid = torch.repeat_interleave(torch.arange(flat_len.numel(), device=dev), flat_len, output_size=total)
+    start = torch.cumsum(flat_len, 0) - flat_len
+    within = torch.arange(total, device=dev) - start[rid]
+    return vstart.reshape(-1)[rid] + within, lo.reshape(-1)[rid] + within, draw.expand_as(lo).reshape(-1)[rid]
 
 
 class _SparseToDense(torch.autograd.Function):
@@ -918,7 +907,12 @@ class _SparseToDense(torch.autograd.Function):
     def forward(ctx, vals, sp):
         idx_val, idx_cad, idx_draw = sp._indices()
         out = torch.zeros(sp.n_draw, sp.n_cad, dtype=torch.float64, device=vals.device)
-        out.index_put_((idx_draw, idx_cad), vals.reshape(-1)[idx_val], accumulate=True)
+        # the lists of a draw (planets, occultations) may cover the same cadence, and their values add up; a merged light
+        # curve's segments are disjoint: plain assignment
+        if sp._lists_overlap:
+            out.index_put_((idx_draw, idx_cad), vals.reshape(-1)[idx_val], accumulate=True)
+        else:
+            out[idx_draw, idx_cad] = vals.reshape(-1)[idx_val]
         ctx.sp = sp
         return out
 
@@ -926,7 +920,8 @@ class _SparseToDense(torch.autograd.Function):
     def backward(ctx, gout):
         sp = ctx.sp
         idx_val, idx_cad, idx_draw = sp._indices()
-        g = torch.zeros(sp.n_draw, sp.n_planet * sp.n_cad, dtype=torch.float64, device=gout.device)
+        # (the cotangent in the layout of `values`: the sweep's (D, P * N), or (D, N) of a merged light curve)
+        g = torch.zeros(sp.n_draw, sp._values_per_draw(), dtype=torch.float64, device=gout.device)
         g.view(-1)[idx_val] = gout[idx_draw, idx_cad]
         return g, None
 
@@ -949,24 +944,23 @@ class SparseLightCurve:
     def model_struct(self):
         """exo_sparse_model for the celerite entries (a host struct of device pointers: keep ``self`` alive while it is used)"""
         m = _lib.SparseModel()
-        import ctypes
-
         n_ev = 2 if self.flags & FLAG_SECONDARY else 1
         if self.n_planet * n_ev != 1:
             raise ValueError("a sparse GaussianProcess mean is one list of segments per draw; this light curve has "
                              f"{self.n_planet} planet(s) x {n_ev} event(s): use .merged() (or .dense())")
-
-        nbytes = _lib.load().exo_transit_flux_workspace_bytes(self.n_cad, self.n_draw, self.n_planet)
-        _lib.check(_lib.load().exo_transit_flux_sparse_model(_ptr(self._ws), nbytes, self.n_cad, self.n_draw, self.n_planet,
-                                                             self.flags & FLAG_SECONDARY, ctypes.addressof(m)),
-                   "exo_transit_flux_sparse_model")
+        _call("exo_transit_flux_sparse_model", None, _ptr(self._ws), _workspace_bytes(self.n_cad, self.n_draw, self.n_planet),
+              self.n_cad, self.n_draw, self.n_planet, self.flags & FLAG_SECONDARY, ctypes.addressof(m))
         return m
+
+    _lists_overlap = True       # (several lists per draw: _SparseToDense)
+
+    def _values_per_draw(self):
+        return self.n_planet * self.n_cad
 
     def _indices(self):
         """(position in values.view(-1), cadence, draw) of every solved cadence -- built with torch ops from the runs"""
         lay = self.layout()
         D, P, N = self.n_draw, self.n_planet, self.n_cad
-        n_ev = lay.n_ev
         nrun = lay.nrun.long()                                   # (D, P, n_ev)
         K = int(nrun.max().item()) if nrun.numel() else 0
         dev = self.values.device
@@ -974,24 +968,13 @@ class SparseLightCurve:
             z = torch.zeros(0, dtype=torch.long, device=dev)
             return z, z, z
         runs = lay.runs[..., :K, :].long()                       # (D, P, n_ev, K, 4)
-        lo, hi = runs[..., 0], runs[..., 3]
-        live = torch.arange(K, device=dev) < nrun.unsqueeze(-1)
-        ln = torch.where(live, hi - lo, torch.zeros_like(lo))    # (D, P, n_ev, K)
         pre = lay.pre_all[..., :K].long()
         tot = torch.gather(lay.pre_all.long(), -1, nrun.unsqueeze(-1)).squeeze(-1)          # (D, P, n_ev)
         evbase = torch.cumsum(tot, -1) - tot                      # occultations behind the transits
         d_i = torch.arange(D, device=dev).view(D, 1, 1, 1)
         p_i = torch.arange(P, device=dev).view(1, P, 1, 1)
         vbase = (d_i * P + p_i) * N + evbase.unsqueeze(-1) + pre  # first value of every run
-        flat_len = ln.reshape(-1)
-        total = int(flat_len.sum().item())
-        rid = torch.repeat_interleave(torch.arange(flat_len.numel(), device=dev), flat_len, output_size=total)
-        start = torch.cumsum(flat_len, 0) - flat_len
-        within = torch.arange(total, device=dev) - start[rid]
-        idx_val = vbase.reshape(-1)[rid] + within
-        idx_cad = lo.reshape(-1)[rid] + within
-        idx_draw = d_i.expand_as(ln).reshape(-1)[rid]
-        return idx_val, idx_cad, idx_draw
+        return _expand_runs(runs[..., 0], runs[..., 3], nrun, vbase, d_i)
 
     def dense(self):
         """the (draws, cadences) summed flux, differentiable"""
@@ -1028,6 +1011,10 @@ _POISON = [None]    # tests: fill the merge workspace and its cotangent buffer w
                     # held before the call -- under hipGraph replay that is the previous step's: gp/celerite.py has the same hook)
 
 
+def _merge_bytes(N, D, P):
+    return _lib.load().exo_sparse_merge_workspace_bytes(N, D, P)
+
+
 def _scratch(n, device):
     x = torch.empty(n, dtype=torch.float64, device=device)
     if _POISON[0] is not None:
@@ -1042,21 +1029,15 @@ class _MergeSparse(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, vals, sp, box):
-        lib = _lib.load()
         N, D, P = sp.n_cad, sp.n_draw, sp.n_planet
-        nbytes = lib.exo_transit_flux_workspace_bytes(N, D, P)
-        mbytes = lib.exo_sparse_merge_workspace_bytes(N, D, P)
+        nbytes, mbytes = _workspace_bytes(N, D, P), _merge_bytes(N, D, P)
         mws = _scratch(max(mbytes // 8 + 1, 1), vals.device)
-        with torch.cuda.device(vals.device):
-            _lib.check(lib.exo_sparse_model_merge_f64(_ptr(sp._ws), nbytes, N, D, P, sp.flags & FLAG_SECONDARY, _ptr(mws), mbytes,
-                                                      None, _stream(vals)), "exo_sparse_model_merge_f64")
-        import ctypes
-
-        lay = (ctypes.c_int64 * 5)()
-        _lib.check(lib.exo_sparse_merge_layout(N, D, P, lay), "exo_sparse_merge_layout")
+        _call("exo_sparse_model_merge_f64", vals.device, _ptr(sp._ws), nbytes, N, D, P, sp.flags & FLAG_SECONDARY, _ptr(mws),
+              mbytes, None, _stream(vals))
+        off_vals = _merge_layout(N, D, P)[3]
         ctx.sp, ctx.mws, ctx.sizes = sp, mws, (nbytes, mbytes)
         box.append(mws)
-        return mws[lay[3] // 8: lay[3] // 8 + D * N].view(D, N)
+        return mws[off_vals // 8: off_vals // 8 + D * N].view(D, N)
 
     @staticmethod
     def backward(ctx, gm):
@@ -1067,10 +1048,8 @@ class _MergeSparse(torch.autograd.Function):
             raise ValueError("the cotangent of a merged sparse light curve's values must be a contiguous (n_draw, n_cad) array")
         # (only the positions the lists cover are defined, as in `vals` itself -- gp/celerite.py, _CeleriteLogLikeSparse.backward)
         gvals = _scratch(D * P * N, gm.device).view(D, P * N)
-        with torch.cuda.device(gm.device):
-            _lib.check(_lib.load().exo_sparse_model_merge_vjp_f64(_ptr(sp._ws), nbytes, N, D, P, sp.flags & FLAG_SECONDARY,
-                                                                  _ptr(ctx.mws), mbytes, _ptr(gm), _ptr(gvals), _stream(gm)),
-                       "exo_sparse_model_merge_vjp_f64")
+        _call("exo_sparse_model_merge_vjp_f64", gm.device, _ptr(sp._ws), nbytes, N, D, P, sp.flags & FLAG_SECONDARY,
+              _ptr(ctx.mws), mbytes, _ptr(gm), _ptr(gvals), _stream(gm))
         return gvals, None, None
 
 
@@ -1082,25 +1061,15 @@ class MergedSparseLightCurve(SparseLightCurve):
     def merged(self):
         return self
 
-    def _merge_layout(self):
-        import ctypes
-
-        lay = (ctypes.c_int64 * 5)()
-        _lib.check(_lib.load().exo_sparse_merge_layout(self.n_cad, self.n_draw, self.n_planet, lay), "exo_sparse_merge_layout")
-        return list(lay)
-
     def model_struct(self):
-        import ctypes
-
         m = _lib.SparseModel()
-        nbytes = _lib.load().exo_sparse_merge_workspace_bytes(self.n_cad, self.n_draw, self.n_planet)
-        _lib.check(_lib.load().exo_sparse_model_merged(_ptr(self._ws), nbytes, self.n_cad, self.n_draw, self.n_planet,
-                                                       ctypes.addressof(m)), "exo_sparse_model_merged")
+        _call("exo_sparse_model_merged", None, _ptr(self._ws), _merge_bytes(self.n_cad, self.n_draw, self.n_planet), self.n_cad,
+              self.n_draw, self.n_planet, ctypes.addressof(m))
         return m
 
     def segments(self):
         """(nseg (D,), seg (D, cap, 2), off (D, cap + 1)) int32 views of the merge workspace"""
-        o_nseg, o_seg, o_off, _, cap = self._merge_layout()
+        o_nseg, o_seg, o_off, _, cap = _merge_layout(self.n_cad, self.n_draw, self.n_planet)
         raw = self._ws.view(torch.int32)
         D = self.n_draw
         nseg = raw[o_nseg // 4: o_nseg // 4 + D]
@@ -1111,50 +1080,23 @@ class MergedSparseLightCurve(SparseLightCurve):
     def layout(self):
         raise NotImplementedError("a merged light curve has segments(), not the sweep's per-list runs")
 
+    _lists_overlap = False      # (disjoint segments: _SparseToDense)
+
+    def _values_per_draw(self):
+        return self.n_cad
+
     def _indices(self):
         nseg, seg, off = self.segments()
         D, N = self.n_draw, self.n_cad
-        dev = self.values.device
         K = int(nseg.max().item()) if nseg.numel() else 0
         if K == 0:
-            z = torch.zeros(0, dtype=torch.long, device=dev)
+            z = torch.zeros(0, dtype=torch.long, device=self.values.device)
             return z, z, z
-        lo, hi = seg[:, :K, 0].long(), seg[:, :K, 1].long()
-        live = torch.arange(K, device=dev) < nseg.long().unsqueeze(-1)
-        ln = torch.where(live, hi - lo, torch.zeros_like(lo))
-        flat_len = ln.reshape(-1)
-        total = int(flat_len.sum().item())
-        rid = torch.repeat_interleave(torch.arange(flat_len.numel(), device=dev), flat_len, output_size=total)
-        start = torch.cumsum(flat_len, 0) - flat_len
-        within = torch.arange(total, device=dev) - start[rid]
-        d_i = torch.arange(D, device=dev).view(D, 1).expand(D, K).reshape(-1)[rid]
-        idx_val = d_i * N + off[:, :K].long().reshape(-1)[rid] + within
-        idx_cad = lo.reshape(-1)[rid] + within
-        return idx_val, idx_cad, d_i
-
-    def dense(self):
-        return _MergedToDense.apply(self.values, self)
+        d_i = torch.arange(D, device=self.values.device).view(D, 1)
+        return _expand_runs(seg[:, :K, 0].long(), seg[:, :K, 1].long(), nseg.long(), d_i * N + off[:, :K].long(), d_i)
 
     def detach(self):
         return MergedSparseLightCurve(self.values.detach(), self._ws, self.n_cad, self.n_draw, self.n_planet, self.flags)
-
-
-class _MergedToDense(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, vals, sp):
-        idx_val, idx_cad, idx_draw = sp._indices()
-        out = torch.zeros(sp.n_draw, sp.n_cad, dtype=torch.float64, device=vals.device)
-        out[idx_draw, idx_cad] = vals.reshape(-1)[idx_val]
-        ctx.sp = sp
-        return out
-
-    @staticmethod
-    def backward(ctx, gout):
-        sp = ctx.sp
-        idx_val, idx_cad, idx_draw = sp._indices()
-        g = torch.zeros(sp.n_draw, sp.n_cad, dtype=torch.float64, device=gout.device)
-        g.view(-1)[idx_val] = gout[idx_draw, idx_cad]
-        return g, None
 
 
 def transit_flux_sparse_model(t, params, ld, texp=None, stencil_dt=None, stencil_w=None, flags=0):
@@ -1183,16 +1125,13 @@ class KeptDenseFlux:
         self.texp, self.stencil = texp, (stencil_dt, stencil_w)
         self.flags = int(flags)
         self.D, self.P, self.N = int(n_draw), int(n_planet), self.t.numel()
-        self._nbytes = _lib.load().exo_transit_flux_workspace_bytes(self.N, self.D, self.P)
         # zeroed: a workspace without runs (the first step has nothing to clear), a flux array without a transit
-        self._ws = torch.zeros(max(self._nbytes // 8 + 1, 1), dtype=torch.float64, device=self.t.device)
+        self._ws, self._nbytes = _workspace(self.N, self.D, self.P, self.t.device, zero=True)
         self.flux = torch.zeros(self.D, self.N, dtype=torch.float64, device=self.t.device)
 
     def _scatter(self, clear):
-        with torch.cuda.device(self.t.device):
-            _lib.check(_lib.load().exo_transit_sparse_scatter_f64(_ptr(self._ws), self._nbytes, self.N, self.D, self.P,
-                                                                  self.flags & FLAG_SECONDARY, 1 if clear else 0, _ptr(self.flux),
-                                                                  _stream(self.t)), "exo_transit_sparse_scatter_f64")
+        _call("exo_transit_sparse_scatter_f64", self.t.device, _ptr(self._ws), self._nbytes, self.N, self.D, self.P,
+              self.flags & FLAG_SECONDARY, 1 if clear else 0, _ptr(self.flux), _stream(self.t))
 
     @torch.no_grad()
     def step(self, params, ld, gflux=None):
@@ -1214,8 +1153,6 @@ class _TtvTables(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, period, t0, n_draw, *ttvs):
-        import ctypes
-
         period, t0 = _dev(period.detach(), "period"), _dev(t0.detach(), "t0")
         ttvs = [_dev(x.detach(), "ttvs") for x in ttvs]
         P, D = len(ttvs), int(n_draw)
@@ -1223,10 +1160,8 @@ class _TtvTables(torch.autograd.Function):
         n_edge = max(counts) + 1
         edges = torch.empty(D, P, n_edge, dtype=torch.float64, device=period.device)
         shift = torch.empty(D, P, n_edge + 1, dtype=torch.float64, device=period.device)
-        args = _TtvTables._args(period, t0, ttvs, counts)
-        lib = _lib.load()
-        with torch.cuda.device(period.device):
-            _lib.check(lib.exo_ttv_tables_f64(*args, D, P, n_edge, _ptr(edges), _ptr(shift), _stream(period)), "exo_ttv_tables_f64")
+        _call("exo_ttv_tables_f64", period.device, *_TtvTables._args(period, t0, ttvs, counts), D, P, n_edge, _ptr(edges),
+              _ptr(shift), _stream(period))
         ctx.save_for_backward(period, t0, *ttvs)
         ctx.meta = (D, P, n_edge, counts)
         ctx.mark_non_differentiable(edges)
@@ -1234,21 +1169,17 @@ class _TtvTables(torch.autograd.Function):
 
     @staticmethod
     def _args(period, t0, ttvs, counts):
-        import ctypes
-
         def strides(x):      # (rows, P) -> element strides of (draw, planet); one row: broadcast over draws
             return (x.stride(0) if x.shape[0] > 1 else 0, x.stride(1) if x.shape[1] > 1 else 0)
 
         P = len(ttvs)
-        tp = (ctypes.c_void_p * P)(*[x.data_ptr() for x in ttvs])
+        tp = _ptr_array(ttvs, P)
         td = (ctypes.c_int64 * P)(*[(x.stride(0) if x.shape[0] > 1 else 0) for x in ttvs])
         tn = (ctypes.c_int32 * P)(*counts)
         return (_ptr(period), *strides(period), _ptr(t0), *strides(t0), tp, td, tn)
 
     @staticmethod
     def backward(ctx, _gedges, gshift):
-        import ctypes
-
         period, t0, *ttvs = ctx.saved_tensors
         D, P, n_edge, counts = ctx.meta
         if gshift is None:
@@ -1258,11 +1189,8 @@ class _TtvTables(torch.autograd.Function):
         gper = torch.empty(D, P, dtype=torch.float64, device=gshift.device) if need_p else None
         gt = [torch.empty(D, n, dtype=torch.float64, device=gshift.device) if ctx.needs_input_grad[3 + p] else None
               for p, n in enumerate(counts)]
-        gp = (ctypes.c_void_p * P)(*[_ptr(x) for x in gt])
-        lib = _lib.load()
-        with torch.cuda.device(gshift.device):
-            _lib.check(lib.exo_ttv_tables_vjp_f64(*_TtvTables._args(period, t0, ttvs, counts), D, P, n_edge, _ptr(gshift), gp,
-                                                  _ptr(gper), _stream(gshift)), "exo_ttv_tables_vjp_f64")
+        _call("exo_ttv_tables_vjp_f64", gshift.device, *_TtvTables._args(period, t0, ttvs, counts), D, P, n_edge, _ptr(gshift),
+              _ptr_array(gt, P), _ptr(gper), _stream(gshift))
         if gper is not None:
             gper = gper.sum_to_size(period.shape)
         gt = [None if g is None else g.sum_to_size(x.shape) for g, x in zip(gt, ttvs)]
@@ -1297,10 +1225,7 @@ class _RadialVelocity(torch.autograd.Function):
             raise ValueError(f"params must be (n_draw, n_planet, {RV_NPAR})")
         D, P, _ = params.shape
         rv = torch.empty(D, t.numel(), P, dtype=torch.float64, device=t.device)
-        lib = _lib.load()
-        with torch.cuda.device(t.device):
-            _lib.check(lib.exo_radial_velocity_fwd_f64(_ptr(t), t.numel(), _ptr(params), D, P, _ptr(rv), _stream(t)),
-                       "exo_radial_velocity_fwd_f64")
+        _call("exo_radial_velocity_fwd_f64", t.device, _ptr(t), t.numel(), _ptr(params), D, P, _ptr(rv), _stream(t))
         ctx.save_for_backward(t, params)
         return rv
 
@@ -1310,10 +1235,8 @@ class _RadialVelocity(torch.autograd.Function):
         D, P, _ = params.shape
         grv = _dev(grv, "grv")
         gparams = torch.empty_like(params)
-        lib = _lib.load()
-        with torch.cuda.device(t.device):
-            _lib.check(lib.exo_radial_velocity_vjp_f64(_ptr(t), t.numel(), _ptr(params), D, P, _ptr(grv),
-                                                       _ptr(gparams), _stream(t)), "exo_radial_velocity_vjp_f64")
+        _call("exo_radial_velocity_vjp_f64", t.device, _ptr(t), t.numel(), _ptr(params), D, P, _ptr(grv), _ptr(gparams),
+              _stream(t))
         return None, gparams
 
 
@@ -1328,10 +1251,7 @@ class _OrbitVector(torch.autograd.Function):
             raise ValueError(f"params must be (n_draw, n_planet, {OV_NPAR})")
         D, P, _ = params.shape
         out = torch.empty(D, t.numel(), P, 3, dtype=torch.float64, device=t.device)
-        lib = _lib.load()
-        with torch.cuda.device(t.device):
-            _lib.check(lib.exo_orbit_vector_fwd_f64(_ptr(t), t.numel(), _ptr(params), D, P, flags, _ptr(out), _stream(t)),
-                       "exo_orbit_vector_fwd_f64")
+        _call("exo_orbit_vector_fwd_f64", t.device, _ptr(t), t.numel(), _ptr(params), D, P, flags, _ptr(out), _stream(t))
         ctx.save_for_backward(t, params)
         ctx.flags = flags
         return out
@@ -1342,10 +1262,8 @@ class _OrbitVector(torch.autograd.Function):
         D, P, _ = params.shape
         gout = _dev(gout, "gout")
         gparams = torch.empty_like(params)
-        lib = _lib.load()
-        with torch.cuda.device(t.device):
-            _lib.check(lib.exo_orbit_vector_vjp_f64(_ptr(t), t.numel(), _ptr(params), D, P, ctx.flags, _ptr(gout),
-                                                    _ptr(gparams), _stream(t)), "exo_orbit_vector_vjp_f64")
+        _call("exo_orbit_vector_vjp_f64", t.device, _ptr(t), t.numel(), _ptr(params), D, P, ctx.flags, _ptr(gout),
+              _ptr(gparams), _stream(t))
         return None, gparams, None
 
 
@@ -1381,10 +1299,8 @@ class _PackRecords(torch.autograd.Function):
             raise ValueError(f"ld_in must be (n_draw, {2 * nset})")
         params = torch.empty(D, P, NPAR, dtype=torch.float64, device=orbit_in.device)
         ld = torch.empty(D, 3 * nset, dtype=torch.float64, device=orbit_in.device)
-        lib = _lib.load()
-        with torch.cuda.device(orbit_in.device):
-            _lib.check(lib.exo_pack_records_f64(_ptr(orbit_in), _ptr(ld_in), D, P, flags, _ptr(params), _ptr(ld),
-                                                _stream(orbit_in)), "exo_pack_records_f64")
+        _call("exo_pack_records_f64", orbit_in.device, _ptr(orbit_in), _ptr(ld_in), D, P, flags, _ptr(params), _ptr(ld),
+              _stream(orbit_in))
         ctx.save_for_backward(orbit_in, ld_in)
         ctx.flags = flags
         return params, ld
@@ -1397,11 +1313,8 @@ class _PackRecords(torch.autograd.Function):
         gld = _dev(gld, "gld")
         go = torch.empty_like(orbit_in)
         gl = torch.empty_like(ld_in)
-        lib = _lib.load()
-        with torch.cuda.device(orbit_in.device):
-            _lib.check(lib.exo_pack_records_vjp_f64(_ptr(orbit_in), _ptr(ld_in), D, P, ctx.flags, _ptr(gparams),
-                                                    _ptr(gld), _ptr(go), _ptr(gl), _stream(orbit_in)),
-                       "exo_pack_records_vjp_f64")
+        _call("exo_pack_records_vjp_f64", orbit_in.device, _ptr(orbit_in), _ptr(ld_in), D, P, ctx.flags, _ptr(gparams),
+              _ptr(gld), _ptr(go), _ptr(gl), _stream(orbit_in))
         return go, gl, None
 
 
@@ -1417,10 +1330,8 @@ class _ShoCoefficients(torch.autograd.Function):
         n = amp.numel()
         coef = torch.empty(n, 4, dtype=torch.float64, device=amp.device)
         kind = torch.empty(n, dtype=torch.int32, device=amp.device)
-        lib = _lib.load()
-        with torch.cuda.device(amp.device):
-            _lib.check(lib.exo_sho_coefficients_f64(_ptr(amp), _ptr(freq), _ptr(damp), flags, eps, n, _ptr(coef), _ptr(kind),
-                                                    _stream(amp)), "exo_sho_coefficients_f64")
+        _call("exo_sho_coefficients_f64", amp.device, _ptr(amp), _ptr(freq), _ptr(damp), flags, eps, n, _ptr(coef), _ptr(kind),
+              _stream(amp))
         ctx.save_for_backward(amp, freq, damp)
         ctx.flags, ctx.eps = flags, eps
         ctx.mark_non_differentiable(kind)
@@ -1435,11 +1346,8 @@ class _ShoCoefficients(torch.autograd.Function):
             return None, None, None, None, None
         gcoef = _dev(gcoef, "gcoef").contiguous()
         ga, gf, gd = (torch.empty_like(amp) for _ in range(3))
-        lib = _lib.load()
-        with torch.cuda.device(amp.device):
-            _lib.check(lib.exo_sho_coefficients_vjp_f64(_ptr(amp), _ptr(freq), _ptr(damp), ctx.flags, ctx.eps, n, _ptr(gcoef),
-                                                        _ptr(ga), _ptr(gf), _ptr(gd), _stream(amp)),
-                       "exo_sho_coefficients_vjp_f64")
+        _call("exo_sho_coefficients_vjp_f64", amp.device, _ptr(amp), _ptr(freq), _ptr(damp), ctx.flags, ctx.eps, n,
+              _ptr(gcoef), _ptr(ga), _ptr(gf), _ptr(gd), _stream(amp))
         return ga, gf, gd, None, None
 
 
@@ -1459,8 +1367,6 @@ class _ShoCoefficientsMulti(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, flags, eps, *cols):
-        import ctypes
-
         T = len(flags)
         cols = [_dev(x, "SHO parameter").contiguous() for x in cols]
         n = cols[0].numel()
@@ -1468,12 +1374,10 @@ class _ShoCoefficientsMulti(torch.autograd.Function):
             raise ValueError("three 1-D tensors of one length per term, at most %d terms" % SHO_MAX_TERMS)
         coef = torch.empty(n, T, 4, dtype=torch.float64, device=cols[0].device)
         kind = torch.empty(n, T, dtype=torch.int32, device=cols[0].device)
-        vp = ctypes.c_void_p
-        arr = lambda q: (vp * T)(*[cols[3 * k + q].data_ptr() for k in range(T)])  # noqa: E731
+        arr = lambda q: _ptr_array(cols[q::3], T)  # noqa: E731
         fl = (ctypes.c_uint32 * T)(*[int(f) for f in flags])
-        with torch.cuda.device(coef.device):
-            _lib.check(_lib.load().exo_sho_coefficients_multi_f64(arr(0), arr(1), arr(2), fl, T, eps, n, _ptr(coef), _ptr(kind),
-                                                                  _stream(coef)), "exo_sho_coefficients_multi_f64")
+        _call("exo_sho_coefficients_multi_f64", coef.device, arr(0), arr(1), arr(2), fl, T, eps, n, _ptr(coef), _ptr(kind),
+              _stream(coef))
         ctx.save_for_backward(*cols)
         ctx.flags, ctx.eps = tuple(int(f) for f in flags), eps
         ctx.mark_non_differentiable(kind)
@@ -1482,8 +1386,6 @@ class _ShoCoefficientsMulti(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gcoef, _gkind):
-        import ctypes
-
         cols = ctx.saved_tensors
         T = len(ctx.flags)
         if gcoef is None:
@@ -1491,13 +1393,10 @@ class _ShoCoefficientsMulti(torch.autograd.Function):
         n = cols[0].numel()
         gcoef = _dev(gcoef, "gcoef").contiguous()
         grads = [torch.empty_like(c) for c in cols]
-        vp = ctypes.c_void_p
-        arr = lambda xs, q: (vp * T)(*[xs[3 * k + q].data_ptr() for k in range(T)])  # noqa: E731
+        arr = lambda xs, q: _ptr_array(xs[q::3], T)  # noqa: E731
         fl = (ctypes.c_uint32 * T)(*ctx.flags)
-        with torch.cuda.device(gcoef.device):
-            _lib.check(_lib.load().exo_sho_coefficients_multi_vjp_f64(arr(cols, 0), arr(cols, 1), arr(cols, 2), fl, T, ctx.eps, n,
-                                                                      _ptr(gcoef), arr(grads, 0), arr(grads, 1), arr(grads, 2),
-                                                                      _stream(gcoef)), "exo_sho_coefficients_multi_vjp_f64")
+        _call("exo_sho_coefficients_multi_vjp_f64", gcoef.device, arr(cols, 0), arr(cols, 1), arr(cols, 2), fl, T, ctx.eps, n,
+              _ptr(gcoef), arr(grads, 0), arr(grads, 1), arr(grads, 2), _stream(gcoef))
         return (None, None) + tuple(grads)
 
 
@@ -1508,240 +1407,103 @@ def sho_coefficients_multi(terms, eps=1e-5):
     return _ShoCoefficientsMulti.apply(tuple(int(f) for *_, f in terms), float(eps), *flat)
 
 
+_PACK_DEFAULTS = (float("nan"), 0.0, 0.0, 0.0, 0.0, float("nan"), 1.0, 1.0, 0.0, 0.0)   # EXO_IN_* order; period, r: required
+
+
 def _cols_vjp(t, texp, stencil_dt, stencil_w, host, D, P, nset, flags, pack_flags, gflux, events=(None, None), fold=None):
     """exo_transit_flux_cols_vjp_f64: the constructor's columns (``host`` = the six host arrays of _cols_host) -> records, the
     value + VJP sweep and, ``fold = (gscale | None, gcols, gld_cols)`` (host arrays of output pointers), the packing VJP in
     the same call.  Returns (flux | SparseFlux, gparams, gld, dot)."""
-    cp, ds, ps, df, lp, ls = host
     t = _dev(t, "t")
-    N = t.numel()
+    N, dev = t.numel(), t.device
     if t.dim() != 1:
         raise ValueError("t must be 1-D (n_cad,)")
-    if texp is None:
-        n_texp, n_sub, sdt, sw = 0, 1, None, None
-    else:
-        texp = _dev(texp, "texp").reshape(-1)
-        sdt, sw = _dev(stencil_dt, "stencil_dt"), _dev(stencil_w, "stencil_w")
-        n_texp, n_sub = texp.numel(), sdt.numel()
-        if n_texp not in (1, N) or sw.numel() != n_sub or not 1 <= n_sub <= MAX_SUBEXP:
-            raise ValueError("texp: a scalar or one entry per cadence; stencil: 1..%d points" % MAX_SUBEXP)
+    texp, n_texp, sdt, sw, n_sub = _exposure_args(t, texp, stencil_dt, stencil_w)
     if not 1 <= P <= MAX_PLANETS:
         raise ValueError(f"1 <= n_planet <= {MAX_PLANETS}")
     flags = int(flags) | _sorted_flag(t)
-    shape = (D, N, P) if flags & FLAG_PER_PLANET else (D, N)
+    shape = _flux_shape(N, D, P, flags)
     if isinstance(gflux, torch.Tensor) and tuple(gflux.shape) != shape:
         raise ValueError(f"gflux must have shape {shape}")
-    cm_sweep = n_texp <= 1 and not flags & (FLAG_EXACT_SCAN | FLAG_PER_PLANET)
-    if is_cadence_major(gflux) and cm_sweep:
-        flags |= FLAG_CADENCE_MAJOR
-    elif flags & FLAG_CADENCE_MAJOR and cm_sweep:
-        gflux = _dev(gflux, "gflux").t().contiguous().t()
-    else:
-        flags &= ~FLAG_CADENCE_MAJOR
-        gflux = _dev(gflux, "gflux")
-    dev = t.device
-    lib = _lib.load()
-    nbytes = lib.exo_transit_flux_workspace_bytes(N, D, P)
-    ws = torch.empty(max(nbytes // 8 + 1, 1), dtype=torch.float64, device=dev)
+    gflux, flags = _cotangent_layout(gflux, flags, n_texp <= 1 and not flags & (FLAG_EXACT_SCAN | FLAG_PER_PLANET), True)
+    ws, nbytes = _workspace(N, D, P, dev)
     params = torch.empty(D, P, NPAR, dtype=torch.float64, device=dev)
     ld = torch.empty(D, 3 * nset, dtype=torch.float64, device=dev)
     gparams, gld = torch.empty_like(params), torch.empty_like(ld)
     dot = torch.empty(D, dtype=torch.float64, device=dev)
-    flux = None
-    if not flags & FLAG_SPARSE:
-        flux = (torch.empty((N, D), dtype=torch.float64, device=dev).t() if flags & FLAG_CADENCE_MAJOR
-                else torch.empty(shape, dtype=torch.float64, device=dev))
+    flux = None if flags & FLAG_SPARSE else _flux_out(N, D, P, flags, dev)
     gscale, gcp, glp = (None, None, None) if fold is None else fold
-    with torch.cuda.device(dev):
-        _lib.check(lib.exo_transit_flux_cols_vjp_f64(cp, ds, ps, df, lp, ls, int(pack_flags), _ptr(t), N, _ptr(texp), n_texp,
-                                                     _ptr(sdt), _ptr(sw), n_sub, D, P, flags, _ptr(gflux), _ptr(flux),
-                                                     _ptr(params), _ptr(ld), _ptr(gparams), _ptr(gld), _ptr(dot),
-                                                     0 if fold is None else 1, _ptr(gscale), gcp, glp, _ptr(ws), nbytes,
-                                                     _stream(t), events[0], events[1]), "exo_transit_flux_cols_vjp_f64")
+    _call("exo_transit_flux_cols_vjp_f64", dev, *host, int(pack_flags), _ptr(t), N, _ptr(texp), n_texp, _ptr(sdt), _ptr(sw),
+          n_sub, D, P, flags, _ptr(gflux), _ptr(flux), _ptr(params), _ptr(ld), _ptr(gparams), _ptr(gld), _ptr(dot),
+          0 if fold is None else 1, _ptr(gscale), gcp, glp, _ptr(ws), nbytes, _stream(t), events[0], events[1])
     if flags & FLAG_SPARSE:
         flux = _sparse_from_ws(ws, N, D, P, flags)
     return flux, gparams, gld, dot
 
 
-def _cols_host(ocols, lcols, D, P):
-    """the host arrays exo_pack_records_cols_f64 / exo_transit_flux_cols_vjp_f64 take for a list of NIN orbit columns (None = the
-    constructor's default) and the limb-darkening columns, + the expanded views (kept alive by the caller)"""
-    import ctypes
-
-    vp, i64 = ctypes.c_void_p, ctypes.c_int64
-    cp, ds, ps, df = (vp * NIN)(), (i64 * NIN)(), (i64 * NIN)(), (ctypes.c_double * NIN)(*_PACK_DEFAULTS)
-    keep = []
-    for k, c in enumerate(ocols):
-        if c is None:
-            continue
-        c = _dev(c.detach(), "orbit parameter")
-        v = c.reshape(1, 1) if c.dim() == 0 else (c.unsqueeze(0) if c.dim() == 1 else c)
-        v = v.expand(D, P)
-        keep.append(v)
-        cp[k], ds[k], ps[k] = v.data_ptr(), v.stride(0), v.stride(1)
-    lp, ls = (vp * 4)(), (i64 * 4)()
-    for k, c in enumerate(lcols):
-        c = _dev(c.detach(), "limb-darkening coefficient")
-        v = (c.reshape(1) if c.dim() == 0 else c).expand(D)
-        keep.append(v)
-        lp[k], ls[k] = v.data_ptr(), v.stride(0)
-    return (cp, ds, ps, df, lp, ls), keep
-
-
-@torch.no_grad()
-def orbit_flux_value_and_grad(t, gflux, orbit_cols, ld_cols, flags=0, pack_flags=0, texp=None, stencil_dt=None, stencil_w=None,
-                              gscale=None, events=(None, None), wanted=None):
-    """Value AND gradient of ``L[d] = sum_n gflux[d, n] flux[d, n]`` for orbits in the standard parameterisation given column
-    by column (as :func:`orbit_flux_dot`), WITHOUT autograd: returns ``(flux, L, gcols, gld_cols)`` -- ``gcols[k]`` the
-    gradient of ``sum_d gscale[d] L[d]`` (``gscale`` None: of ``sum_d L[d]``) with respect to orbit column k in that
-    column's own shape (None where the column was None), ``gld_cols`` likewise for (u1, u2[, u1s, u2s]).  What a sampler's
-    leapfrog step needs, in ONE call of the library (exo_transit_flux_cols_vjp_f64): the packing rides on the windows +
-    enumeration launch, then the sweep, then the packing VJP -- three launches at >= 512 draws, no autograd graph.
-    ``wanted``: one bool per orbit column -- False: no gradient for it (None in ``gcols``)."""
-    import ctypes
-
-    ocols, lcols = list(orbit_cols), list(ld_cols)
-    if len(ocols) != NIN or len(lcols) not in (2, 4):
-        raise ValueError(f"{NIN} orbit columns (None = default) and 2 or 4 limb-darkening columns")
-    D = P = 1
+def _cols_batch(ocols, lcols, n_draw=None):
+    """(D, P) of a set of columns: what their shapes imply, or -- ``n_draw`` -- the caller's D and the planets of the orbit
+    columns"""
+    D, P = (1, 1) if n_draw is None else (int(n_draw), 1)
     for c in ocols:
         if c is not None:
             if c.dim() > 2:
                 raise ValueError("orbit parameters may carry at most one draw dimension here")
             P = max(P, c.shape[-1] if c.dim() >= 1 else 1)
-            D = max(D, c.shape[0] if c.dim() == 2 else 1)
-    for c in lcols:
-        if c.dim() > 1:
-            raise ValueError("limb-darkening coefficients may carry at most one draw dimension")
-        D = max(D, c.shape[0] if c.dim() == 1 else 1)
-    host, keep = _cols_host(ocols, lcols, D, P)
-    dev = keep[0].device
-    vp = ctypes.c_void_p
-    gcp, glp = (vp * NIN)(), (vp * 4)()
-    wanted = [True] * NIN if wanted is None else list(wanted)
-    outs = [None if (c is None or not w) else torch.empty(D, P, dtype=torch.float64, device=dev) for c, w in zip(ocols, wanted)]
-    louts = [torch.empty(D, dtype=torch.float64, device=dev) for _ in lcols]
-    for k, o in enumerate(outs):
-        if o is not None:
-            gcp[k] = o.data_ptr()
-    for k, o in enumerate(louts):
-        glp[k] = o.data_ptr()
-    if gscale is not None:
-        gscale = _dev(gscale, "gscale")
-        if tuple(gscale.shape) != (D,):
-            raise ValueError("gscale: one factor per draw")
-    flux, _, _, dot = _cols_vjp(t, texp, stencil_dt, stencil_w, host, D, P, len(lcols) // 2, flags, pack_flags, gflux, events,
-                                fold=(gscale, gcp, glp))
-
-    def back(g, c):       # dense (D, P) / (D,) cotangents back to the column's own shape (sums over what was broadcast)
-        if g is None:
-            return None
-        shp = tuple(c.shape)
-        return g.reshape(shp) if g.numel() == _numel(shp) else g.sum_to_size(_bshape(shp, g.dim())).reshape(shp)
-
-    return flux, dot, [back(g, c) for g, c in zip(outs, ocols)], [back(g, c) for g, c in zip(louts, lcols)]
-
-
-class _OrbitFluxDot(torch.autograd.Function):
-    """Record packing (column form: every constructor argument its own tensor), the one-sweep value + VJP light
-    curve, and -- backward -- the packing VJP with the cotangent of L folded in (``gscale``): the whole
-    user-level step of a standard-parameterisation orbit is the sweep plus TWO small kernels, where the
-    composition pack_records -> transit_flux_dot costs seven (two concatenations, the pack, two scalings of
-    the saved cotangents, the pack VJP, and whatever produced the cotangent of L)."""
-
-    @staticmethod
-    def forward(ctx, t, gflux, texp, stencil_dt, stencil_w, flags, pack_flags, events, n_ld, *cols):
-        import ctypes
-
-        t = _dev(t, "t")
-        ocols, lcols = list(cols[:NIN]), list(cols[NIN:NIN + n_ld])
-        D = P = 1
-        for c in ocols:
-            if c is not None:
-                if c.dim() > 2:
-                    raise ValueError("orbit parameters may carry at most one draw dimension here")
-                P = max(P, c.shape[-1] if c.dim() >= 1 else 1)
+            if n_draw is None:
                 D = max(D, c.shape[0] if c.dim() == 2 else 1)
+    if n_draw is None:
         for c in lcols:
             if c.dim() > 1:
                 raise ValueError("limb-darkening coefficients may carry at most one draw dimension")
             D = max(D, c.shape[0] if c.dim() == 1 else 1)
-        vp, i64 = ctypes.c_void_p, ctypes.c_int64
-        cp, ds, ps, df = (vp * NIN)(), (i64 * NIN)(), (i64 * NIN)(), (ctypes.c_double * NIN)(*_PACK_DEFAULTS)
-        keep = []
-        for k, c in enumerate(ocols):
-            if c is None:
-                continue
-            c = _dev(c.detach(), "orbit parameter")
-            v = c.reshape(1, 1) if c.dim() == 0 else (c.unsqueeze(0) if c.dim() == 1 else c)
-            v = v.expand(D, P)
-            keep.append(v)
-            cp[k], ds[k], ps[k] = v.data_ptr(), v.stride(0), v.stride(1)
-        lp, ls = (vp * 4)(), (i64 * 4)()
-        for k, c in enumerate(lcols):
-            c = _dev(c.detach(), "limb-darkening coefficient")
-            v = (c.reshape(1) if c.dim() == 0 else c).expand(D)
-            keep.append(v)
-            lp[k], ls[k] = v.data_ptr(), v.stride(0)
-        nset = n_ld // 2
-        # (packing, windows + enumeration in ONE launch, then the sweep: exo_transit_flux_cols_vjp_f64; the packing VJP stays in
-        # backward() -- the cotangent of L is not known before)
-        flux, gparams, gld, dot = _cols_vjp(t, texp, stencil_dt, stencil_w, (cp, ds, ps, df, lp, ls), D, P, nset, flags,
-                                            pack_flags, gflux, events)
-        ctx.save_for_backward(gparams, gld, *keep)
-        ctx.meta = (D, P, pack_flags, n_ld, [c is not None for c in ocols], [None if c is None else tuple(c.shape) for c in cols])
-        ctx.set_materialize_grads(False)
-        if isinstance(flux, SparseFlux):
-            shape = torch.tensor([D, P], dtype=torch.int64)      # (host tensor: the wrapper needs the batch the columns implied)
-            ctx.mark_non_differentiable(flux._ws, shape)
-            return flux._ws, dot, shape
-        ctx.mark_non_differentiable(flux)
-        return flux, dot
+    return D, P
 
-    @staticmethod
-    def backward(ctx, _gflux_unused, gdot, *_shape_unused):
-        import ctypes
 
-        D, P, pack_flags, n_ld, present, shapes = ctx.meta
-        nfix = 9
-        if gdot is None:
-            return (None,) * (nfix + len(shapes))
-        gparams, gld, *keep = ctx.saved_tensors
-        vp, i64 = ctypes.c_void_p, ctypes.c_int64
-        cp, ds, ps, df = (vp * NIN)(), (i64 * NIN)(), (i64 * NIN)(), (ctypes.c_double * NIN)(*_PACK_DEFAULTS)
-        it = iter(keep)
-        for k in range(NIN):
-            if present[k]:
-                v = next(it)
-                cp[k], ds[k], ps[k] = v.data_ptr(), v.stride(0), v.stride(1)
-        lp, ls = (vp * 4)(), (i64 * 4)()
-        for k in range(n_ld):
+def _cols_host(ocols, lcols, D, P):
+    """the host arrays exo_pack_records_cols_f64 / exo_transit_flux_cols_vjp_f64 take for a list of NIN orbit columns (None = the
+    constructor's default) and the limb-darkening columns, + the expanded views (kept alive by the caller)"""
+    keep = []
+    for c in ocols:
+        if c is None:
+            continue
+        c = _dev(c.detach(), "orbit parameter")
+        v = c.reshape(1, 1) if c.dim() == 0 else (c.unsqueeze(0) if c.dim() == 1 else c)
+        keep.append(v.expand(D, P))
+    for c in lcols:
+        c = _dev(c.detach(), "limb-darkening coefficient")
+        keep.append((c.reshape(1) if c.dim() == 0 else c).expand(D))
+    return _cols_host_saved(keep, [c is not None for c in ocols], len(lcols)), keep
+
+
+def _cols_host_saved(keep, present, n_ld):
+    """the six host arrays from the expanded views of _cols_host (``present[k]``: orbit column k was given): also what the
+    reverse pass rebuilds them with"""
+    vp, i64 = ctypes.c_void_p, ctypes.c_int64
+    cp, ds, ps, df = (vp * NIN)(), (i64 * NIN)(), (i64 * NIN)(), (ctypes.c_double * NIN)(*_PACK_DEFAULTS)
+    lp, ls = (vp * 4)(), (i64 * 4)()
+    it = iter(keep)
+    for k in range(NIN):
+        if present[k]:
             v = next(it)
-            lp[k], ls[k] = v.data_ptr(), v.stride(0)
-        dev = gparams.device
-        gcp, glp = (vp * NIN)(), (vp * 4)()
-        outs = [None] * len(shapes)
-        for k in range(NIN):
-            if present[k] and ctx.needs_input_grad[nfix + k]:
-                outs[k] = torch.empty(D, P, dtype=torch.float64, device=dev)
-                gcp[k] = outs[k].data_ptr()
-        for k in range(n_ld):
-            if ctx.needs_input_grad[nfix + NIN + k]:
-                outs[NIN + k] = torch.empty(D, dtype=torch.float64, device=dev)
-                glp[k] = outs[NIN + k].data_ptr()
-        gdot = _dev(gdot, "gdot")
-        lib = _lib.load()
-        with torch.cuda.device(dev):
-            _lib.check(lib.exo_pack_records_cols_vjp_f64(cp, ds, ps, df, lp, ls, D, P, pack_flags, _ptr(gparams), _ptr(gld),
-                                                         _ptr(gdot), gcp, glp, _stream(gparams)),
-                       "exo_pack_records_cols_vjp_f64")
-        # dense (D, P) / (D,) cotangents back to the shapes the caller passed (sums over what was broadcast)
-        grads = [None if g is None else (g.reshape(shp) if g.numel() == _numel(shp) else g.sum_to_size(_bshape(shp, g.dim())).reshape(shp))
-                 for g, shp in zip(outs, shapes)]
-        return (None,) * nfix + tuple(grads)
+            cp[k], ds[k], ps[k] = v.data_ptr(), v.stride(0), v.stride(1)
+    for k in range(n_ld):
+        v = next(it)
+        lp[k], ls[k] = v.data_ptr(), v.stride(0)
+    return cp, ds, ps, df, lp, ls
 
 
-_PACK_DEFAULTS = (float("nan"), 0.0, 0.0, 0.0, 0.0, float("nan"), 1.0, 1.0, 0.0, 0.0)   # EXO_IN_* order; period, r: required
+def _cols_meta(D, P, pack_flags, n_ld, cols):
+    """what the reverse pass of a column-form packing needs besides the views: the batch, which orbit columns were given,
+    every column's own shape"""
+    return D, P, pack_flags, n_ld, [c is not None for c in cols[:NIN]], [None if c is None else tuple(c.shape) for c in cols]
+
+
+def _to_col_shape(g, shape):
+    """a dense (D, P) / (D,) cotangent back to the shape the caller passed (sums over what was broadcast)"""
+    if g is None:
+        return None
+    return g.reshape(shape) if g.numel() == _numel(shape) else g.sum_to_size(_bshape(shape, g.dim())).reshape(shape)
 
 
 def _numel(shape):
@@ -1754,6 +1516,72 @@ def _numel(shape):
 def _bshape(shape, ndim):
     """`shape` left-padded with ones to `ndim` dimensions (what sum_to_size reduces to)"""
     return (1,) * (ndim - len(shape)) + tuple(shape)
+
+
+@torch.no_grad()
+def orbit_flux_value_and_grad(t, gflux, orbit_cols, ld_cols, flags=0, pack_flags=0, texp=None, stencil_dt=None, stencil_w=None,
+                              gscale=None, events=(None, None), wanted=None):
+    """Value AND gradient of ``L[d] = sum_n gflux[d, n] flux[d, n]`` for orbits in the standard parameterisation given column
+    by column (as :func:`orbit_flux_dot`), WITHOUT autograd: returns ``(flux, L, gcols, gld_cols)`` -- ``gcols[k]`` the
+    gradient of ``sum_d gscale[d] L[d]`` (``gscale`` None: of ``sum_d L[d]``) with respect to orbit column k in that
+    column's own shape (None where the column was None), ``gld_cols`` likewise for (u1, u2[, u1s, u2s]).  What a sampler's
+    leapfrog step needs, in ONE call of the library (exo_transit_flux_cols_vjp_f64): the packing rides on the windows +
+    enumeration launch, then the sweep, then the packing VJP -- three launches at >= 512 draws, no autograd graph.
+    ``wanted``: one bool per orbit column -- False: no gradient for it (None in ``gcols``)."""
+    ocols, lcols = list(orbit_cols), list(ld_cols)
+    if len(ocols) != NIN or len(lcols) not in (2, 4):
+        raise ValueError(f"{NIN} orbit columns (None = default) and 2 or 4 limb-darkening columns")
+    D, P = _cols_batch(ocols, lcols)
+    host, keep = _cols_host(ocols, lcols, D, P)
+    dev = keep[0].device
+    wanted = [True] * NIN if wanted is None else list(wanted)
+    outs = [None if (c is None or not w) else torch.empty(D, P, dtype=torch.float64, device=dev) for c, w in zip(ocols, wanted)]
+    louts = [torch.empty(D, dtype=torch.float64, device=dev) for _ in lcols]
+    if gscale is not None:
+        gscale = _dev(gscale, "gscale")
+        if tuple(gscale.shape) != (D,):
+            raise ValueError("gscale: one factor per draw")
+    flux, _, _, dot = _cols_vjp(t, texp, stencil_dt, stencil_w, host, D, P, len(lcols) // 2, flags, pack_flags, gflux, events,
+                                fold=(gscale, _ptr_array(outs, NIN), _ptr_array(louts, 4)))
+    return (flux, dot, [None if g is None else _to_col_shape(g, tuple(c.shape)) for g, c in zip(outs, ocols)],
+            [_to_col_shape(g, tuple(c.shape)) for g, c in zip(louts, lcols)])
+
+
+class _OrbitFluxDot(torch.autograd.Function):
+    """Record packing (column form: every constructor argument its own tensor), the one-sweep value + VJP light
+    curve, and -- backward -- the packing VJP with the cotangent of L folded in (``gscale``): the whole
+    user-level step of a standard-parameterisation orbit is the sweep plus TWO small kernels, where the
+    composition pack_records -> transit_flux_dot costs seven (two concatenations, the pack, two scalings of
+    the saved cotangents, the pack VJP, and whatever produced the cotangent of L)."""
+
+    @staticmethod
+    def forward(ctx, t, gflux, texp, stencil_dt, stencil_w, flags, pack_flags, events, n_ld, *cols):
+        t = _dev(t, "t")
+        ocols, lcols = list(cols[:NIN]), list(cols[NIN:NIN + n_ld])
+        D, P = _cols_batch(ocols, lcols)
+        host, keep = _cols_host(ocols, lcols, D, P)
+        # (packing, windows + enumeration in ONE launch, then the sweep: exo_transit_flux_cols_vjp_f64; the packing VJP stays in
+        # backward() -- the cotangent of L is not known before)
+        flux, gparams, gld, dot = _cols_vjp(t, texp, stencil_dt, stencil_w, host, D, P, n_ld // 2, flags, pack_flags, gflux,
+                                            events)
+        ctx.save_for_backward(gparams, gld, *keep)
+        ctx.meta = _cols_meta(D, P, pack_flags, n_ld, cols)
+        ctx.set_materialize_grads(False)
+        if isinstance(flux, SparseFlux):
+            shape = torch.tensor([D, P], dtype=torch.int64)      # (host tensor: the wrapper needs the batch the columns implied)
+            ctx.mark_non_differentiable(flux._ws, shape)
+            return flux._ws, dot, shape
+        ctx.mark_non_differentiable(flux)
+        return flux, dot
+
+    @staticmethod
+    def backward(ctx, _gflux_unused, gdot, *_shape_unused):
+        nfix = 9
+        if gdot is None:
+            return (None,) * (nfix + len(ctx.meta[5]))
+        gparams, gld, *keep = ctx.saved_tensors
+        return (None,) * nfix + tuple(_pack_cols_backward(keep, ctx.meta, gparams, gld, _dev(gdot, "gdot"),
+                                                          ctx.needs_input_grad[nfix:]))
 
 
 def orbit_flux_dot(t, gflux, orbit_cols, ld_cols, flags=0, pack_flags=0, texp=None, stencil_dt=None, stencil_w=None,
@@ -1774,79 +1602,32 @@ def orbit_flux_dot(t, gflux, orbit_cols, ld_cols, flags=0, pack_flags=0, texp=No
 def _pack_cols_forward(cols, n_ld, n_draw, pack_flags):
     """exo_pack_records_cols_f64 on a list of NIN orbit columns (None = constructor default) + n_ld limb-darkening
     columns: (params (D, P, 20), ld (D, 3|6), the expanded views to keep for the reverse call, meta)"""
-    import ctypes
-
     ocols, lcols = list(cols[:NIN]), list(cols[NIN:NIN + n_ld])
     ref = next(c for c in ocols + lcols if c is not None)
-    D, P = int(n_draw), 1
-    for c in ocols:
-        if c is not None:
-            if c.dim() > 2:
-                raise ValueError("orbit parameters may carry at most one draw dimension here")
-            P = max(P, c.shape[-1] if c.dim() >= 1 else 1)
-    vp, i64 = ctypes.c_void_p, ctypes.c_int64
-    cp, ds, ps, df = (vp * NIN)(), (i64 * NIN)(), (i64 * NIN)(), (ctypes.c_double * NIN)(*_PACK_DEFAULTS)
-    keep = []
-    for k, c in enumerate(ocols):
-        if c is None:
-            continue
-        c = _dev(c.detach(), "orbit parameter")
-        v = c.reshape(1, 1) if c.dim() == 0 else (c.unsqueeze(0) if c.dim() == 1 else c)
-        v = v.expand(D, P)
-        keep.append(v)
-        cp[k], ds[k], ps[k] = v.data_ptr(), v.stride(0), v.stride(1)
-    lp, ls = (vp * 4)(), (i64 * 4)()
-    for k, c in enumerate(lcols):
-        c = _dev(c.detach(), "limb-darkening coefficient")
-        v = (c.reshape(1) if c.dim() == 0 else c).expand(D)
-        keep.append(v)
-        lp[k], ls[k] = v.data_ptr(), v.stride(0)
-    nset = n_ld // 2
+    D, P = _cols_batch(ocols, lcols, n_draw)
+    host, keep = _cols_host(ocols, lcols, D, P)
     params = torch.empty(D, P, NPAR, dtype=torch.float64, device=ref.device)
-    ld = torch.empty(D, 3 * nset, dtype=torch.float64, device=ref.device)
-    lib = _lib.load()
-    with torch.cuda.device(ref.device):
-        _lib.check(lib.exo_pack_records_cols_f64(cp, ds, ps, df, lp, ls, D, P, pack_flags, _ptr(params), _ptr(ld),
-                                                 _stream(params)), "exo_pack_records_cols_f64")
-    meta = (D, P, pack_flags, n_ld, [c is not None for c in ocols], [None if c is None else tuple(c.shape) for c in cols])
-    return params, ld, keep, meta
+    ld = torch.empty(D, 3 * (n_ld // 2), dtype=torch.float64, device=ref.device)
+    _call("exo_pack_records_cols_f64", ref.device, *host, D, P, pack_flags, _ptr(params), _ptr(ld), _stream(params))
+    return params, ld, keep, _cols_meta(D, P, pack_flags, n_ld, cols)
 
 
 def _pack_cols_backward(keep, meta, gparams, gld, gscale, needs):
     """exo_pack_records_cols_vjp_f64: cotangents of (params, ld), optionally scaled per draw by ``gscale``, back to the
     columns' own shapes; ``needs[k]``: whether column k wants one"""
-    import ctypes
-
     D, P, pack_flags, n_ld, present, shapes = meta
     dev = keep[0].device
-    vp, i64 = ctypes.c_void_p, ctypes.c_int64
-    cp, ds, ps, df = (vp * NIN)(), (i64 * NIN)(), (i64 * NIN)(), (ctypes.c_double * NIN)(*_PACK_DEFAULTS)
-    it = iter(keep)
-    for k in range(NIN):
-        if present[k]:
-            v = next(it)
-            cp[k], ds[k], ps[k] = v.data_ptr(), v.stride(0), v.stride(1)
-    lp, ls = (vp * 4)(), (i64 * 4)()
-    for k in range(n_ld):
-        v = next(it)
-        lp[k], ls[k] = v.data_ptr(), v.stride(0)
-    gcp, glp = (vp * NIN)(), (vp * 4)()
+    host = _cols_host_saved(keep, present, n_ld)
     outs = [None] * len(shapes)
     for k in range(NIN):
         if present[k] and needs[k]:
             outs[k] = torch.empty(D, P, dtype=torch.float64, device=dev)
-            gcp[k] = outs[k].data_ptr()
     for k in range(n_ld):
         if needs[NIN + k]:
             outs[NIN + k] = torch.empty(D, dtype=torch.float64, device=dev)
-            glp[k] = outs[NIN + k].data_ptr()
-    lib = _lib.load()
-    with torch.cuda.device(dev):
-        _lib.check(lib.exo_pack_records_cols_vjp_f64(cp, ds, ps, df, lp, ls, D, P, pack_flags, _ptr(gparams), _ptr(gld),
-                                                     _ptr(gscale), gcp, glp, _stream(gparams)), "exo_pack_records_cols_vjp_f64")
-    # dense (D, P) / (D,) cotangents back to the shapes the caller passed (sums over what was broadcast)
-    return [None if g is None else (g.reshape(shp) if g.numel() == _numel(shp) else g.sum_to_size(_bshape(shp, g.dim())).reshape(shp))
-            for g, shp in zip(outs, shapes)]
+    _call("exo_pack_records_cols_vjp_f64", dev, *host, D, P, pack_flags, _ptr(gparams), _ptr(gld), _ptr(gscale),
+          _ptr_array(outs[:NIN], NIN), _ptr_array(outs[NIN:NIN + n_ld], 4), _stream(gparams))
+    return [_to_col_shape(g, shp) for g, shp in zip(outs, shapes)]
 
 
 class _PackCols(torch.autograd.Function):
@@ -1881,31 +1662,11 @@ class _OrbitLoglike(torch.autograd.Function):
     def forward(ctx, t, texp, stencil_dt, stencil_w, obs, ivar, cterm, flags, pack_flags, n_ld, n_draw, ttv_edges, ttv_shift,
                 *cols):
         params, ld, keep, meta = _pack_cols_forward(cols, n_ld, n_draw, pack_flags)
-        t, texp, n_texp, sdt, sw, n_sub, params, ld, D, P = _transit_args(t, texp, stencil_dt, stencil_w, params, ld, flags)
-        flags |= _sorted_flag(t)
-        edges, shift, n_edge = _ttv_args(None if ttv_edges is None else (ttv_edges, ttv_shift), D, P)
-        N = t.numel()
-        lib = _lib.load()
-        nbytes = lib.exo_transit_flux_workspace_bytes(N, D, P)
-        ws = torch.empty(max(nbytes // 8 + 1, 1), dtype=torch.float64, device=t.device)
-        chi2 = torch.empty(D, dtype=torch.float64, device=t.device)
-        gparams, gld = torch.empty_like(params), torch.empty_like(ld)
-        gshift = torch.empty_like(shift) if n_edge else None
-        with torch.cuda.device(t.device):
-            if n_edge:
-                _lib.check(lib.exo_transit_chi2_ttv_vjp_f64(_ptr(t), N, _ptr(texp), n_texp, _ptr(sdt), _ptr(sw), n_sub,
-                                                            _ptr(params), _ptr(ld), D, P, flags, _ptr(edges), _ptr(shift),
-                                                            n_edge, _ptr(obs), _ptr(ivar), ivar.numel(), _ptr(chi2),
-                                                            _ptr(gparams), _ptr(gld), _ptr(gshift), _ptr(ws), nbytes,
-                                                            _stream(t)), "exo_transit_chi2_ttv_vjp_f64")
-            else:
-                _lib.check(lib.exo_transit_chi2_vjp_f64(_ptr(t), N, _ptr(texp), n_texp, _ptr(sdt), _ptr(sw), n_sub, _ptr(params),
-                                                        _ptr(ld), D, P, flags, _ptr(obs), _ptr(ivar), ivar.numel(), _ptr(chi2),
-                                                        _ptr(gparams), _ptr(gld), _ptr(ws), nbytes, _stream(t)),
-                           "exo_transit_chi2_vjp_f64")
+        a = _transit_args(t, texp, stencil_dt, stencil_w, params, ld, flags)
+        chi2, gparams, gld, gshift = _chi2_launch(a, flags, ttv_edges, ttv_shift, obs, ivar)
         ctx.meta = meta
         ctx.n_keep = len(keep)
-        ctx.save_for_backward(gparams, gld, *keep, *([gshift] if n_edge else []))
+        ctx.save_for_backward(gparams, gld, *keep, *([] if gshift is None else [gshift]))
         return torch.add(cterm, chi2, alpha=-0.5)
 
     @staticmethod
