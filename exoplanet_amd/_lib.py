@@ -10,7 +10,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # EXOPLANET_AMD_LIB selects another in-tree build of the same ABI (A/B measurements)
 LIB_PATH = os.environ.get("EXOPLANET_AMD_LIB") or os.path.join(_HERE, "lib", "libexoplanet_amd.so")
-ABI_VERSION = 16
+ABI_VERSION = 17
 
 _c_dp = ctypes.c_void_p  # device pointers travel as integers
 _i64 = ctypes.c_int64
@@ -174,6 +174,10 @@ _SIGNATURES = {
                                                  _c_dp]),
     "exo_pack_records_cols_vjp_f64": (ctypes.c_int, [_c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _i64, _i32, _u32, _c_dp,
                                                      _c_dp, _c_dp, _c_dp, _c_dp, _c_dp]),
+    # z, n_chain, n_free, table (host array of exo_prior_block), n_block, theta (host array of pointers), log_prior, stream
+    "exo_prior_transform_f64": (ctypes.c_int, [_c_dp, _i64, _i32, _c_dp, _i32, _c_dp, _c_dp, _c_dp]),
+    # ..., n_block, gtheta (host array of pointers, null: no cotangent), glog_prior, gz, stream
+    "exo_prior_transform_vjp_f64": (ctypes.c_int, [_c_dp, _i64, _i32, _c_dp, _i32, _c_dp, _c_dp, _c_dp, _c_dp]),
 }
 
 class SparseModel(ctypes.Structure):
@@ -181,6 +185,12 @@ class SparseModel(ctypes.Structure):
     _fields_ = [("nseg", ctypes.c_void_p), ("seg", ctypes.c_void_p), ("off", ctypes.c_void_p), ("vals", ctypes.c_void_p),
                 ("seg_row", _i64), ("off_row", _i64), ("val_row", _i64), ("seg_step", _i32), ("hi_at", _i32),
                 ("row_of_draw", ctypes.c_void_p)]
+
+
+class PriorBlock(ctypes.Structure):
+    """exo_prior_block of include/exoplanet_amd.h"""
+    _fields_ = [("kind", _i32), ("offset", _i32), ("count", _i32), ("link", _i32), ("out", _i32), ("flags", _i32),
+                ("p", ctypes.c_double * 8)]
 
 
 _ERRORS = {1: "invalid argument", 2: "kernel launch failed", 3: "workspace too small"}

@@ -1407,6 +1407,57 @@ def sho_coefficients_multi(terms, eps=1e-5):
     return _ShoCoefficientsMulti.apply(tuple(int(f) for *_, f in terms), float(eps), *flat)
 
 
+class PriorTable:
+    """the block table of a ParameterSpace as the kernels take it (include/exoplanet_amd.h, exo_prior_block): ``rows`` --
+    dicts of kind, offset, count, link, out, flags, p; ``n_free`` columns of z; ``out_cols``: the columns of every output array"""
+
+    def __init__(self, rows, n_free, out_cols):
+        self.n_block, self.n_free, self.out_cols = len(rows), int(n_free), [int(c) for c in out_cols]
+        self.blocks = (_lib.PriorBlock * max(self.n_block, 1))()
+        for b, row in zip(self.blocks, rows):
+            b.kind, b.offset, b.count, b.link, b.out, b.flags = (int(row[k]) for k in ("kind", "offset", "count", "link", "out", "flags"))
+            for i, v in enumerate(row["p"]):
+                b.p[i] = float(v)
+
+
+class _PriorTransform(torch.autograd.Function):
+    """exo_prior_transform_f64 / _vjp_f64: (table, z) -> (log prior (D,), one (D, columns) array per output); the reverse
+    recomputes from z and takes missing cotangents as null pointers"""
+
+    @staticmethod
+    def forward(ctx, table, z):
+        z = _dev(z, "z")
+        if z.dim() != 2 or z.shape[1] != table.n_free:
+            raise ValueError(f"z must have shape (n_chain, {table.n_free})")
+        D = z.shape[0]
+        outs = [torch.empty(D, c, dtype=torch.float64, device=z.device) for c in table.out_cols]
+        log_prior = torch.empty(D, dtype=torch.float64, device=z.device)
+        _call("exo_prior_transform_f64", z.device, _ptr(z), D, table.n_free, table.blocks, table.n_block,
+              _ptr_array(outs, len(outs)), _ptr(log_prior), _stream(z))
+        ctx.save_for_backward(z)
+        ctx.table = table
+        ctx.set_materialize_grads(False)
+        return (log_prior, *outs)
+
+    @staticmethod
+    def backward(ctx, glp, *gouts):
+        (z,) = ctx.saved_tensors
+        table = ctx.table
+        if glp is None and all(g is None for g in gouts):
+            return None, None
+        glp, *gouts = (None if g is None else _dev(g, "cotangent") for g in (glp, *gouts))
+        gz = torch.empty_like(z)
+        _call("exo_prior_transform_vjp_f64", z.device, _ptr(z), z.shape[0], table.n_free, table.blocks, table.n_block,
+              _ptr_array(gouts, len(gouts)), _ptr(glp), _ptr(gz), _stream(z))
+        return None, gz
+
+
+def prior_transform(z, table):
+    """``z`` (D, n_free) on the device, ``table``: a PriorTable -> (log prior (D,), the constrained parameters, one (D, columns)
+    tensor each): one launch each way (exoplanet_amd.distributions.ParameterSpace.constrain)"""
+    return _PriorTransform.apply(table, z)
+
+
 _PACK_DEFAULTS = (float("nan"), 0.0, 0.0, 0.0, 0.0, float("nan"), 1.0, 1.0, 0.0, 0.0)   # EXO_IN_* order; period, r: required
 
 

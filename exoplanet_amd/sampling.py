@@ -18,6 +18,9 @@ batch of chains: every chain grows its own trajectory by doubling, all chains in
 value + gradient evaluation per leaf, chains whose tree has ended are masked), the turning checks of the sub-trees
 through O(depth) momentum checkpoints (the iterative tree building of Phan, Pradhan & Jankowiak 2019), one host
 synchronisation per DOUBLING ("is any chain still growing?") instead of one per leaf.
+
+Both integrate whatever tensors they are given as unconstrained reals; supports and priors of a model's parameters come from
+`distributions.ParameterSpace` (``NUTS(space.wrap(logp_fn), [z0], ...)``).
 """
 import torch
 

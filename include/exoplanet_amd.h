@@ -47,8 +47,9 @@ extern "C" {
  *     exo_sparse_model_merged, exo_sparse_model_merge_vjp_f64: several lists per draw (planets, occultations) as one.
  * 14: EXO_GP_PREPARE_ADJOINT, a flag or-ed into n_chunks of a celerite pair (the adjoint scan beside the forward chunk kernel).
  * 15: the predictive variance -- exo_celerite_predict_var_work_doubles, exo_celerite_predict_var_f64.
- * 16: period search -- exo_bls_workspace_bytes, exo_bls_power_f64, exo_lomb_scargle_power_f64. */
-#define EXO_ABI_VERSION 16
+ * 16: period search -- exo_bls_workspace_bytes, exo_bls_power_f64, exo_lomb_scargle_power_f64.
+ * 17: priors and constrained parameters -- exo_prior_block, EXO_PRIOR_*, exo_prior_transform_f64 / _vjp_f64. */
+#define EXO_ABI_VERSION 17
 int32_t exo_abi_version(void);
 
 /* ---------------------------------------------------------------------------
@@ -825,6 +826,68 @@ int exo_bls_power_f64(const double* t, const double* y, const double* yerr, int6
 int exo_lomb_scargle_power_f64(const double* t, const double* y, const double* yerr, int64_t n_yerr, int64_t n, int64_t n_series,
                                const double* frequencies, int64_t n_frequency, double* power, void* workspace,
                                int64_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------
+ * Priors and constrained parameters (exoplanet_amd/distributions.py; definitions and measurements: DESIGN.md section 10).
+ * One unconstrained array z[n_chain][n_free] -- the flat array the samplers integrate -- becomes the constrained, named
+ * parameters of a model and the log prior density of every chain INCLUDING the log-Jacobians of the transforms, in one
+ * kernel; the reverse is one kernel too.  s(z) = 1 / (1 + exp(-z)), L(z) = log s(z) + log s(-z).
+ *
+ *   kind                 free coordinates        constrained value(s)                          contribution to the log prior
+ *   NORMAL               z                       x = z                                         -((x-mu)/sd)^2/2 - log sd - log(2 pi)/2
+ *   LOGNORMAL            z                       x = exp z                                     the normal log-density of z
+ *   UNIFORM              z                       x = lo + (hi-lo) s(z)                         L(z)
+ *   ANGLE                z1, z2                  theta = atan2(z1, z2)                         -(z1^2+z2^2)/2 - log 2pi [+ reg log(z1^2+z2^2)]
+ *   UNIT_DISK            z1, z2                  x = s(z1) - s(-z1), y = (s(z2) - s(-z2)) w    L(z1) + L(z2) + log(w),  w = 2 sqrt(s(z1) s(-z1))
+ *   QUAD_LIMB_DARK       z1, z2                  u1 = 2 sqrt(s(z1)) s(z2),                     L(z1) + L(z2)
+ *                                                u2 = sqrt(s(z1)) (s(-z2) - s(z2))
+ *   IMPACT_PARAMETER     z                       b = s(z) (1 + ror)                            L(z)
+ *   KIPPING13            z                       e = lo + (hi-lo) s(z)                         log Beta(e; alpha, beta) - log(I_hi - I_lo) + log(hi-lo) + L(z)
+ *   VANEYLEN19           z                       e = lo + (hi-lo) s(z)                         L(z) + logaddexp(log(1-f) + halfnormal(e; sg), log f + Rayleigh(e; sr))
+ *   KIPPING13_HYPER      za, zb, z               alpha = exp za, beta = exp zb, e = s(z)       the Beta log-density of every e + L(z), the hyperpriors
+ *   VANEYLEN19_HYPER     zg, zr, zf, z           sg = exp zg, sr = exp zr, f = s(zf), e        as VANEYLEN19, the hyperpriors
+ *
+ * A block has `count` elements.  Its free coordinates start at column `offset` of z: the hyperparameters first (one each,
+ * shared by the elements), then z1 of every element, then z2 of every element.  Its values go to consecutive entries of
+ * the output pointer list, the first at index `out`: one array [n_chain][count] per value (NORMAL .. VANEYLEN19: one;
+ * UNIT_DISK, QUAD_LIMB_DARK: two), then one array [n_chain] per hyperparameter.  p[]:
+ *   NORMAL, LOGNORMAL: mu, sd.  UNIFORM: lo, hi.  ANGLE: reg (flags & 1: regularised).  IMPACT_PARAMETER: ror, used when
+ *   link < 0; link >= 0 names an EARLIER block of kind NORMAL, LOGNORMAL or UNIFORM with `count` elements or one, whose
+ *   value is ror (and receives db/dror in the reverse pass).  KIPPING13: alpha, beta, lo, hi, c with c = -log B(alpha, beta)
+ *   [- log(I_hi - I_lo) + log(hi - lo) when flags & 1: bounded], computed by the caller.  VANEYLEN19: sg, sr, f, lo, hi.
+ *   KIPPING13_HYPER: alpha_mu, alpha_sd, beta_mu, beta_sd (truncated normals, lower bound 0; log-Jacobian za, zb).
+ *   VANEYLEN19_HYPER: sg_mu, sg_sd, sr_mu, sr_sd, f_mu, f_sd, lo, hi (sg, sr as above; f a normal truncated to [0, 1]).
+ *
+ * table: HOST array of n_block <= EXO_PRIOR_MAX_BLOCKS blocks; theta: HOST array of the device output pointers (at most
+ * EXO_PRIOR_MAX_OUTPUTS, every one required); both travel by value in the kernel arguments.  log_prior[n_chain].  The
+ * reverse recomputes from z; gtheta: HOST array of the cotangents of the outputs, a null entry standing for zero;
+ * glog_prior[n_chain] or null; gz[n_chain][n_free]: every element is written (coordinates no block covers: zero).
+ * A lane is a chain and sums its log prior in a register: results do not depend on the launch geometry.
+ * EXO_ERR_INVALID_ARGUMENT, before any launch: negative sizes, null pointers, an unknown kind, a block outside z or
+ * overlapping its predecessor, a link that points forward or to itself.  n_chain == 0: EXO_OK, nothing launched.
+ * ------------------------------------------------------------------------- */
+#define EXO_PRIOR_MAX_BLOCKS 32
+#define EXO_PRIOR_MAX_OUTPUTS 48
+#define EXO_PRIOR_NORMAL 0
+#define EXO_PRIOR_LOGNORMAL 1
+#define EXO_PRIOR_UNIFORM 2
+#define EXO_PRIOR_ANGLE 3
+#define EXO_PRIOR_UNIT_DISK 4
+#define EXO_PRIOR_QUAD_LIMB_DARK 5
+#define EXO_PRIOR_IMPACT_PARAMETER 6
+#define EXO_PRIOR_KIPPING13 7
+#define EXO_PRIOR_VANEYLEN19 8
+#define EXO_PRIOR_KIPPING13_HYPER 9
+#define EXO_PRIOR_VANEYLEN19_HYPER 10
+#define EXO_PRIOR_N_KINDS 11
+typedef struct exo_prior_block {
+  int32_t kind, offset, count, link, out, flags;
+  double p[8];
+} exo_prior_block;
+int exo_prior_transform_f64(const double* z, int64_t n_chain, int32_t n_free, const exo_prior_block* table, int32_t n_block,
+                            double* const* theta, double* log_prior, void* stream);
+int exo_prior_transform_vjp_f64(const double* z, int64_t n_chain, int32_t n_free, const exo_prior_block* table, int32_t n_block,
+                                const double* const* gtheta, const double* glog_prior, double* gz, void* stream);
 
 #ifdef __cplusplus
 }
