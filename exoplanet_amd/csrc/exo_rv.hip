@@ -12,39 +12,22 @@
 // A radial-velocity series is a few hundred to a few thousand epochs: the work is nothing, the
 // ~20 launch-bound torch kernels of the composed path (M, Kepler op, rotations, broadcasts, and
 // their reverse) were as long as a whole light-curve sweep.  One launch forward, one reverse.
-//   rv[d][n][p] = amp[d][p] * (cw cos f - sw sin f + e cw),   f = f(M = (t_n - tp) nn, e)
+//   rv[d][n][p] = amp[d][p] * (cw (cos f + e) - sw sin f),   f = f(M = (t_n - tp) nn, e)
 // Reverse: one block per (draw, planet); lanes stride over the epochs, partial sums in
 // registers, one fixed-order LDS reduction (bit-reproducible).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/exoplanet_amd.h"
-#include "exo_math.hpp"
+#include "exo_rv_core.hpp"     // the per-sample arithmetic: rv_sample, ov_sample, rv_vjp_term, ov_vjp_term
 
 namespace {
 
+using exo::OvSample;
+using exo::ov_sample;
+using exo::rv_sample;
+
 constexpr int kRvBlock = 256;
-
-struct RvSample {
-  double g;      // cw cos f - sw sin f + e cw
-  double sinf, cosf;
-};
-
-// e outside [0, 1): NaN (the docstring's contract for the Kepler op, keplerian.py:58)
-__device__ __forceinline__ RvSample rv_sample(double t, const double* __restrict__ p) {
-  const double e = p[EXO_RV_ECC];
-  const bool ok = (e >= 0.0) && (e < 1.0);
-  const double es = ok ? e : 0.5;
-  const exo::KeplerHalf kh = exo::kepler_half((t - p[EXO_RV_TP]) * p[EXO_RV_N], es, sqrt(1.0 - es), sqrt(1.0 + es));
-  const double X2 = kh.X * kh.X, Y2 = kh.Y * kh.Y;
-  const double iden = 1.0 / (X2 + Y2);
-  const double nan = __builtin_nan("");
-  RvSample s;
-  s.sinf = ok ? 2.0 * kh.X * kh.Y * iden : nan;
-  s.cosf = ok ? (X2 - Y2) * iden : nan;
-  s.g = p[EXO_RV_COSW] * s.cosf - p[EXO_RV_SINW] * s.sinf + e * p[EXO_RV_COSW];
-  return s;
-}
 
 __global__ __launch_bounds__(kRvBlock) void rv_fwd_kernel(const double* __restrict__ t, int64_t n_cad,
                                                           const double* __restrict__ params, int64_t n_draw,
@@ -68,29 +51,11 @@ __global__ __launch_bounds__(kRvBlock) void rv_vjp_kernel(const double* __restri
   const int64_t d = rec_i / n_planet;
   const int p = (int)(rec_i - d * n_planet);
   const double* __restrict__ rec = params + rec_i * EXO_RV_NPAR;
-  const double nn = rec[EXO_RV_N], tp = rec[EXO_RV_TP], e = rec[EXO_RV_ECC], cw = rec[EXO_RV_COSW],
-               sw = rec[EXO_RV_SINW], amp = rec[EXO_RV_AMP];
-  const double ome2 = 1.0 - e * e;
-  const double iome2 = 1.0 / ome2, iome32 = iome2 / sqrt(ome2);
   double acc[EXO_RV_NPAR];
 #pragma unroll
   for (int k = 0; k < EXO_RV_NPAR; ++k) acc[k] = 0.0;
-  for (int64_t n = threadIdx.x; n < n_cad; n += kRvBlock) {
-    const double tn = t[n];
-    const RvSample s = rv_sample(tn, rec);
-    const double gb = grv[(d * n_cad + n) * n_planet + p];
-    // d f / d M = (1 + e cos f)^2 / (1 - e^2)^(3/2),  d f / d e = (2 + e cos f) sin f / (1 - e^2)
-    const double q = 1.0 + e * s.cosf;
-    const double dfdM = q * q * iome32, dfde = (1.0 + q) * s.sinf * iome2;
-    const double dgdf = -(cw * s.sinf + sw * s.cosf);
-    const double a = gb * amp;
-    acc[EXO_RV_N] += a * dgdf * dfdM * (tn - tp);
-    acc[EXO_RV_TP] -= a * dgdf * dfdM * nn;
-    acc[EXO_RV_ECC] += a * (dgdf * dfde + cw);
-    acc[EXO_RV_COSW] += a * (s.cosf + e);
-    acc[EXO_RV_SINW] -= a * s.sinf;
-    acc[EXO_RV_AMP] += gb * s.g;
-  }
+  for (int64_t n = threadIdx.x; n < n_cad; n += kRvBlock)
+    exo::rv_vjp_term(t[n], rec, grv[(d * n_cad + n) * n_planet + p], acc);
   // fixed-order reduction: thread (slot, c) adds 16 columns, then one thread per slot the 16 partials
   __shared__ double cols[EXO_RV_NPAR][kRvBlock];
   __shared__ double part[EXO_RV_NPAR][16];
@@ -123,44 +88,6 @@ __global__ __launch_bounds__(kRvBlock) void rv_vjp_kernel(const double* __restri
 // torch kernels (solve, radius, three rotations, broadcasts, and their reverse: ~40) are the cost; here one launch
 // each way.  out[d][n][p][3]; reverse: one block per (draw, planet), fixed-order reduction.
 // ---------------------------------------------------------------------------------------------
-struct OvSample {
-  double sinf, cosf;
-  double u, v;          // in-plane vector for unit amplitude
-  double x2, y1, y2;    // after the omega and inclination rotations
-  double X, Y, Z;       // unit amplitude
-};
-
-template <int MODE>
-__device__ __forceinline__ OvSample ov_sample(double t, const double* __restrict__ p) {
-  const double e = p[EXO_OV_ECC];
-  const bool ok = (e >= 0.0) && (e < 1.0);
-  const double es = ok ? e : 0.5;
-  const exo::KeplerHalf kh = exo::kepler_half((t - p[EXO_OV_TP]) * p[EXO_OV_N], es, sqrt(1.0 - es), sqrt(1.0 + es));
-  const double X2 = kh.X * kh.X, Y2 = kh.Y * kh.Y;
-  const double iden = 1.0 / (X2 + Y2);
-  const double nan = __builtin_nan("");
-  OvSample s;
-  s.sinf = ok ? 2.0 * kh.X * kh.Y * iden : nan;
-  s.cosf = ok ? (X2 - Y2) * iden : nan;
-  if (MODE == 1) {
-    s.u = -s.sinf; s.v = s.cosf + e;
-  } else if (MODE == 2) {
-    const double q = 1.0 + e * s.cosf, g = q * q / (1.0 - e * e);
-    s.u = -g * s.cosf; s.v = -g * s.sinf;
-  } else {
-    const double rho = (1.0 - e * e) / (1.0 + e * s.cosf);
-    s.u = rho * s.cosf; s.v = rho * s.sinf;
-  }
-  const double x1 = p[EXO_OV_COSW] * s.u - p[EXO_OV_SINW] * s.v;
-  s.y1 = p[EXO_OV_SINW] * s.u + p[EXO_OV_COSW] * s.v;
-  s.x2 = x1;
-  s.y2 = p[EXO_OV_COSI] * s.y1;
-  s.Z = -p[EXO_OV_SINI] * s.y1;
-  s.X = p[EXO_OV_COSO] * s.x2 - p[EXO_OV_SINO] * s.y2;
-  s.Y = p[EXO_OV_SINO] * s.x2 + p[EXO_OV_COSO] * s.y2;
-  return s;
-}
-
 template <int MODE>
 __global__ __launch_bounds__(kRvBlock) void ov_fwd_kernel(const double* __restrict__ t, int64_t n_cad,
                                                           const double* __restrict__ params, int64_t n_draw,
@@ -187,55 +114,12 @@ __global__ __launch_bounds__(kRvBlock) void ov_vjp_kernel(const double* __restri
   const int64_t d = rec_i / n_planet;
   const int p = (int)(rec_i - d * n_planet);
   const double* __restrict__ rec = params + rec_i * EXO_OV_NPAR;
-  const double nn = rec[EXO_OV_N], tp = rec[EXO_OV_TP], e = rec[EXO_OV_ECC], cw = rec[EXO_OV_COSW], sw = rec[EXO_OV_SINW],
-               ci = rec[EXO_OV_COSI], si = rec[EXO_OV_SINI], amp = rec[EXO_OV_AMP], cO = rec[EXO_OV_COSO],
-               sO = rec[EXO_OV_SINO];
-  const double ome2 = 1.0 - e * e;
-  const double iome2 = 1.0 / ome2, iome32 = iome2 / sqrt(ome2);
   double acc[EXO_OV_NPAR];
 #pragma unroll
   for (int k = 0; k < EXO_OV_NPAR; ++k) acc[k] = 0.0;
   for (int64_t n = threadIdx.x; n < n_cad; n += kRvBlock) {
-    const double tn = t[n];
-    const OvSample s = ov_sample<MODE>(tn, rec);
     const double* __restrict__ g = gout + 3 * ((d * n_cad + n) * n_planet + p);
-    const double gX0 = g[0], gY0 = g[1], gZ0 = g[2];
-    acc[EXO_OV_AMP] += gX0 * s.X + gY0 * s.Y + gZ0 * s.Z;
-    const double gX = amp * gX0, gY = amp * gY0, gZ = amp * gZ0;
-    acc[EXO_OV_COSO] += gX * s.x2 + gY * s.y2;
-    acc[EXO_OV_SINO] += gY * s.x2 - gX * s.y2;
-    const double gx2 = gX * cO + gY * sO, gy2 = gY * cO - gX * sO;
-    acc[EXO_OV_COSI] += gy2 * s.y1;
-    acc[EXO_OV_SINI] -= gZ * s.y1;
-    const double gy1 = gy2 * ci - gZ * si, gx1 = gx2;
-    acc[EXO_OV_COSW] += gx1 * s.u + gy1 * s.v;
-    acc[EXO_OV_SINW] += gy1 * s.u - gx1 * s.v;
-    const double gu = gx1 * cw + gy1 * sw, gv = gy1 * cw - gx1 * sw;
-    // (u, v) as functions of (f, e), f = f(M, e):  d f / d M = (1 + e cos f)^2 / (1 - e^2)^(3/2),
-    // d f / d e = (2 + e cos f) sin f / (1 - e^2)
-    const double q = 1.0 + e * s.cosf;
-    double gf, ge;
-    if (MODE == 1) {
-      gf = -gu * s.cosf - gv * s.sinf;
-      ge = gv;
-    } else if (MODE == 2) {
-      const double g = q * q * iome2;
-      const double g_f = -2.0 * q * e * s.sinf * iome2;                                 // d g / d f
-      const double g_e = 2.0 * q * (s.cosf * ome2 + e * q) * iome2 * iome2;             // d g / d e at fixed f
-      gf = -gu * (g_f * s.cosf - g * s.sinf) - gv * (g_f * s.sinf + g * s.cosf);
-      ge = -(gu * s.cosf + gv * s.sinf) * g_e;
-    } else {
-      const double iq = 1.0 / q, rho = ome2 * iq;
-      const double rho_f = rho * e * s.sinf * iq;                                // d rho / d f
-      const double rho_e = -(2.0 * e + s.cosf * (1.0 + e * e)) * iq * iq;        // d rho / d e at fixed f
-      gf = gu * (rho_f * s.cosf - rho * s.sinf) + gv * (rho_f * s.sinf + rho * s.cosf);
-      ge = (gu * s.cosf + gv * s.sinf) * rho_e;
-    }
-    const double dfdM = q * q * iome32, dfde = (1.0 + q) * s.sinf * iome2;
-    const double gM = gf * dfdM;
-    acc[EXO_OV_N] += gM * (tn - tp);
-    acc[EXO_OV_TP] -= gM * nn;
-    acc[EXO_OV_ECC] += ge + gf * dfde;
+    exo::ov_vjp_term<MODE>(t[n], rec, g[0], g[1], g[2], acc);
   }
   // fixed-order reduction, as in rv_vjp_kernel
   __shared__ double cols[EXO_OV_NPAR][kRvBlock];

@@ -220,7 +220,7 @@ class _Kepler(torch.autograd.Function):
     def backward(ctx, gs, gc):
         sinf, cosf, e = ctx.saved_tensors
         # df/dM = (1+e cosf)^2/(1-e^2)^{3/2},  df/de = (2+e cosf) sinf/(1-e^2)
-        ome2 = 1 - e * e
+        ome2 = (1 - e) * (1 + e)      # not 1 - e^2, which loses the digits of 1 - e as e -> 1
         gf = gs * cosf - gc * sinf
         dfdM = (1 + e * cosf) ** 2 / ome2 ** 1.5
         dfde = (2 + e * cosf) * sinf / ome2

@@ -214,7 +214,7 @@ class KeplerianOrbit:
             E0 = 2 * torch.atan2(torch.sqrt(1 - self.ecc) * self.cos_omega,
                                  torch.sqrt(1 + self.ecc) * (1 + self.sin_omega))
             self.M0 = E0 - self.ecc * torch.sin(E0)
-            ome2 = 1 - self.ecc ** 2
+            ome2 = (1 - self.ecc) * (1 + self.ecc)      # not 1 - e^2: that loses the digits of 1 - e as e -> 1
             self.K0 = self.K0 / torch.sqrt(ome2)
             incl_factor = (1 + self.ecc * self.sin_omega) / ome2
 

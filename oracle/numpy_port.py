@@ -19,11 +19,18 @@ c_light = 37231.66360672704
 
 TWO_PI_HI = 6.283185307179586
 TWO_PI_LO = 2.4492935982947064e-16
-# three-part split of 2 pi (30 + 30 + 53 bits): k * C1 and k * C2 are exact in
-# float64 for |k| < 2^23, which stands in for the fused multiply-add numpy lacks
-TWO_PI_C1 = 6.283185303211212
-TWO_PI_C2 = 3.9683743166540886e-09
-TWO_PI_C3 = 2.068073192717642e-18
+
+
+def _two_prod(a, b):
+    """a * b = p + err exactly (Veltkamp / Dekker): stands in for the fused multiply-add numpy lacks"""
+    def split(x):
+        c = 134217729.0 * x
+        hi = c - (c - x)
+        return hi, x - hi
+    p = a * b
+    ah, al = split(a)
+    bh, bl = split(b)
+    return p, ((ah * bh - p) + ah * bl + al * bh) + al * bl
 
 
 # =============================================================================
@@ -41,14 +48,31 @@ def _e_minus_sin(E):
     return np.where(np.abs(E) < 0.9, ser, E - np.sin(E))
 
 
+def mean_anomaly_reduced(t, tp, n):
+    """(t - tp) n reduced to [-pi, pi]: the difference and the product each as an exact sum of two doubles, the multiple
+    of 2 pi taken off the leading part exactly, then the tails.  With BJD-sized t and tp = O(1) the plain product carries
+    2.3e-16 |M| ~ 3e-9 rad at |M| = 3e7; this is good to ~2e-16."""
+    t, tp, n = np.broadcast_arrays(*(np.asarray(x, dtype=np.float64) for x in (t, tp, n)))
+    dh = t - tp
+    tb = dh - t
+    dl = (t - (dh - tb)) - (tp + tb)
+    mh, merr = _two_prod(dh, n)
+    ml = merr + dl * n
+    k = np.rint(mh / TWO_PI_HI)
+    p, perr = _two_prod(k, TWO_PI_HI + np.zeros_like(mh))
+    return (((mh - p) - perr) + ml) - k * TWO_PI_LO
+
+
 def kepler_E(M, e):
     """Eccentric anomaly by Markley (1995, CeMDA 63, 101): cubic Pade starter
     + one fifth-order correction (fixed cost, no iteration).  M any real."""
     M = np.asarray(M, dtype=np.float64)
     e = np.asarray(e, dtype=np.float64) + np.zeros_like(M)
-    # Cody-Waite reduction of M to [-pi, pi] with exact partial products
+    # Cody-Waite reduction of M to [-pi, pi]: k * TWO_PI_HI as an exact sum of two doubles, so that M - k * TWO_PI_HI
+    # is exact for any k (a three-constant split with exact products held only for |k| < 2^23, |M| < 5e7)
     k = np.rint(M / TWO_PI_HI)
-    Mr = ((M - k * TWO_PI_C1) - k * TWO_PI_C2) - k * TWO_PI_C3
+    p, perr = _two_prod(k, TWO_PI_HI + np.zeros_like(M))
+    Mr = ((M - p) - perr) - k * TWO_PI_LO
     sgn = np.where(Mr < 0, -1.0, 1.0)
     Mr = np.abs(Mr)
     ome = 1.0 - e
@@ -73,26 +97,29 @@ def kepler_E(M, e):
     return sgn * E, k
 
 
-def kepler(M, e):
-    """(sinf, cosf) of the true anomaly.  e outside [0,1) -> NaN."""
+def _kepler_xy(M, e):
+    """(X, Y) ~ (cos f/2, sin f/2) up to a common factor: (sqrt(1-e) cos E/2, sqrt(1+e) sin E/2).  X^2 + Y^2 = 1 - e cos E,
+    X^2 - Y^2 = cos E - e, 2 X Y = sqrt(1 - e^2) sin E: none of them cancels as e -> 1, at periastron or at apoapsis"""
     M = np.asarray(M, dtype=np.float64)
     e = np.asarray(e, dtype=np.float64) + np.zeros_like(M)
     E, _ = kepler_E(M, e)
-    # half-angle form: (cos f/2, sin f/2) ~ (sqrt(1-e) cos E/2, sqrt(1+e) sin E/2);
-    # 1 - e cos E = X^2 + Y^2 has no cancellation as e -> 1, E -> 0
     with np.errstate(invalid="ignore"):
         X = np.sqrt(1 - e) * np.cos(0.5 * E)
         Y = np.sqrt(1 + e) * np.sin(0.5 * E)
-    den = X * X + Y * Y
-    cosf = (X * X - Y * Y) / den
-    sinf = 2 * X * Y / den
     bad = ~((e >= 0) & (e < 1))
-    return np.where(bad, np.nan, sinf), np.where(bad, np.nan, cosf)
+    return np.where(bad, np.nan, X), np.where(bad, np.nan, Y)
+
+
+def kepler(M, e):
+    """(sinf, cosf) of the true anomaly.  e outside [0,1) -> NaN."""
+    X, Y = _kepler_xy(M, e)
+    den = X * X + Y * Y
+    return 2 * X * Y / den, (X * X - Y * Y) / den
 
 
 def kepler_grad(sinf, cosf, e):
     """df/dM, df/de."""
-    ome2 = 1 - e * e
+    ome2 = (1 - e) * (1 + e)      # not 1 - e^2: that loses the digits of 1 - e as e -> 1
     dfdM = (1 + e * cosf) ** 2 / ome2 ** 1.5
     dfde = (2 + e * cosf) * sinf / ome2
     return dfdM, dfde
@@ -1066,19 +1093,25 @@ def radial_velocity(t, params, jac=False):
     t = np.asarray(t, dtype=np.float64)
     params = np.asarray(params, dtype=np.float64)
     n, tp, e, cw, sw, amp = (params[:, None, :, k] for k in range(RV_NPAR))
-    M = (t[None, :, None] - tp) * n
-    sinf, cosf = kepler(M, e + np.zeros_like(M))
-    g = cw * cosf - sw * sinf + e * cw
+    M = mean_anomaly_reduced(t[None, :, None], tp, n)
+    X, Y = _kepler_xy(M, e + np.zeros_like(M))
+    den = X * X + Y * Y
+    sinf, cosf = 2 * X * Y / den, (X * X - Y * Y) / den
+    cpe = ((1 + e) * X * X - (1 - e) * Y * Y) / den      # cos f + e, without the cancellation at apoapsis as e -> 1
+    g = cw * cpe - sw * sinf
     rv = amp * g
     if not jac:
         return rv
-    dfdM, dfde = kepler_grad(sinf, cosf, e)
+    # as kepler_grad, with 1 + e cos f = (1 - e)(1 + e) / (1 - e cos E) from the half-angle sums (no cancellation at apoapsis)
+    ome2 = (1 - e) * (1 + e)
+    q = ome2 / den
+    dfdM, dfde = q * q / ome2 ** 1.5, (1 + q) * sinf / ome2
     dgdf = -(cw * sinf + sw * cosf)
     J = np.zeros(rv.shape + (RV_NPAR,))
     J[..., RV_N] = amp * dgdf * dfdM * (t[None, :, None] - tp)
     J[..., RV_TP] = -amp * dgdf * dfdM * n
     J[..., RV_ECC] = amp * (dgdf * dfde + cw)
-    J[..., RV_COSW] = amp * (cosf + e)
+    J[..., RV_COSW] = amp * cpe
     J[..., RV_SINW] = -amp * sinf
     J[..., RV_AMP] = g
     return rv, J
@@ -1088,6 +1121,87 @@ def radial_velocity_vjp(t, params, grv):
     """(rv, gparams [D, P, 6]) for a cotangent grv [D, N, P]"""
     rv, J = radial_velocity(t, params, jac=True)
     return rv, np.einsum("dnpk,dnp->dpk", J, np.asarray(grv, dtype=np.float64))
+
+
+# =============================================================================
+# position / velocity / acceleration vectors at record level (ops.orbit_vector): keplerian.py:380-409, :572-578,
+# :679-688, :283-322
+# =============================================================================
+OV_NPAR = 10
+OV_N, OV_TP, OV_ECC, OV_COSW, OV_SINW, OV_COSI, OV_SINI, OV_AMP, OV_COSO, OV_SINO = range(10)
+
+
+def orbit_vector(t, params, mode=0, jac=False):
+    """out [D, N, P, 3] = amp R (u, v): in the orbital plane, mode 0 (position) (u, v) = (1-e^2)/(1+e cos f) (cos f, sin f),
+    mode 1 (velocity) (-sin f, cos f + e), mode 2 (acceleration) -(1+e cos f)^2/(1-e^2) (cos f, sin f); R the rotations by
+    omega, the inclination and Omega.  params [D, P, 10] = (n, t_periastron, e, cos w, sin w, cos i, sin i, amp, cos O,
+    sin O).  With jac: also d out / d params [D, N, P, 3, 10].  1 + e cos f and cos f + e are formed from the half-angle
+    pair, (1 - e^2) as (1 - e)(1 + e): nothing cancels as e -> 1."""
+    t = np.asarray(t, dtype=np.float64)
+    params = np.asarray(params, dtype=np.float64)
+    n, tp, e, cw, sw, ci, si, amp, cO, sO = (params[:, None, :, k] for k in range(OV_NPAR))
+    dt = t[None, :, None] - tp
+    X, Y = _kepler_xy(mean_anomaly_reduced(t[None, :, None], tp, n), e + np.zeros_like(dt))
+    X2, Y2 = X * X, Y * Y
+    den = X2 + Y2
+    sinf, cosf = 2 * X * Y / den, (X2 - Y2) / den
+    ome2 = (1 - e) * (1 + e)
+    q = ome2 / den                                   # 1 + e cos f
+    cpe = ((1 + e) * X2 - (1 - e) * Y2) / den        # cos f + e
+    if mode == 1:
+        u, v = -sinf, cpe
+    elif mode == 2:
+        g = q * q / ome2
+        u, v = -g * cosf, -g * sinf
+    else:
+        u, v = X2 - Y2, 2 * X * Y
+
+    def rot(u, v):
+        x1, y1 = cw * u - sw * v, sw * u + cw * v
+        y2 = ci * y1
+        return np.stack([cO * x1 - sO * y2, sO * x1 + cO * y2, -si * y1], axis=-1), x1, y1, y2
+
+    unit, x1, y1, y2 = rot(u, v)
+    out = amp[..., None] * unit
+    if not jac:
+        return out
+    # (u, v) as functions of (f, e); f = f(M, e)
+    if mode == 1:
+        u_f, v_f, u_e, v_e = -cosf, -sinf, 0.0 * e, 1.0 + 0.0 * e
+    elif mode == 2:
+        g_f = -2 * q * e * sinf / ome2
+        g_e = 2 * q * (cosf * ome2 + e * q) / ome2 ** 2
+        u_f, v_f = -(g_f * cosf - g * sinf), -(g_f * sinf + g * cosf)
+        u_e, v_e = -g_e * cosf, -g_e * sinf
+    else:
+        rho = ome2 / q
+        rho_f = rho * e * sinf / q
+        rho_e = -(e * q + cpe) / q ** 2
+        u_f, v_f = rho_f * cosf - rho * sinf, rho_f * sinf + rho * cosf
+        u_e, v_e = rho_e * cosf, rho_e * sinf
+    dfdM = q * q / ome2 ** 1.5
+    dfde = (1 + q) * sinf / ome2
+    A = amp[..., None]
+    z = np.zeros_like(x1)
+    J = np.zeros(out.shape + (OV_NPAR,))
+    d_f = rot(u_f, v_f)[0]
+    J[..., OV_N] = A * d_f * (dfdM * dt)[..., None]
+    J[..., OV_TP] = -A * d_f * (dfdM * n)[..., None]
+    J[..., OV_ECC] = A * (rot(u_e + 0 * x1, v_e + 0 * x1)[0] + d_f * dfde[..., None])
+    J[..., OV_COSW] = A * np.stack([cO * u - sO * ci * v, sO * u + cO * ci * v, -si * v], axis=-1)
+    J[..., OV_SINW] = A * np.stack([-cO * v - sO * ci * u, -sO * v + cO * ci * u, -si * u], axis=-1)
+    J[..., OV_COSI] = A * np.stack([-sO * y1, cO * y1, z], axis=-1)
+    J[..., OV_SINI] = A * np.stack([z, z, -y1], axis=-1)
+    J[..., OV_AMP] = unit
+    J[..., OV_COSO] = A * np.stack([x1, y2, z], axis=-1)
+    J[..., OV_SINO] = A * np.stack([-y2, x1, z], axis=-1)
+    return out, J
+
+
+def orbit_vector_vjp(t, params, gout, mode=0):
+    """(out, gparams [D, P, 10]) for a cotangent gout [D, N, P, 3]"""
+    out, J = orbit_vector(t, params, mode=mode, jac=True)
+    return out, np.einsum("dnpck,dnpc->dpk", J, np.asarray(gout, dtype=np.float64))
 
 
 # =============================================================================

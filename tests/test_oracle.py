@@ -27,7 +27,8 @@ def harness():
     out = os.path.join(ROOT, "tests", "_build")
     os.makedirs(out, exist_ok=True)
     so = os.path.join(out, "host_harness.so")
-    srcs = [os.path.join(ROOT, "tests", "host_harness.cpp"), os.path.join(ROOT, "exoplanet_amd", "csrc", "exo_math.hpp")]
+    srcs = [os.path.join(ROOT, "tests", "host_harness.cpp")] + [os.path.join(ROOT, "exoplanet_amd", "csrc", h)
+                                                                for h in ("exo_math.hpp", "exo_rv_core.hpp")]
     if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
         subprocess.run(["g++", "-O2", "-shared", "-fPIC", "-o", so, srcs[0]], check=True)
     return ctypes.CDLL(so)
