@@ -10,7 +10,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # EXOPLANET_AMD_LIB selects another in-tree build of the same ABI (A/B measurements)
 LIB_PATH = os.environ.get("EXOPLANET_AMD_LIB") or os.path.join(_HERE, "lib", "libexoplanet_amd.so")
-ABI_VERSION = 17
+ABI_VERSION = 18
 
 _c_dp = ctypes.c_void_p  # device pointers travel as integers
 _i64 = ctypes.c_int64
@@ -153,6 +153,18 @@ _SIGNATURES = {
     "exo_transit_chi2_ttv_vjp_f64": (ctypes.c_int, [_c_dp, _i64, _c_dp, _i64, _c_dp, _c_dp, _i32, _c_dp, _c_dp, _i64, _i32, _u32,
                                                     _c_dp, _c_dp, _i32, _c_dp, _c_dp, _i64, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp,
                                                     _i64, _c_dp]),
+    # ..., flags, y, var, n_var, mean, n_mean, jit2, n_jit, chi2, gmean, gjit2, gparams, gld, workspace, workspace_bytes, stream
+    "exo_transit_noise_vjp_f64": (ctypes.c_int, [_c_dp, _i64, _c_dp, _i64, _c_dp, _c_dp, _i32, _c_dp, _c_dp, _i64, _i32, _u32,
+                                                 _c_dp, _c_dp, _i64, _c_dp, _i64, _c_dp, _i64, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp,
+                                                 _c_dp, _i64, _c_dp]),
+    # ..., flags, ttv_edges, ttv_shift, n_edge, y, var, n_var, mean, n_mean, jit2, n_jit, chi2, gmean, gjit2, gparams, gld, gshift, ...
+    "exo_transit_noise_ttv_vjp_f64": (ctypes.c_int, [_c_dp, _i64, _c_dp, _i64, _c_dp, _c_dp, _i32, _c_dp, _c_dp, _i64, _i32, _u32,
+                                                     _c_dp, _c_dp, _i32, _c_dp, _c_dp, _i64, _c_dp, _i64, _c_dp, _i64, _c_dp, _c_dp,
+                                                     _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _i64, _c_dp]),
+    "exo_white_noise_workspace_bytes": (_i64, [_i64, _i64]),
+    # y, var, n_cad, n_var, mean, n_mean, jit2, n_jit, n_draw, series, series_ready, terms, workspace, workspace_bytes, stream
+    "exo_white_noise_terms_f64": (ctypes.c_int, [_c_dp, _c_dp, _i64, _i64, _c_dp, _i64, _c_dp, _i64, _i64, _c_dp, _i32, _c_dp,
+                                                 _c_dp, _i64, _c_dp]),
     # period, ds, ps, t0, ds, ps, ttv (host), ttv_ds (host), n_transit (host), n_draw, n_planet, n_edge, edges, shift, stream
     "exo_ttv_tables_f64": (ctypes.c_int, [_c_dp, _i64, _i64, _c_dp, _i64, _i64, _c_dp, _c_dp, _c_dp, _i64, _i32, _i32, _c_dp,
                                           _c_dp, _c_dp]),

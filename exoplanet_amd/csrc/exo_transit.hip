@@ -1909,12 +1909,22 @@ struct FillCursor {
 // (1024 threads per block for batches of at most 256 draws: the scatter of a draw's values is one block's work, and
 // with few draws the loads it keeps in flight are what bounds it -- C4 at 64 draws: 34 -> 10 us)
 // (also the tail of transit_runs_kernel when a draw is one block's work -- no restrict on what that kernel wrote)
+// NOISE (exo_transit_noise[_ttv]_vjp_f64): two more per-draw sums ride the same reductions -- sum w f (gmean) and
+// sum w^2 (f^2 - 2 f r) (gjit2) over the solved cadences.  Single-pass route: the limb-darkening slots 3 and 4 of the
+// partials, which only an occultation uses and that route has none; three-sweep route: two more rows of block partials
+// behind the misfit's ([3][n_draw][n_chi2_part]), each summed by a thread of its own in block order.
+struct NoiseOut {
+  double* gmean;
+  double* gjit2;
+};
+template <bool NOISE = false>
 __device__ __forceinline__ void finish_draw(
     int64_t draw, const double* partial, int nblk, int n_planet, bool secondary, double* __restrict__ gparams,
     double* __restrict__ gld, double* __restrict__ flux_dot, int64_t n_cad, uint32_t flags, int n_ev, const RunLists& rl,
     const double* vals, const int32_t* vcad, double* flux,
     const double* __restrict__ chi2_part, int n_chi2_part, double* __restrict__ chi2_out, const Ttv& ttv,
-    int64_t cm_draws = 0) {   // cm_draws: 0, or n_draw -- the summed flux is cadence-major, [n_cad][n_draw]
+    int64_t cm_draws = 0,     // cm_draws: 0, or n_draw -- the summed flux is cadence-major, [n_cad][n_draw]
+    NoiseOut nzo = NoiseOut{nullptr, nullptr}, int64_t n_draw = 0) {
   if (ttv.gshift) {
     // timing tables, lists whose runs carry their bins: the runs' sums to their bins, in run order (the bins of a
     // list's runs ascend); the samples of any other list added to gshift themselves
@@ -1942,6 +1952,12 @@ __device__ __forceinline__ void finish_draw(
     for (int b = 0; b < n_chi2_part; ++b) v += chi2_part[draw * n_chi2_part + b];
     chi2_out[draw] = v;
   }
+  if (NOISE && chi2_out && (threadIdx.x == blockDim.x - 2 || threadIdx.x == blockDim.x - 3)) {
+    const int q = (int)(blockDim.x - 1 - threadIdx.x);   // 1: gmean, 2: gjit2
+    double v = 0.0;
+    for (int b = 0; b < n_chi2_part; ++b) v += chi2_part[(q * n_draw + draw) * n_chi2_part + b];
+    (q == 1 ? nzo.gmean : nzo.gjit2)[draw] = v;
+  }
   const int ng_draw = n_planet * kNG + 7;
   const int s = threadIdx.x;
   if (partial) {
@@ -1967,6 +1983,8 @@ __device__ __forceinline__ void finish_draw(
         const int nld = secondary ? 6 : 3;
         if (k < nld) gld[draw * nld + k] = v;
         if (k == 6 && flux_dot) flux_dot[draw] = v;
+        if (NOISE && !chi2_out && k == 3) nzo.gmean[draw] = v;
+        if (NOISE && !chi2_out && k == 4) nzo.gjit2[draw] = v;
       }
     }
   }
@@ -2049,12 +2067,28 @@ __global__ __launch_bounds__(1024) void transit_finish_kernel(
               ((flags & EXO_FLAG_CADENCE_MAJOR) && !(flags & EXO_FLAG_PER_PLANET)) ? (int64_t)gridDim.x : 0);
 }
 
+// the same with the two sums of the sampled-mean / jitter likelihood (grid: one block per draw)
+__global__ __launch_bounds__(1024) void transit_finish_noise_kernel(
+    const double* __restrict__ partial, int nblk, int n_planet, double* __restrict__ gparams, double* __restrict__ gld,
+    double* __restrict__ chi2_direct, int64_t n_cad, uint32_t flags, int n_ev, RunLists rl, const int32_t* __restrict__ vcad,
+    const double* __restrict__ chi2_part, int n_chi2_part, double* __restrict__ chi2_out, Ttv ttv, NoiseOut nzo) {
+  finish_draw<true>(blockIdx.x, partial, nblk, n_planet, (flags & EXO_FLAG_SECONDARY) != 0, gparams, gld, chi2_direct, n_cad, flags,
+                    n_ev, rl, nullptr, vcad, nullptr, chi2_part, n_chi2_part, chi2_out, ttv, 0, nzo, (int64_t)gridDim.x);
+}
+
 struct FinishArgs {
   double* gparams;
   double* gld;
   double* flux_dot;
   int fold;        // the runs kernel finishes its draws itself: no transit_finish_kernel launch
   int32_t* done;   // [n_draw] blocks of the draw that are through (zeroed by transit_window_kernel)
+};
+// NOISE: the draw's mean and jitter^2 ([1] or [n_draw]; n_jit = 0: none) and where its two extra sums go
+struct NoiseIn {
+  const double* mean;
+  const double* jit2;
+  int64_t n_mean, n_jit;
+  NoiseOut out;
 };
 
 // CHI2 (one planet, one sample per cadence): gflux is the observed series [n_cad], gsparse its weights ([1] or [n_cad],
@@ -2083,14 +2117,19 @@ constexpr int kJac = 16;
 __device__ __forceinline__ int jac_slot(int s) {   // LDS gradient column -> position in the row (-1: not kept)
   return s < G_PAD ? s : (s == G_SINI ? 9 : (s >= kNG && s < kNG + 6 ? 10 + (s - kNG) : -1));
 }
-template <bool GRAD, bool SECONDARY, bool LDELAY = false, bool CHI2 = false, bool TTV = false, bool JAC = false>
+// NOISE (CHI2 with a per-draw mean and jitter, exo_transit_noise[_ttv]_vjp_f64): gflux is the observed series y, gsparse
+// the VARIANCES ([1] or [n_cad]); the residual r = y - mean_d and the weight w = 1 / (var + jit2_d) are formed where CHI2
+// loads obs and ivar (mean_d, jit2_d: scalar registers), and the two extra sums go to the free limb-darkening slots 3 and 4.
+template <bool GRAD, bool SECONDARY, bool LDELAY = false, bool CHI2 = false, bool TTV = false, bool JAC = false, bool NOISE = false>
 __global__ __launch_bounds__(kBlock, LDELAY ? 2 : EXO_RUNS_MIN_WAVES) void transit_runs_kernel(
     const double* __restrict__ t, int64_t n_cad, const double* __restrict__ texp, int64_t n_texp,
     const double* __restrict__ stencil_dt, const double* __restrict__ stencil_w, int n_sub,
     const double* __restrict__ params, const double* __restrict__ ld, int n_planet, uint32_t flags, int n_ev, RunLists rl,
     const double* __restrict__ gflux, const double* __restrict__ gsparse, double* __restrict__ vals,
     int32_t* __restrict__ vcad, double* __restrict__ fill, double* __restrict__ partial, int64_t chi2_nw = 0,
-    Ttv ttv = Ttv{nullptr, nullptr, nullptr, 0}, FinishArgs fin = FinishArgs{nullptr, nullptr, nullptr, 0, nullptr}) {
+    Ttv ttv = Ttv{nullptr, nullptr, nullptr, 0}, FinishArgs fin = FinishArgs{nullptr, nullptr, nullptr, 0, nullptr},
+    NoiseIn nz = NoiseIn{nullptr, nullptr, 0, 0, NoiseOut{nullptr, nullptr}}) {
+  static_assert(!NOISE || (CHI2 && GRAD && !SECONDARY && !JAC), "the sampled-mean / jitter likelihood is a CHI2 sweep");
   __shared__ Shared sh;
   __shared__ Run s_run[kSeg];
   __shared__ int2 s_pre[kSeg + 1];   // positions of a batch's runs among its "inside" items (.x) and its limb items (.y)
@@ -2146,6 +2185,8 @@ __global__ __launch_bounds__(kBlock, LDELAY ? 2 : EXO_RUNS_MIN_WAVES) void trans
   for (int k = 0; k < 6; ++k) cld[k] = uniform((SECONDARY || k < 3) ? sh.c[k] : 0.0);
   const double te = (n_texp == 0) ? 0.0 : texp[0];
   const double sdt0 = uniform(sh.sdt[0]), sw0 = uniform(sh.sw[0]);
+  const double nz_mean = NOISE ? uniform(nz.mean[nz.n_mean == 1 ? 0 : draw]) : 0.0;
+  const double nz_jit2 = (NOISE && nz.n_jit > 0) ? uniform(nz.jit2[nz.n_jit == 1 ? 0 : draw]) : 0.0;
   for (int p = 0; p < n_planet; ++p) {
     const PlanetS c(sh.pc[p]);
     if (GRAD && p > 0) {
@@ -2236,6 +2277,11 @@ __global__ __launch_bounds__(kBlock, LDELAY ? 2 : EXO_RUNS_MIN_WAVES) void trans
           // position in the value array (transit_residual_kernel wrote it there)
           if (JAC) {
             it.g = (j < total) ? 1.0 : 0.0;   // unit cotangent: the row of derivatives itself
+          } else if (NOISE) {
+            if (j < total) {
+              it.g = gflux[it.i] - nz_mean;
+              it.w = exo::fast_rcp(gsparse[chi2_nw == 1 ? 0 : it.i] + nz_jit2);
+            }
           } else if (CHI2) {
             if (j < total) { it.g = gflux[it.i]; it.w = gsparse[chi2_nw == 1 ? 0 : it.i]; }
           } else if (GRAD && j < total)
@@ -2274,6 +2320,10 @@ __global__ __launch_bounds__(kBlock, LDELAY ? 2 : EXO_RUNS_MIN_WAVES) void trans
             if (CHI2) {
               const double r = F - cur.g;
               acc.add(kNG + 6, cur.w * (r * r - cur.g * cur.g));
+              if (NOISE) {
+                acc.add(kNG + 3, cur.w * F);
+                acc.add(kNG + 4, cur.w * cur.w * (r * r - cur.g * cur.g));
+              }
             } else if (GRAD && !JAC) {
               acc.add(kNG + 6, gw * F);
             }
@@ -2328,9 +2378,9 @@ __global__ __launch_bounds__(kBlock, LDELAY ? 2 : EXO_RUNS_MIN_WAVES) void trans
     // the block owns its draw (hb = 1): partials -> gradients, values -> their cadences -- what transit_finish_kernel does
     // otherwise, without its launch; a block barrier is all the hand-shake its own stores need
     __syncthreads();
-    finish_draw(draw, (GRAD && !JAC) ? partial : nullptr, hb, n_planet, SECONDARY, fin.gparams, fin.gld, fin.flux_dot, n_cad, flags, n_ev,
-                rl, vals, vcad, fill, nullptr, 0, nullptr,
-                (TTV && GRAD) ? ttv : Ttv{nullptr, nullptr, nullptr, 0});
+    finish_draw<NOISE>(draw, (GRAD && !JAC) ? partial : nullptr, hb, n_planet, SECONDARY, fin.gparams, fin.gld, fin.flux_dot, n_cad,
+                       flags, n_ev, rl, vals, vcad, fill, nullptr, 0, nullptr,
+                       (TTV && GRAD) ? ttv : Ttv{nullptr, nullptr, nullptr, 0}, 0, nz.out);
   }
 }
 
@@ -2407,18 +2457,25 @@ __global__ __launch_bounds__(kBlock) void transit_jac_vjp_kernel(int64_t n_cad, 
 // the value's own position, where the gradient sweep reads it) and the draw's chi^2 relative to an empty light curve,
 //     sum over solved cadences of  w_i ((total_i - obs_i)^2 - obs_i^2),
 // each cadence counted once (by the first list that holds it).  Block partials in a fixed order (bit-reproducible).
+// NOISE: obs is the series y and ivar holds the VARIANCES; r = y - mean_d, w = 1 / (var + jit2_d), and two more sums over the
+// same cadences: sum w total (row 1 of the block partials) and sum w^2 ((total - r)^2 - r^2) (row 2).
 constexpr int kResidualBlocks = 16;   // per draw
+template <bool NOISE = false>
 __global__ __launch_bounds__(kBlock) void transit_residual_kernel(int64_t n_cad, int n_planet, int n_ev, RunLists rl,
                                                                   const double* __restrict__ vals,
                                                                   const int32_t* __restrict__ vcad,
                                                                   const double* __restrict__ obs,
                                                                   const double* __restrict__ ivar, int64_t n_ivar,
                                                                   double* __restrict__ gvals,
-                                                                  double* __restrict__ chi2_part) {
-  __shared__ double red[kBlock];
+                                                                  double* __restrict__ chi2_part,
+                                                                  NoiseIn nz = NoiseIn{nullptr, nullptr, 0, 0,
+                                                                                       NoiseOut{nullptr, nullptr}}) {
+  __shared__ double red[NOISE ? 3 : 1][kBlock];
   const int64_t draw = blockIdx.y;
   const int nb = gridDim.x, n_lists = n_planet * n_ev;
-  double acc = 0.0;
+  double acc = 0.0, acc_m = 0.0, acc_j = 0.0;
+  const double nz_mean = NOISE ? nz.mean[nz.n_mean == 1 ? 0 : draw] : 0.0;
+  const double nz_jit2 = (NOISE && nz.n_jit > 0) ? nz.jit2[nz.n_jit == 1 ? 0 : draw] : 0.0;
   // value of list l2 at cadence i (0 if none of its runs holds it); `hit` says whether one does
   auto lookup = [&](int l2, int i, bool& hit) -> double {
     const int64_t list = draw * n_lists + l2;
@@ -2455,19 +2512,39 @@ __global__ __launch_bounds__(kBlock) void transit_residual_kernel(int64_t n_cad,
         tot += lookup(l2, i, hit);
         first = first && !(hit && l2 < l);
       }
-      const double o = obs[i], w = ivar[n_ivar == 1 ? 0 : i];
+      const double o = NOISE ? obs[i] - nz_mean : obs[i];
+      const double w = NOISE ? exo::fast_rcp(ivar[n_ivar == 1 ? 0 : i] + nz_jit2) : ivar[n_ivar == 1 ? 0 : i];
       const double r = tot - o;
       gvals[vbase + e] = 2.0 * w * r;
       if (first) acc += w * (r * r - o * o);
+      if (NOISE && first) {
+        acc_m += w * tot;
+        acc_j += w * w * (r * r - o * o);
+      }
     }
   }
-  red[threadIdx.x] = acc;
+  red[0][threadIdx.x] = acc;
+  if (NOISE) {
+    red[NOISE ? 1 : 0][threadIdx.x] = acc_m;
+    red[NOISE ? 2 : 0][threadIdx.x] = acc_j;
+  }
   __syncthreads();
   for (int m = kBlock / 2; m > 0; m >>= 1) {
-    if ((int)threadIdx.x < m) red[threadIdx.x] += red[threadIdx.x + m];
+    if ((int)threadIdx.x < m) {
+      red[0][threadIdx.x] += red[0][threadIdx.x + m];
+      if (NOISE) {
+        red[NOISE ? 1 : 0][threadIdx.x] += red[NOISE ? 1 : 0][threadIdx.x + m];
+        red[NOISE ? 2 : 0][threadIdx.x] += red[NOISE ? 2 : 0][threadIdx.x + m];
+      }
+    }
     __syncthreads();
   }
-  if (threadIdx.x == 0) chi2_part[draw * nb + blockIdx.x] = red[0];
+  if (threadIdx.x == 0) chi2_part[draw * nb + blockIdx.x] = red[0][0];
+  if (NOISE && threadIdx.x == 0) {
+    const int64_t n_draw = gridDim.y;
+    chi2_part[(n_draw + draw) * nb + blockIdx.x] = red[NOISE ? 1 : 0][0];
+    chi2_part[(2 * n_draw + draw) * nb + blockIdx.x] = red[NOISE ? 2 : 0][0];
+  }
 }
 
 // (the reference's standalone Ops -- kepler, quad_solution_vector, contact_points -- are exo_ops.hip)
@@ -2627,7 +2704,7 @@ inline RunWs carve_runs(void* base, int64_t n_cad, int64_t n_draw, int n_planet)
   w.off_vals = off; w.vals = (double*)(p + off); off = up16(off + 8 * n_draw * n_planet * n_cad);
   w.vcad = (int32_t*)(p + off); off = up16(off + 4 * n_draw * n_planet * n_cad);
   w.gvals = (double*)(p + off); off = up16(off + 8 * n_draw * n_planet * n_cad);
-  w.chi2_part = (double*)(p + off); off = up16(off + 8 * n_draw * kResidualBlocks);
+  w.chi2_part = (double*)(p + off); off = up16(off + 8 * n_draw * kResidualBlocks * 3);   // (the misfit; NOISE: + gmean, gjit2)
   w.done = (int32_t*)(p + off); off = up16(off + 4 * n_draw);
   w.bytes = off;
   return w;
@@ -2646,6 +2723,7 @@ struct Chi2Args {
   const double* ivar;
   int64_t n_ivar;
   double* chi2;
+  const NoiseIn* nz = nullptr;   // sampled mean / jitter: obs is the series y, ivar the VARIANCES
 };
 // the arguments of transit_runs_kernel that every launch of a sweep shares
 struct RunsCommon {
@@ -2664,6 +2742,13 @@ inline void launch_runs(const RunsCommon& a, const double* gflux, const double* 
   hipLaunchKernelGGL((transit_runs_kernel<G, SEC, LDELAY, CHI2, TTV, JAC>), a.grid, dim3(kBlock), 0, a.st, a.t, a.n_cad, a.texp,
                      a.n_texp, a.stencil_dt, a.stencil_w, a.n_sub, a.params, a.ld, a.n_planet, a.flags, a.n_ev, a.rl, gflux, gsparse,
                      vals, vcad, fill, partial, chi2_nw, a.ttv, fin);
+}
+// the single-pass likelihood with a sampled mean / jitter
+template <bool LDELAY, bool TTV>
+inline void launch_runs_noise(const RunsCommon& a, const Chi2Args& c, double* partial, const FinishArgs& fin) {
+  hipLaunchKernelGGL((transit_runs_kernel<true, false, LDELAY, true, TTV, false, true>), a.grid, dim3(kBlock), 0, a.st, a.t, a.n_cad,
+                     a.texp, a.n_texp, a.stencil_dt, a.stencil_w, a.n_sub, a.params, a.ld, a.n_planet, a.flags, a.n_ev, a.rl, c.obs,
+                     c.ivar, nullptr, nullptr, nullptr, partial, c.n_ivar, a.ttv, fin, *c.nz);
 }
 inline int launch_runs_sweep(const double* t, int64_t n_cad, const double* texp, int64_t n_texp, const double* stencil_dt,
                              const double* stencil_w, int32_t n_sub, const double* params, const double* ld,
@@ -2731,6 +2816,17 @@ inline int launch_runs_sweep(const double* t, int64_t n_cad, const double* texp,
   if (chi2 && n_planet == 1 && !secondary && n_sub == 1) {
     // one planet, one sample per cadence: the cotangent of a cadence's flux needs nothing but that flux -- value and
     // gradient in ONE evaluation per solved cadence (the misfit comes out of the "dot" slot of the partials)
+    if (chi2->nz) {
+      if (has_ttv) launch_runs_noise<false, true>(ra, *chi2, w.partial, fin);
+      else if (ldelay) launch_runs_noise<true, false>(ra, *chi2, w.partial, fin);
+      else launch_runs_noise<false, false>(ra, *chi2, w.partial, fin);
+      if (launch_status() != EXO_OK) return EXO_ERR_LAUNCH;
+      if (fold) return EXO_OK;
+      hipLaunchKernelGGL(transit_finish_noise_kernel, dim3((unsigned)n_draw), dim3(n_draw <= 256 ? 1024 : kBlock), 0, st, w.partial,
+                         w.hb, (int)n_planet, gparams, gld, chi2->chi2, n_cad, flags, n_ev, w.rl, w.vcad, nullptr, 0, nullptr, ra.ttv,
+                         chi2->nz->out);
+      return launch_status();
+    }
     if (has_ttv)
       launch_runs<true, false, false, true, true>(ra, chi2->obs, chi2->ivar, nullptr, nullptr, nullptr, w.partial, fin, chi2->n_ivar);
     else if (ldelay)
@@ -2747,8 +2843,12 @@ inline int launch_runs_sweep(const double* t, int64_t n_cad, const double* texp,
   if (has_ttv && chi2) {
     // value sweep into the sparse output, residuals + cotangents on it, gradient sweep reading them (gshift included)
     launch_runs<false, false, false, false, true>(ra, nullptr, nullptr, w.vals, w.vcad, nullptr, nullptr, no_fin);
-    hipLaunchKernelGGL(transit_residual_kernel, dim3(kResidualBlocks, (unsigned)n_draw), block, 0, st, n_cad, (int)n_planet,
-                       n_ev, w.rl, w.vals, w.vcad, chi2->obs, chi2->ivar, chi2->n_ivar, w.gvals, w.chi2_part);
+    if (chi2->nz)
+      hipLaunchKernelGGL(transit_residual_kernel<true>, dim3(kResidualBlocks, (unsigned)n_draw), block, 0, st, n_cad, (int)n_planet,
+                         n_ev, w.rl, w.vals, w.vcad, chi2->obs, chi2->ivar, chi2->n_ivar, w.gvals, w.chi2_part, *chi2->nz);
+    else
+      hipLaunchKernelGGL(transit_residual_kernel<>, dim3(kResidualBlocks, (unsigned)n_draw), block, 0, st, n_cad, (int)n_planet,
+                         n_ev, w.rl, w.vals, w.vcad, chi2->obs, chi2->ivar, chi2->n_ivar, w.gvals, w.chi2_part);
     launch_runs<true, false, false, false, true>(ra, nullptr, w.gvals, nullptr, nullptr, nullptr, w.partial, no_fin);
   } else if (has_ttv) {
     // (transits only, no light delay: runs_path)
@@ -2758,8 +2858,12 @@ inline int launch_runs_sweep(const double* t, int64_t n_cad, const double* texp,
       launch_runs<false, false, false, false, true>(ra, nullptr, nullptr, vals, fill ? w.vcad : nullptr, fill, nullptr, fin);
   } else if (chi2) {
     plain(std::false_type{}, nullptr, nullptr, w.vals, w.vcad, nullptr, nullptr, no_fin);
-    hipLaunchKernelGGL(transit_residual_kernel, dim3(kResidualBlocks, (unsigned)n_draw), block, 0, st, n_cad, (int)n_planet,
-                       n_ev, w.rl, w.vals, w.vcad, chi2->obs, chi2->ivar, chi2->n_ivar, w.gvals, w.chi2_part);
+    if (chi2->nz)
+      hipLaunchKernelGGL(transit_residual_kernel<true>, dim3(kResidualBlocks, (unsigned)n_draw), block, 0, st, n_cad, (int)n_planet,
+                         n_ev, w.rl, w.vals, w.vcad, chi2->obs, chi2->ivar, chi2->n_ivar, w.gvals, w.chi2_part, *chi2->nz);
+    else
+      hipLaunchKernelGGL(transit_residual_kernel<>, dim3(kResidualBlocks, (unsigned)n_draw), block, 0, st, n_cad, (int)n_planet,
+                         n_ev, w.rl, w.vals, w.vcad, chi2->obs, chi2->ivar, chi2->n_ivar, w.gvals, w.chi2_part);
     plain(std::true_type{}, nullptr, w.gvals, nullptr, nullptr, nullptr, w.partial, no_fin);
   } else if (gvals) {
     // (the values stay as the forward sweep left them: the GP's reverse pass has read them, nobody reads them again)
@@ -2777,6 +2881,12 @@ inline int launch_runs_sweep(const double* t, int64_t n_cad, const double* texp,
   }
   if (launch_status() != EXO_OK) return EXO_ERR_LAUNCH;
   const bool three_sweeps = chi2 != nullptr;   // (the single-pass likelihood returned above)
+  if (chi2 && chi2->nz) {
+    hipLaunchKernelGGL(transit_finish_noise_kernel, dim3((unsigned)n_draw), dim3(n_draw <= 256 ? 1024 : kBlock), 0, st, w.partial, w.hb,
+                       (int)n_planet, gparams, gld, (double*)nullptr, n_cad, flags, n_ev, w.rl, w.vcad, w.chi2_part, kResidualBlocks,
+                       chi2->chi2, ra.ttv, chi2->nz->out);
+    return launch_status();
+  }
   if ((grad || fill) && (!fold || three_sweeps))
     hipLaunchKernelGGL(transit_finish_kernel, dim3((unsigned)n_draw), dim3(n_draw <= 256 ? 1024 : kBlock), 0, st,
                        grad ? w.partial : nullptr, w.hb, (int)n_planet, secondary, gparams, gld, flux_dot, n_cad, flags, n_ev,
@@ -3577,6 +3687,65 @@ int exo_transit_chi2_ttv_vjp_f64(const double* t, int64_t n_cad, const double* t
   hipStream_t st = (hipStream_t)stream;
   if (!exo::zero_fill_async(gshift, (int64_t)(n_draw * n_planet * (n_edge + 1)), st)) return EXO_ERR_LAUNCH;
   const Chi2Args c2{obs, ivar, n_ivar, chi2};
+  const Ttv ttv{ttv_edges, ttv_shift, gshift, n_edge};
+  return launch_runs_sweep(t, n_cad, texp, n_texp, stencil_dt, stencil_w, n_sub, params, ld, n_draw, n_planet, flags, nullptr,
+                           nullptr, gparams, gld, nullptr, rw, st, &c2, &ttv);
+}
+
+// the two likelihood entries with a sampled mean and a jitter: the checks of the chi2 entries, plus the new arrays
+static bool noise_args_ok(int64_t n_cad, int64_t n_draw, const double* y, const double* var, int64_t n_var, const double* mean,
+                          int64_t n_mean, const double* jit2, int64_t n_jit, const double* gmean, const double* gjit2) {
+  if ((n_var != 1 && n_var != n_cad) || (n_mean != 1 && n_mean != n_draw) || (n_jit != 0 && n_jit != 1 && n_jit != n_draw))
+    return false;
+  if (n_draw == 0) return true;
+  return var && mean && gmean && gjit2 && (n_cad == 0 || y) && (n_jit == 0 || jit2);
+}
+
+int exo_transit_noise_vjp_f64(const double* t, int64_t n_cad, const double* texp, int64_t n_texp, const double* stencil_dt,
+                              const double* stencil_w, int32_t n_sub, const double* params, const double* ld,
+                              int64_t n_draw, int32_t n_planet, uint32_t flags, const double* y, const double* var,
+                              int64_t n_var, const double* mean, int64_t n_mean, const double* jit2, int64_t n_jit,
+                              double* chi2, double* gmean, double* gjit2, double* gparams, double* gld, void* workspace,
+                              int64_t workspace_bytes, void* stream) {
+  if (!transit_args_ok(n_cad, n_texp, n_sub, n_draw, n_planet) || !sweep_flags_ok(flags) ||
+      !noise_args_ok(n_cad, n_draw, y, var, n_var, mean, n_mean, jit2, n_jit, gmean, gjit2))
+    return EXO_ERR_INVALID_ARGUMENT;
+  if (flags & (EXO_FLAG_PER_PLANET | EXO_FLAG_SPARSE | EXO_FLAG_EXACT_SCAN)) return EXO_ERR_INVALID_ARGUMENT;
+  if (n_draw == 0) return EXO_OK;
+  if (!params || !ld || !chi2 || !gparams || !gld || (n_cad > 0 && !t) || (n_texp > 0 && (!texp || !stencil_dt || !stencil_w)))
+    return EXO_ERR_INVALID_ARGUMENT;
+  if (!runs_path(false, n_texp, flags)) return EXO_ERR_INVALID_ARGUMENT;   // one exposure time (or none) for all cadences
+  const RunWs rw = carve_runs(workspace, n_cad, n_draw, n_planet);
+  if (!workspace || workspace_bytes < rw.bytes) return EXO_ERR_WORKSPACE;
+  const NoiseIn nz{mean, jit2, n_mean, n_jit, NoiseOut{gmean, gjit2}};
+  const Chi2Args c2{y, var, n_var, chi2, &nz};
+  return launch_runs_sweep(t, n_cad, texp, n_texp, stencil_dt, stencil_w, n_sub, params, ld, n_draw, n_planet, flags, nullptr,
+                           nullptr, gparams, gld, nullptr, rw, (hipStream_t)stream, &c2);
+}
+
+int exo_transit_noise_ttv_vjp_f64(const double* t, int64_t n_cad, const double* texp, int64_t n_texp, const double* stencil_dt,
+                                  const double* stencil_w, int32_t n_sub, const double* params, const double* ld,
+                                  int64_t n_draw, int32_t n_planet, uint32_t flags, const double* ttv_edges,
+                                  const double* ttv_shift, int32_t n_edge, const double* y, const double* var, int64_t n_var,
+                                  const double* mean, int64_t n_mean, const double* jit2, int64_t n_jit, double* chi2,
+                                  double* gmean, double* gjit2, double* gparams, double* gld, double* gshift, void* workspace,
+                                  int64_t workspace_bytes, void* stream) {
+  if (!transit_args_ok(n_cad, n_texp, n_sub, n_draw, n_planet) || n_cad < 1 || !sweep_flags_ok(flags) ||
+      !noise_args_ok(n_cad, n_draw, y, var, n_var, mean, n_mean, jit2, n_jit, gmean, gjit2))
+    return EXO_ERR_INVALID_ARGUMENT;
+  if (flags & (EXO_FLAG_PER_PLANET | EXO_FLAG_SPARSE | EXO_FLAG_EXACT_SCAN | EXO_FLAG_SECONDARY | EXO_FLAG_LIGHT_DELAY))
+    return EXO_ERR_INVALID_ARGUMENT;
+  if (!ttv_args_ok(ttv_edges, ttv_shift, n_edge) || !gshift) return EXO_ERR_INVALID_ARGUMENT;
+  if (n_draw == 0) return EXO_OK;
+  if (!params || !ld || !chi2 || !gparams || !gld || !t || (n_texp > 0 && (!texp || !stencil_dt || !stencil_w)))
+    return EXO_ERR_INVALID_ARGUMENT;
+  if (!runs_path(true, n_texp, flags)) return EXO_ERR_INVALID_ARGUMENT;   // one exposure time (or none) for all cadences
+  const RunWs rw = carve_runs(workspace, n_cad, n_draw, n_planet);
+  if (!workspace || workspace_bytes < rw.bytes) return EXO_ERR_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  if (!exo::zero_fill_async(gshift, (int64_t)(n_draw * n_planet * (n_edge + 1)), st)) return EXO_ERR_LAUNCH;
+  const NoiseIn nz{mean, jit2, n_mean, n_jit, NoiseOut{gmean, gjit2}};
+  const Chi2Args c2{y, var, n_var, chi2, &nz};
   const Ttv ttv{ttv_edges, ttv_shift, gshift, n_edge};
   return launch_runs_sweep(t, n_cad, texp, n_texp, stencil_dt, stencil_w, n_sub, params, ld, n_draw, n_planet, flags, nullptr,
                            nullptr, gparams, gld, nullptr, rw, st, &c2, &ttv);

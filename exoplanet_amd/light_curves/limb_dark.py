@@ -229,16 +229,21 @@ class LimbDarkLightCurve:
         return flux.reshape(tuple(batch) + (t.shape[0], rec.shape[1]))
 
     def white_noise_log_likelihood(self, orbit=None, r=None, t=None, y=None, yerr=None, mean=0.0, texp=None, oversample=7,
-                                   order=0, use_in_transit=False, light_delay=False):
+                                   order=0, use_in_transit=False, light_delay=False, jitter=None):
         """Gaussian log-likelihood (one value per draw) of the observed series ``y`` with independent errors ``yerr``
         given ``mean + sum over planets of get_light_curve(...)`` -- what the reference's tutorials write as
         ``pm.Normal("obs", mu=mean + pt.sum(light_curves, axis=-1), sigma=yerr, observed=y)`` -- for a KeplerianOrbit
         or a TTVOrbit (gradients to its transit times / offsets included) with sorted times and one exposure time: value and gradient in ONE call on the sparse light curve
         (ops.transit_chi2), no (draws, cadences) array anywhere.  ``yerr``: a number, one value per cadence, or PER DRAW
-        (a 0-d or (draws, 1) tensor, differentiable: a jitter term sampled per chain costs nothing extra).  Whatever
-        the fused form cannot differentiate -- a per-cadence ``yerr``, a ``mean`` or a ``y`` that requires grad, a
-        ``mean`` per draw -- takes the dense light curve (``get_light_curve(total=True)``) and torch: slower, never a
-        partial gradient."""
+        (a 0-d or (draws, 1) tensor, differentiable: a jitter term sampled per chain costs nothing extra).
+        ``mean``: a number or PER DRAW (a 0-d, (draws,) or (draws, 1) tensor); ``jitter``: None, a number or per draw
+        likewise, added to ``yerr`` -- a number or per cadence -- in quadrature, ``sigma = sqrt(yerr**2 + jitter**2)``.
+        Both are differentiable and both stay fused: the tutorials' ``mean = pm.Normal("mean", ...)`` and
+        ``sigma = sqrt(yerr**2 + exp(2 * log_jitter))`` cost the sweep two more sums per draw and one pass over the data
+        terms (ops.white_noise_loglike), still without a (draws, cadences) array.  Draw counts of the parameters, ``mean``
+        and ``jitter`` that do not agree raise a ValueError.  What the fused form cannot differentiate -- a ``y`` or a
+        per-cadence ``yerr`` that requires grad -- takes the dense light curve (``get_light_curve(total=True)``) and
+        torch: slower, never a partial gradient."""
         from ..orbits.keplerian import KeplerianOrbit
 
         if orbit is None or r is None or t is None or y is None or yerr is None:
@@ -246,11 +251,15 @@ class LimbDarkLightCurve:
         needs = lambda x: isinstance(x, torch.Tensor) and x.requires_grad and torch.is_grad_enabled()  # noqa: E731
         n_cad = as_tensor(t).numel()
         per_draw = ops.per_draw_yerr(yerr, n_cad) is not None
-        if needs(y) or needs(mean) or (needs(yerr) and not per_draw) or (isinstance(mean, torch.Tensor) and mean.numel() > 1):
+        if needs(y) or (needs(yerr) and not per_draw):
             lc = self.get_light_curve(orbit=orbit, r=r, t=t, texp=texp, oversample=oversample, order=order,
                                       use_in_transit=use_in_transit, light_delay=light_delay, total=True)
-            resid = as_tensor(y, lc).to(lc.device) - mean - lc
+            # (a (draws,) mean / jitter is per draw, as on the fused route: a column against the (draws, cadences) curve)
+            col = lambda x: x.reshape(-1, 1) if isinstance(x, torch.Tensor) and x.dim() == 1 and x.numel() > 1 else x  # noqa: E731
+            resid = as_tensor(y, lc).to(lc.device) - col(mean) - lc
             w = as_tensor(yerr, lc).to(lc.device) ** -2
+            if jitter is not None:
+                w = 1.0 / (1.0 / w + as_tensor(col(jitter), lc).to(lc.device) ** 2)
             lognorm = torch.log(w / (2.0 * math.pi))
             lognorm = lognorm.sum(-1) if (lognorm.dim() and lognorm.shape[-1] == n_cad) else lognorm.reshape(lognorm.shape[:-1] if lognorm.dim() else ()) * float(n_cad)
             return -0.5 * (w * resid * resid).sum(-1) + 0.5 * lognorm
@@ -260,7 +269,13 @@ class LimbDarkLightCurve:
         if has_ttv and light_delay:
             raise NotImplementedError("white_noise_log_likelihood: no light delay together with timing variations")
         t = as_tensor(t, r if isinstance(r, torch.Tensor) else self.u1)
-        fused = self._loglike_from_columns(orbit, r, t, y, yerr, mean, texp, oversample, order, use_in_transit, light_delay, has_ttv)
+        # draws of a sampled mean / jitter and of the per-draw error bars that go with them (one system with many of
+        # them: the parameters are repeated)
+        n_noise = 1
+        if ops.sampled_noise(mean, jitter):
+            n_noise = max([x.numel() for x in (mean, jitter, ops.per_draw_yerr(yerr, n_cad)) if isinstance(x, torch.Tensor)] + [1])
+        fused = self._loglike_from_columns(orbit, r, t, y, yerr, mean, texp, oversample, order, use_in_transit, light_delay, has_ttv,
+                                           jitter, n_noise)
         if fused is not None:
             return fused
         rec, ld, batch, flags = orbit.kernel_inputs(r, (self.u1, self.u2), use_in_transit=use_in_transit,
@@ -281,15 +296,23 @@ class LimbDarkLightCurve:
             kw["ttv"] = (edges.expand(full + edges.shape[-2:]).reshape(-1, P, edges.shape[-1]).contiguous(),
                          shift.expand(full + shift.shape[-2:]).reshape(-1, P, shift.shape[-1]).contiguous())
             rec, ld, batch = rec.contiguous(), ld.contiguous(), full
-        ll = ops.white_noise_loglike(t.detach(), rec, ld, as_tensor(y, t).to(rec.device), yerr, mean=mean, flags=flags, **kw)
+        if rec.shape[0] == 1 and n_noise > 1:
+            rec, ld, batch = rec.expand(n_noise, -1, -1).contiguous(), ld.expand(n_noise, -1).contiguous(), (n_noise,)
+            if has_ttv:
+                kw["ttv"] = tuple(x.expand(n_noise, -1, -1).contiguous() for x in kw["ttv"])
+        ll = ops.white_noise_loglike(t.detach(), rec, ld, as_tensor(y, t).to(rec.device), yerr, mean=mean, flags=flags,
+                                     jitter=jitter, **kw)
         return _batch_shape(ll, batch, bool(batch))
 
-    def _loglike_from_columns(self, orbit, r, t, y, yerr, mean, texp, oversample, order, use_in_transit, light_delay, has_ttv):
+    def _loglike_from_columns(self, orbit, r, t, y, yerr, mean, texp, oversample, order, use_in_transit, light_delay, has_ttv,
+                              jitter=None, n_noise=1):
         """white_noise_log_likelihood of the standard parameterisation with the constructor arguments handed to the
         kernels as they are (ops.orbit_white_noise_loglike: packing, misfit + gradient, packing VJP with the
         likelihood's cotangent folded in); None when that form does not apply"""
-        if not getattr(orbit, "_standard", False) or not t.is_cuda or not isinstance(mean, (int, float)):
+        if not getattr(orbit, "_standard", False) or not t.is_cuda:
             return None
+        if not isinstance(mean, (int, float)) and not ops.sampled_noise(mean, jitter):
+            return None      # a one-element tensor that is a constant: the record form, as ever
         A = orbit._args
         like = next((x for x in list(A.values()) + [r] if isinstance(x, torch.Tensor)), None)
         got = orbit._standard_cols(r, (self.u1, self.u2), None, like)
@@ -307,6 +330,10 @@ class LimbDarkLightCurve:
             D = max(D, Dt)
             batched = batched or edges.dim() == 3
             kw["ttv"] = (edges.expand((D,) + tuple(edges.shape[-2:])).contiguous(), shift.expand((D,) + tuple(shift.shape[-2:])).contiguous())
+        if D == 1 and n_noise > 1:
+            D, batched = n_noise, True
+            if has_ttv:
+                kw["ttv"] = tuple(x.expand(D, -1, -1).contiguous() for x in kw["ttv"])
         if texp is not None:
             dt, w = exposure_stencil(oversample, order)
             kw.update(texp=as_tensor(texp, t).reshape(-1).detach(), stencil_dt=_on_device(dt, t.device),
@@ -314,7 +341,8 @@ class LimbDarkLightCurve:
         flags = (ops.FLAG_WINDOW if use_in_transit else 0) | (ops.FLAG_LIGHT_DELAY if light_delay else 0)
         pack_flags = (flags & ops.FLAG_WINDOW) | (ops.PACK_CIRCULAR if A["ecc"] is None else 0)
         yt = as_tensor(y, t).to(t.device)
-        ll = ops.orbit_white_noise_loglike(t.detach(), yt, yerr, cols, us, D, mean=mean, flags=flags, pack_flags=pack_flags, **kw)
+        ll = ops.orbit_white_noise_loglike(t.detach(), yt, yerr, cols, us, D, mean=mean, flags=flags, pack_flags=pack_flags,
+                                           jitter=jitter, **kw)
         return ll if batched else _batch_shape(ll, (), False)
 
     # ---- generic orbit objects: ops.quad_solution_vector on their positions

@@ -742,14 +742,203 @@ def _scaled_loglike(unit_fn, y, yerr_d, mean):
     return -0.5 * w * (chi2 + s2) + 0.5 * n * torch.log(w / (2.0 * torch.pi))
 
 
-def white_noise_loglike(t, params, ld, y, yerr, mean=0.0, texp=None, stencil_dt=None, stencil_w=None, flags=0, ttv=None):
+# sampled mean / jitter: (series, error bars) -> variances and the per-series sums of the data terms.  Like _WN_CACHE's
+# residuals and weights, the variances of an entry live as long as the entry (or the caller's own tensors) does: a captured
+# graph that read them must not be replayed after the entry is gone.  The per-series sums (64 B) outlive the entry once a
+# graph holds their address: a capture after a warm-up reads the sums the warm-up filled and pins them in _NZ_PINNED; a
+# capture without one gets a buffer from the graph's own pool and fills it on every replay.
+_NZ_CACHE = {}
+_NZ_PINNED = {}
+_NOISE_SERIES = 8   # doubles of exo_white_noise_terms_f64's `series`
+_LOG_2PI = 1.8378770664093453
+
+
+class _NoiseData:
+    """what depends on (y, yerr) alone: the variances yerr^2 ((1,) or (n_cad,)) and the buffer of per-series sums that
+    exo_white_noise_terms_f64 fills on its first eager call on a stream and reads in every later call on THAT stream
+    (one buffer per stream: a call on another stream never reads sums that are still being written)"""
+
+    def __init__(self, y, yerr, var):
+        self.y, self.yerr, self.var = y, yerr, var
+        self.series = {}     # stream -> filled buffer
+
+
+def _noise_data(y, yerr):
+    """the :class:`_NoiseData` of a series and its error bars (a number or a per-cadence tensor), kept per (y, yerr) like
+    :func:`_white_noise_terms` keeps its constants: a sampler calls with the same series thousands of times"""
+    number = isinstance(yerr, (int, float))
+    key = (id(y), y._version, float(yerr) if number else (id(yerr), yerr._version))
+    hit = _NZ_CACHE.get(key)
+    if hit is not None and hit.y is y and (number or hit.yerr is yerr):
+        return hit
+    if number:
+        var = _const(float(yerr) * float(yerr), y.device)
+    else:
+        yerr = _dev(yerr, "yerr")
+        var = (yerr * yerr).reshape(-1)
+        if var.numel() not in (1, y.numel()):
+            raise ValueError("yerr must be a number, one entry per cadence, or per draw: (n_draw, 1)")
+    hit = _NoiseData(y, yerr, var)
+    if len(_NZ_CACHE) >= 4:      # (an entry keeps y and its variances alive: a few series at most)
+        _NZ_CACHE.clear()
+    _NZ_CACHE[key] = hit
+    return hit
+
+
+def _per_draw(x, name, D, device):
+    """``x`` (a number, or a 0-d / (D,) / (D, 1) / (1, 1) tensor) as a (1,) or (D,) tensor"""
+    if isinstance(x, (int, float)):
+        return _const(x, device)
+    x = _dev(x, name).reshape(-1).contiguous()
+    if x.numel() not in (1, D):
+        raise ValueError(f"white-noise likelihood: `{name}` holds {x.numel()} draws, the parameters {D} -- one value, or one per draw")
+    return x
+
+
+def _noise_launch(a, flags, ttv_edges, ttv_shift, data, var, mean, jit2):
+    """exo_transit_noise[_ttv]_vjp_f64 + exo_white_noise_terms_f64 -> (loglike (D,), d/dmean (D,), d/djit2 (D,), gparams and
+    gld of the MISFIT (d loglike = -1/2 of them), gshift | None)"""
+    flags |= _sorted_flag(a.t)
+    edges, shift, n_edge = a.ttv(None if ttv_edges is None else (ttv_edges, ttv_shift))
+    dev = a.t.device
+    y = data.y
+    ws, nbytes = _workspace(a.N, a.D, a.P, dev)
+    sums = torch.empty(3, a.D, dtype=torch.float64, device=dev)          # chi2, gmean, gjit2
+    gparams = torch.empty_like(a.params)
+    gld = torch.empty_like(a.ld)
+    gshift = torch.empty_like(shift) if n_edge else None
+    n_jit = 0 if jit2 is None else jit2.numel()
+    noise = (_ptr(y), _ptr(var), var.numel(), _ptr(mean), mean.numel(), _ptr(jit2), n_jit,
+             _ptr(sums[0]), _ptr(sums[1]), _ptr(sums[2]), _ptr(gparams), _ptr(gld))
+    tail = (_ptr(ws), nbytes, _stream(a.t))
+    if n_edge:
+        _call("exo_transit_noise_ttv_vjp_f64", dev, *a.head(flags), _ptr(edges), _ptr(shift), n_edge, *noise, _ptr(gshift), *tail)
+    else:
+        _call("exo_transit_noise_vjp_f64", dev, *a.head(flags), *noise, *tail)
+    # the sums over all cadences: per-series sums once per (y, yerr) and stream where the weight separates (see _NZ_CACHE)
+    separable = n_jit == 0 or var.numel() == 1
+    terms = torch.empty(5, a.D, dtype=torch.float64, device=dev)
+    tws, tbytes = None, 0
+    if not separable:
+        tbytes = int(_lib.load().exo_white_noise_workspace_bytes(a.N, a.D))
+        tws = torch.empty(tbytes // 8, dtype=torch.float64, device=dev)
+    stream = _stream(a.t)
+    capturing = torch.cuda.is_current_stream_capturing()
+    keep = separable and data.var is var
+    series = None
+    if keep and capturing:
+        # sums that an eager call (the warm-up) filled before the capture began -- torch.cuda.graph waits for the device on
+        # entry -- pinned for good: the graph holds their address
+        series = next(iter(data.series.values()), None)
+        if series is not None:
+            _NZ_PINNED[series.data_ptr()] = series
+    elif keep:
+        series = data.series.get(stream)
+    ready = series is not None
+    if not ready:
+        series = torch.empty(_NOISE_SERIES, dtype=torch.float64, device=dev)
+    _call("exo_white_noise_terms_f64", dev, _ptr(y), _ptr(var), a.N, var.numel(), _ptr(mean), mean.numel(), _ptr(jit2), n_jit, a.D,
+          _ptr(series), 1 if ready else 0, _ptr(terms), _ptr(tws), tbytes, stream)
+    if keep and not ready and not capturing:
+        data.series[stream] = series
+    ll = torch.add(terms[0] + terms[1], sums[0]).mul_(-0.5).sub_(0.5 * a.N * _LOG_2PI)
+    dmean = terms[2] - sums[1]
+    djit2 = (terms[3] + sums[2] - terms[4]).mul_(0.5)
+    return ll, dmean, djit2, gparams, gld, gshift
+
+
+def _refuse_data_grads(ctx, first, names):
+    for k, name in enumerate(names):
+        if ctx.needs_input_grad[first + k]:
+            raise NotImplementedError(
+                f"white-noise likelihood: `{name}` requires grad, and the fused kernels differentiate the orbit, the limb "
+                "darkening, `mean` and `jitter` only; use get_light_curve(total=True) with torch")
+
+
+def _draw_cotangent(g, n):
+    """cotangent of a (1,) or (D,) per-draw input from its per-draw contributions"""
+    return g.sum().reshape(1) if n == 1 and g.numel() != 1 else g
+
+
+class _TransitNoise(torch.autograd.Function):
+    """White-noise log-likelihood with a per-draw mean and jitter (``jit2`` = jitter^2, or None): value and every gradient
+    from one pass of the sweep (exo_transit_noise[_ttv]_vjp_f64) and the data terms (exo_white_noise_terms_f64)."""
+
+    @staticmethod
+    def forward(ctx, t, texp, stencil_dt, stencil_w, params, ld, data, var, mean, jit2, flags, ttv_edges, ttv_shift):
+        _refuse_data_grads(ctx, 7, ("yerr",))
+        a = _transit_args(t, texp, stencil_dt, stencil_w, params, ld, flags)
+        ll, dmean, djit2, gparams, gld, gshift = _noise_launch(a, flags, ttv_edges, ttv_shift, data, var, mean, jit2)
+        ctx.n_mean, ctx.n_jit = mean.numel(), 0 if jit2 is None else jit2.numel()
+        ctx.save_for_backward(gparams, gld, dmean, djit2, *([] if gshift is None else [gshift]))
+        return ll
+
+    @staticmethod
+    def backward(ctx, gll):
+        gparams, gld, dmean, djit2, *rest = ctx.saved_tensors
+        half = -0.5 * gll
+        gshift = half[:, None, None] * rest[0] if rest else None
+        gjit2 = _draw_cotangent(gll * djit2, ctx.n_jit) if ctx.n_jit else None
+        return (None, None, None, None, half[:, None, None] * gparams, half[:, None] * gld, None, None,
+                _draw_cotangent(gll * dmean, ctx.n_mean), gjit2, None, None, gshift)
+
+
+def sampled_noise(mean, jitter):
+    """whether (``mean``, ``jitter``) take the sampled-mean / jitter kernels: any jitter, a per-draw ``mean``, a ``mean``
+    that requires grad.  A number, and a one-element tensor that is a constant of the call, stay where they always went
+    (:func:`_white_noise_terms`, :func:`_scaled_loglike`): same launches, same bits as before those kernels existed."""
+    if jitter is not None:
+        return True
+    return isinstance(mean, torch.Tensor) and (mean.numel() > 1 or (mean.requires_grad and torch.is_grad_enabled()))
+
+
+def _noise_inputs(y, yerr, mean, jitter, D):
+    """(data, var, mean, jit2) of the sampled-mean / jitter likelihood for ``D`` draws: a per-draw ``yerr`` is a jitter on
+    top of a zero variance"""
+    for name, x in (("y", y), ("yerr", yerr)):
+        if isinstance(x, torch.Tensor) and x.requires_grad and torch.is_grad_enabled() and (name == "y" or per_draw_yerr(x, y.numel()) is None):
+            raise NotImplementedError(
+                f"white-noise likelihood: `{name}` requires grad, and the fused kernels differentiate the orbit, the limb "
+                "darkening, `mean`, `jitter` and per-draw error bars only; use LimbDarkLightCurve.white_noise_log_likelihood "
+                "(it falls back to the dense light curve) or get_light_curve(total=True) with torch")
+    dev = y.device
+    mean = _per_draw(mean, "mean", D, dev)
+    jit2 = None
+    if jitter is not None:
+        jit2 = _per_draw(jitter, "jitter", D, dev)
+        jit2 = jit2 * jit2 if isinstance(jitter, torch.Tensor) else _const(float(jitter) ** 2, dev)
+    yd = per_draw_yerr(yerr, y.numel())
+    if yd is not None:
+        yd = _per_draw(yd, "yerr", D, dev)
+        jit2 = yd * yd if jit2 is None else yd * yd + jit2
+        data = _noise_data(y, 0.0)
+    else:
+        data = _noise_data(y, yerr)
+    return data, data.var, mean, jit2
+
+
+def white_noise_loglike(t, params, ld, y, yerr, mean=0.0, texp=None, stencil_dt=None, stencil_w=None, flags=0, ttv=None,
+                        jitter=None):
     """Gaussian log-likelihood (n_draw,) of the observed series ``y`` with independent errors ``yerr`` (a number, a
     per-cadence vector, or PER DRAW: a 0-d / (n_draw, 1) tensor, differentiable -- a jitter term sampled per chain)
     given ``mean + light curve`` -- the reference's ``pm.Normal("obs", mu=mean + lc, sigma=yerr, observed=y)`` for a
-    batch of parameter sets, value and gradient in one call (:func:`transit_chi2`).  ``y``, a per-cadence ``yerr`` and
-    ``mean`` are data here: a tensor among them that requires grad is refused, not silently dropped."""
+    batch of parameter sets, value and gradient in one call (:func:`transit_chi2`).
+
+    ``mean``: a number, or PER DRAW -- a 0-d, (n_draw,) or (n_draw, 1) tensor -- and ``jitter`` (None, a number or per
+    draw likewise), added to ``yerr`` in quadrature: ``sigma = sqrt(yerr**2 + jitter**2)``.  Both are differentiable and
+    stay on the sparse light curve (exo_transit_noise_vjp_f64 + exo_white_noise_terms_f64): the reference's
+    ``pm.Normal("obs", mu=mean + lc, sigma=sqrt(yerr**2 + exp(2 * log_jitter)), observed=y)`` with ``mean`` and
+    ``log_jitter`` sampled.  ``y`` and a per-cadence ``yerr`` are data: one that requires grad is refused, not silently
+    dropped."""
     y = _dev(y, "y")
     kw = dict(texp=texp, stencil_dt=stencil_dt, stencil_w=stencil_w, flags=flags, ttv=ttv)
+    if sampled_noise(mean, jitter):
+        params = _dev(params, "params")
+        if tuple(y.shape) != (_dev(t, "t").numel(),):
+            raise ValueError("y must have shape (n_cad,)")
+        data, var, mean, jit2 = _noise_inputs(y, yerr, mean, jitter, params.shape[0])
+        edges, shift = (None, None) if ttv is None else ttv
+        return _TransitNoise.apply(t, texp, stencil_dt, stencil_w, params, ld, data, var, mean, jit2, int(flags), edges, shift)
     yd = per_draw_yerr(yerr, y.numel())
     if yd is not None:
         return _scaled_loglike(lambda obs, one: transit_chi2(t, params, ld, obs, one, **kw), y, _dev(yd, "yerr"), mean)
@@ -1731,16 +1920,51 @@ class _OrbitLoglike(torch.autograd.Function):
         return (None,) * 11 + (None, gshift) + tuple(grads)
 
 
+class _OrbitNoiseLoglike(torch.autograd.Function):
+    """:class:`_OrbitLoglike` with a per-draw mean and jitter: column-form packing, the sweep and the data terms of
+    :class:`_TransitNoise`, and -- backward -- the packing VJP with the likelihood's cotangent folded in."""
+
+    @staticmethod
+    def forward(ctx, t, texp, stencil_dt, stencil_w, data, var, mean, jit2, flags, pack_flags, n_ld, n_draw, ttv_edges, ttv_shift,
+                *cols):
+        _refuse_data_grads(ctx, 5, ("yerr",))
+        params, ld, keep, meta = _pack_cols_forward(cols, n_ld, n_draw, pack_flags)
+        a = _transit_args(t, texp, stencil_dt, stencil_w, params, ld, flags)
+        ll, dmean, djit2, gparams, gld, gshift = _noise_launch(a, flags, ttv_edges, ttv_shift, data, var, mean, jit2)
+        ctx.meta = meta
+        ctx.n_keep = len(keep)
+        ctx.n_mean, ctx.n_jit = mean.numel(), 0 if jit2 is None else jit2.numel()
+        ctx.save_for_backward(gparams, gld, dmean, djit2, *keep, *([] if gshift is None else [gshift]))
+        return ll
+
+    @staticmethod
+    def backward(ctx, gll):
+        saved = ctx.saved_tensors
+        gparams, gld, dmean, djit2, keep = saved[0], saved[1], saved[2], saved[3], saved[4:4 + ctx.n_keep]
+        gll = _dev(gll, "gll")
+        gscale = -0.5 * gll
+        nfix = 14
+        grads = _pack_cols_backward(keep, ctx.meta, gparams, gld, gscale, ctx.needs_input_grad[nfix:])
+        gshift = gscale[:, None, None] * saved[4 + ctx.n_keep] if len(saved) > 4 + ctx.n_keep else None
+        gjit2 = _draw_cotangent(gll * djit2, ctx.n_jit) if ctx.n_jit else None
+        return (None,) * 6 + (_draw_cotangent(gll * dmean, ctx.n_mean), gjit2) + (None,) * 5 + (gshift,) + tuple(grads)
+
+
 def orbit_white_noise_loglike(t, y, yerr, orbit_cols, ld_cols, n_draw, mean=0.0, flags=0, pack_flags=0, texp=None,
-                              stencil_dt=None, stencil_w=None, ttv=None):
+                              stencil_dt=None, stencil_w=None, ttv=None, jitter=None):
     """:func:`white_noise_loglike` for orbits in the standard parameterisation given column by column (the EXO_IN_*
-    inputs of :func:`pack_records_cols`): Gaussian log-likelihood (n_draw,), differentiable w.r.t. every column and the
-    timing shifts, value and gradient in seven launches."""
+    inputs of :func:`pack_records_cols`): Gaussian log-likelihood (n_draw,), differentiable w.r.t. every column, the
+    timing shifts, a per-draw ``mean`` and ``jitter``, value and gradient in seven launches (nine with the data terms of
+    a sampled mean / jitter)."""
     t = _dev(t, "t")
     y = _dev(y, "y")
     if tuple(y.shape) != (t.numel(),):
         raise ValueError("y must have shape (n_cad,)")
     edges, shift = (None, None) if ttv is None else ttv
+    if sampled_noise(mean, jitter):
+        data, var, mean, jit2 = _noise_inputs(y, yerr, mean, jitter, int(n_draw))
+        return _OrbitNoiseLoglike.apply(t, texp, stencil_dt, stencil_w, data, var, mean, jit2, int(flags), int(pack_flags),
+                                        len(ld_cols), int(n_draw), edges, shift, *orbit_cols, *ld_cols)
 
     def run(obs, ivar, cterm):
         return _OrbitLoglike.apply(t, texp, stencil_dt, stencil_w, obs, ivar, cterm, int(flags), int(pack_flags),

@@ -48,8 +48,10 @@ extern "C" {
  * 14: EXO_GP_PREPARE_ADJOINT, a flag or-ed into n_chunks of a celerite pair (the adjoint scan beside the forward chunk kernel).
  * 15: the predictive variance -- exo_celerite_predict_var_work_doubles, exo_celerite_predict_var_f64.
  * 16: period search -- exo_bls_workspace_bytes, exo_bls_power_f64, exo_lomb_scargle_power_f64.
- * 17: priors and constrained parameters -- exo_prior_block, EXO_PRIOR_*, exo_prior_transform_f64 / _vjp_f64. */
-#define EXO_ABI_VERSION 17
+ * 17: priors and constrained parameters -- exo_prior_block, EXO_PRIOR_*, exo_prior_transform_f64 / _vjp_f64.
+ * 18: the white-noise likelihood with a sampled mean and jitter -- exo_transit_noise_vjp_f64, exo_transit_noise_ttv_vjp_f64,
+ *     exo_white_noise_terms_f64, exo_white_noise_workspace_bytes; a slightly larger exo_transit_flux_workspace_bytes. */
+#define EXO_ABI_VERSION 18
 int32_t exo_abi_version(void);
 
 /* ---------------------------------------------------------------------------
@@ -309,6 +311,55 @@ int exo_transit_chi2_ttv_vjp_f64(const double* t, int64_t n_cad, const double* t
                                  const double* ttv_shift, int32_t n_edge, const double* obs, const double* ivar,
                                  int64_t n_ivar, double* chi2, double* gparams, double* gld, double* gshift, void* workspace,
                                  int64_t workspace_bytes, void* stream);
+
+/* The same likelihood with a PER-DRAW mean and a PER-DRAW jitter added in quadrature -- the reference's
+ * `pm.Normal("obs", mu=mean + light_curve, sigma=sqrt(yerr**2 + exp(2 * log_jitter)), observed=y)` with `mean` and
+ * `log_jitter` sampled.  With v_n = var[n_var == 1 ? 0 : n] (yerr^2), mean_d = mean[n_mean == 1 ? 0 : d],
+ * s2_d = n_jit == 0 ? 0 : jit2[n_jit == 1 ? 0 : d] (jitter^2), w_dn = 1 / (v_n + s2_d), r_dn = y[n] - mean_d, and the sums
+ * over the cadences n solved for draw d:
+ *   chi2[d]  = sum w_dn (f[d][n]^2 - 2 f[d][n] r_dn)           (= exo_transit_chi2_vjp_f64 with obs = r_d, ivar = w_d)
+ *   gmean[d] = sum w_dn f[d][n]                                 (d chi2 / d mean_d = 2 gmean[d])
+ *   gjit2[d] = sum w_dn^2 (f[d][n]^2 - 2 f[d][n] r_dn)          (d chi2 / d s2_d = -gjit2[d])
+ *   gparams, gld = d chi2[d] / d (params, ld)                   (cotangent 2 w_dn (f - r_dn) per solved cadence)
+ * The sums over ALL cadences that complete the likelihood are exo_white_noise_terms_f64.  n_var: 1 or n_cad; n_mean: 1 or
+ * n_draw; n_jit: 0, 1 or n_draw (EXO_ERR_INVALID_ARGUMENT otherwise).  Routes, flags, workspace and the other argument
+ * checks are those of exo_transit_chi2_vjp_f64; the two extra sums ride the same block partials in the same fixed order:
+ * bit-reproducible, no floating-point atomics. */
+int exo_transit_noise_vjp_f64(const double* t, int64_t n_cad, const double* texp, int64_t n_texp, const double* stencil_dt,
+                              const double* stencil_w, int32_t n_sub, const double* params, const double* ld,
+                              int64_t n_draw, int32_t n_planet, uint32_t flags, const double* y, const double* var,
+                              int64_t n_var, const double* mean, int64_t n_mean, const double* jit2, int64_t n_jit,
+                              double* chi2, double* gmean, double* gjit2, double* gparams, double* gld, void* workspace,
+                              int64_t workspace_bytes, void* stream);
+
+/* ... and with timing tables: exo_transit_chi2_ttv_vjp_f64 (which see for the tables, the flags and gshift) with the
+ * data arguments and the two extra sums of exo_transit_noise_vjp_f64. */
+int exo_transit_noise_ttv_vjp_f64(const double* t, int64_t n_cad, const double* texp, int64_t n_texp, const double* stencil_dt,
+                                  const double* stencil_w, int32_t n_sub, const double* params, const double* ld,
+                                  int64_t n_draw, int32_t n_planet, uint32_t flags, const double* ttv_edges,
+                                  const double* ttv_shift, int32_t n_edge, const double* y, const double* var, int64_t n_var,
+                                  const double* mean, int64_t n_mean, const double* jit2, int64_t n_jit, double* chi2,
+                                  double* gmean, double* gjit2, double* gparams, double* gld, double* gshift, void* workspace,
+                                  int64_t workspace_bytes, void* stream);
+
+/* The data side of that likelihood: for every draw the sums over ALL n_cad cadences (notation as above)
+ *   terms[0][d] = Q   = sum w_dn r_dn^2         terms[1][d] = Lam = sum log(v_n + s2_d)
+ *   terms[2][d] = G   = sum w_dn r_dn           terms[3][d] = H   = sum w_dn^2 r_dn^2        terms[4][d] = A = sum w_dn
+ * (terms is [5][n_draw]), so that
+ *   loglike_d = -(Q + chi2 + Lam) / 2 - n_cad / 2 log(2 pi),   d / d mean_d = G - gmean,   d / d s2_d = (H + gjit2 - A) / 2.
+ * Three regimes, chosen from n_var, n_mean and n_jit alone:
+ *   n_jit == 0 or n_var == 1: the weight separates, w_dn = u_n x (a factor of the draw).  Per-series sums of the series
+ *     CENTRED on its weighted mean (series[0..7]: ybar, sum u, sum u y', sum u y'^2, sum u^2, sum u^2 y', sum u^2 y'^2,
+ *     sum log v; y' = y - ybar) are taken in one launch unless series_ready != 0 says that `series` still holds them for
+ *     this (y, var) -- they are data -- and every draw is O(1) work from them.  Centring keeps Q a sum of non-negative terms.
+ *   otherwise (per-cadence variances AND a jitter): one pass over (draw, cadence), no array of that size; Lam as the
+ *     logarithm of a running product of mantissas with a summed exponent.  workspace: exo_white_noise_workspace_bytes.
+ * `series` ([8], device) may be null in the second regime; `workspace` in the first.  Every sum in a fixed order:
+ * bit-reproducible, and a draw's terms do not depend on the batch it is in.  n_draw == 0: nothing to do. */
+int64_t exo_white_noise_workspace_bytes(int64_t n_cad, int64_t n_draw);
+int exo_white_noise_terms_f64(const double* y, const double* var, int64_t n_cad, int64_t n_var, const double* mean,
+                              int64_t n_mean, const double* jit2, int64_t n_jit, int64_t n_draw, double* series,
+                              int32_t series_ready, double* terms, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* Diagnostic for the scan kernel's conservative fp32 cadence classifier: the fp32
  * estimate of (cos E - e, sqrt(1-e^2) sin E) for mean anomaly M (fp64 phase) and
