@@ -255,6 +255,22 @@ EXO_HD void sincos_any(double x, double* s, double* c) {
   *c = neg_c ? -cc : cc;
 }
 
+// (t - tp) n reduced to [-pi, pi] (up to a rounding): t - tp as an exact sum of two doubles (Knuth), its product with n as
+// an exact sum of two (fma), the multiple of 2 pi taken off the leading part exactly, then the tails added.  With BJD-sized
+// t and tp = O(1) the two roundings of the plain product are 2.3e-16 |M| ~ 3e-9 rad at |M| = 3e7; this is good to
+// ~2e-16 (1 + |M| 1e-16).  Used by the radial-velocity, orbit-vector and light-curve kernels (exo_rv_core.hpp, exo_transit.hip).
+EXO_HD double mean_anomaly_reduced(double t, double tp, double n) {
+  const double dh = t - tp;
+  const double tb = dh - t;
+  const double dl = (t - (dh - tb)) - (tp + tb);     // t - tp = dh + dl
+  const double mh = dh * n;
+  const double ml = fma(dh, n, -mh) + dl * n;        // (t - tp) n = mh + ml (+ O(1e-32 |M|))
+  const double k = rint(mh * (1.0 / kTwoPiHi));
+  double Mr = fma(-k, kTwoPiHi, mh);                 // |.| <= pi: one rounding of a small number
+  Mr += ml;
+  return fma(-k, kTwoPiLo, Mr);
+}
+
 // ---------------------------------------------------------------------------
 // Kepler solver.  Markley (1995) cubic starter + one fifth-order correction:
 // fixed cost, so there is nothing to vote on.

@@ -17,7 +17,7 @@ constexpr double kPi = 3.14159265358979323846;
 constexpr double kCLight = 37231.66360672704;  // R_sun / day (orbits/constants.py:36)
 
 struct Derived {
-  double a, n, cw, sw, E0, M0, f, cosi, x, y, mtot;
+  double a, n, cw, sw, opsw, E0, M0, f, cosi, x, y, mtot;   // opsw = 1 + sin w
 };
 
 __device__ __forceinline__ Derived derive(const double* in, bool circular) {
@@ -27,14 +27,18 @@ __device__ __forceinline__ Derived derive(const double* in, bool circular) {
   d.a = cbrt(kG * d.mtot * P * P * (1.0 / (4.0 * kPi * kPi)));
   d.n = 2.0 * kPi / P;
   if (circular) {
-    d.cw = 1.0; d.sw = 0.0; d.E0 = 0.5 * kPi; d.M0 = 0.5 * kPi; d.f = 1.0; d.x = 1.0; d.y = 1.0;
+    d.cw = 1.0; d.sw = 0.0; d.opsw = 1.0; d.E0 = 0.5 * kPi; d.M0 = 0.5 * kPi; d.f = 1.0; d.x = 1.0; d.y = 1.0;
   } else {
     sincos(in[EXO_IN_OMEGA], &d.sw, &d.cw);
     d.y = sqrt(1.0 - e) * d.cw;
-    d.x = sqrt(1.0 + e) * (1.0 + d.sw);
+    // 1 + sin w without the cancellation at w -> -pi/2: at w = -fl(pi/2) the sum is exactly 0 in float64, E0 = 2 atan2(y, 0)
+    // is still right, but d E0 / d omega = 2 (x dy - y dx) / (x^2 + y^2) needs the x = O(cos^2 w) that was lost and came out
+    // twice its value (tests/golden/lightcurve_mp.npz, omega_minus_half_pi)
+    d.opsw = d.sw < 0.0 ? d.cw * d.cw / (1.0 - d.sw) : 1.0 + d.sw;
+    d.x = sqrt(1.0 + e) * d.opsw;
     d.E0 = 2.0 * atan2(d.y, d.x);
     d.M0 = d.E0 - e * sin(d.E0);
-    d.f = (1.0 + e * d.sw) / (1.0 - e * e);
+    d.f = (1.0 + e * d.sw) / ((1.0 - e) * (1.0 + e));   // not 1 - e * e: that loses the digits of 1 - e as e -> 1
   }
   d.cosi = d.f * in[EXO_IN_RSTAR] / d.a * in[EXO_IN_B];
   return d;
@@ -202,7 +206,7 @@ __device__ __forceinline__ void pack_vjp_record(const Src& src, int64_t i, int64
     const double M0b = -gtp / d.n;
     nb += g[EXO_P_N] + gtp * d.M0 / (d.n * d.n);
     if (!circular) {
-      const double ome2 = 1.0 - e * e;
+      const double ome2 = (1.0 - e) * (1.0 + e);
       eb += g[EXO_P_ECC] + fb * (d.sw / ome2 + (1.0 + e * d.sw) * 2.0 * e / (ome2 * ome2));
       swb += g[EXO_P_SINW] + fb * e / ome2;
       cwb += g[EXO_P_COSW];
@@ -217,7 +221,7 @@ __device__ __forceinline__ void pack_vjp_record(const Src& src, int64_t i, int64
       cwb += yb * se;
       eb -= yb * d.cw * 0.5 / se;
       swb += xb * pe;
-      eb += xb * (1.0 + d.sw) * 0.5 / pe;
+      eb += xb * d.opsw * 0.5 / pe;
       wb = -cwb * d.sw + swb * d.cw;
     }
     // n = 2 pi / P ;  a = (G mtot P^2 / 4 pi^2)^(1/3)

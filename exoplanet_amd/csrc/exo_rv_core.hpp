@@ -18,19 +18,7 @@
 
 namespace exo {
 
-// (t - tp) n reduced to [-pi, pi] (up to a rounding): t - tp as an exact sum of two doubles (Knuth), its product with n as
-// an exact sum of two (fma), the multiple of 2 pi taken off the leading part exactly, then the tails added.
-EXO_HD double mean_anomaly_reduced(double t, double tp, double n) {
-  const double dh = t - tp;
-  const double tb = dh - t;
-  const double dl = (t - (dh - tb)) - (tp + tb);     // t - tp = dh + dl
-  const double mh = dh * n;
-  const double ml = fma(dh, n, -mh) + dl * n;        // (t - tp) n = mh + ml (+ O(1e-32 |M|))
-  const double k = rint(mh * (1.0 / kTwoPiHi));
-  double Mr = fma(-k, kTwoPiHi, mh);                 // |.| <= pi: one rounding of a small number
-  Mr += ml;
-  return fma(-k, kTwoPiLo, Mr);
-}
+// (mean_anomaly_reduced: exo_math.hpp, shared with the light-curve kernels)
 
 struct RvSample {
   double g;      // cw (cos f + e) - sw sin f

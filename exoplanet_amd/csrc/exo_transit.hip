@@ -511,7 +511,7 @@ __device__ __forceinline__ double eval_sample(double tt, const PlanetS& c, const
   // saved by the delay computation for its reverse sweep
   double ld_cx = 0, ld_sx = 0, ld_den = 0, ld_z = 0, ld_vz = 0, ld_az = 0, ld_w = 0, ld_s = 0, ld_D = 0, ld_sig = 1, ld_t = tt;
   if (LDELAY) {
-    const exo::KeplerHalf k1 = exo::kepler_half((tt - c.tp) * c.n, c.e, c.se, c.pe);
+    const exo::KeplerHalf k1 = exo::kepler_half(exo::mean_anomaly_reduced(tt, c.tp, c.n), c.e, c.se, c.pe);
     const double X2 = k1.X * k1.X, Y2 = k1.Y * k1.Y;
     ld_cx = X2 - Y2; ld_sx = 2.0 * k1.X * k1.Y; ld_den = X2 + Y2;
     const double y1 = -c.aor * (c.sw * ld_cx + c.cw * ld_sx);
@@ -527,7 +527,9 @@ __device__ __forceinline__ double eval_sample(double tt, const PlanetS& c, const
     ld_D = 2.0 * q * ic / (ld_w + ld_s);
     tt -= ld_D;
   }
-  const double M = (tt - c.tp) * c.n;
+  // not (tt - c.tp) * c.n: with BJD-sized times and t_periastron = O(1) the plain product's two roundings are 3e-9 rad,
+  // which every gradient slot then carries in its ninth digit (tests/golden/lightcurve_mp.npz, bjd_times_tp_03)
+  const double M = exo::mean_anomaly_reduced(tt, c.tp, c.n);
   const exo::KeplerHalf kh = exo::kepler_half(M, c.e, c.se, c.pe);
   const double X2 = kh.X * kh.X, Y2 = kh.Y * kh.Y;
   const double cx = X2 - Y2;            // (1 - e cos E) cos f = cos E - e
@@ -613,6 +615,8 @@ __device__ __forceinline__ double eval_sample(double tt, const PlanetS& c, const
       const double Ebar = fma(-sinE, cxbar, c.sq1me2 * cosE * sxbar);
       const double Mbar = Ebar * iden;
       acc.add(G_ECC, Mbar * sinE - cxbar - c.e * sinE * c.isq1me2 * sxbar);
+      // d M / d n = t - tp: fl(tt - c.tp) is the leading part of mean_anomaly_reduced's split, good to one rounding
+      // (relative 1e-16 of this term), so the cotangent needs no tail
       acc.add(G_N, Mbar * (tt - c.tp));
       acc.add(G_TP, -Mbar * c.n);
       if (LDELAY) {
@@ -694,7 +698,9 @@ template <bool SECONDARY, bool FAST>
 __device__ __forceinline__ int classify_sample(double tt, const PlanetConst& c) {
   if (FAST) {
     // conservative fp32 classification: only the phase is fp64 (see exo::orbit_pos_f32);
-    // every accepted cadence is re-evaluated in fp64 by the heavy kernel
+    // every accepted cadence is re-evaluated in fp64 by the heavy kernel.  The phase stays the plain product: its two
+    // roundings (2.3e-16 |M| each, 7e-9 rad at |M| = 3e7) move the position by |d pos / d M| <= sqrt((1 + e) / (1 - e))
+    // times that, in units of a -- 1e-7 at e = 0.99 -- against the 1.6e-3 a/R that the margin holds for the fp32 error.
     float cx, sx;
     exo::orbit_pos_f32((tt - c.tp) * c.n, c.ef, c.omf, c.sqf, &cx, &sx);
     const float x1 = c.cwf * cx - c.swf * sx;
@@ -705,7 +711,8 @@ __device__ __forceinline__ int classify_sample(double tt, const PlanetConst& c) 
     const float b2s = fmaf(x1, x1, Ys * Ys);
     return (vis && !(b2s >= c.thrf)) ? ((b2s < c.inthrf) ? 1 : 2) : 0;
   }
-  const exo::KeplerHalf kh = exo::kepler_half((tt - c.tp) * c.n, c.e, c.se, c.pe);
+  // the exact classifier decides with the same phase as eval_sample
+  const exo::KeplerHalf kh = exo::kepler_half(exo::mean_anomaly_reduced(tt, c.tp, c.n), c.e, c.se, c.pe);
   const double cx = kh.X * kh.X - kh.Y * kh.Y, sx = 2.0 * kh.X * kh.Y;
   const double x1 = c.cw * cx - c.sw * sx;  // position / (-a/R)
   const double y1 = c.sw * cx + c.cw * sx;
