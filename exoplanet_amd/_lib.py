@@ -10,7 +10,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # EXOPLANET_AMD_LIB selects another in-tree build of the same ABI (A/B measurements)
 LIB_PATH = os.environ.get("EXOPLANET_AMD_LIB") or os.path.join(_HERE, "lib", "libexoplanet_amd.so")
-ABI_VERSION = 18
+ABI_VERSION = 19
 
 _c_dp = ctypes.c_void_p  # device pointers travel as integers
 _i64 = ctypes.c_int64
@@ -139,6 +139,10 @@ _SIGNATURES = {
     "exo_lomb_scargle_power_f64": (ctypes.c_int, [_c_dp, _c_dp, _c_dp, _i64, _i64, _i64, _c_dp, _i64, _c_dp, _c_dp, _i64, _c_dp]),
     "exo_radial_velocity_fwd_f64": (ctypes.c_int, [_c_dp, _i64, _c_dp, _i64, _i32, _c_dp, _c_dp]),
     "exo_radial_velocity_vjp_f64": (ctypes.c_int, [_c_dp, _i64, _c_dp, _i64, _i32, _c_dp, _c_dp, _c_dp]),
+    # t, tau, inst, rv, var, n_cad, n_var, params, n_draw, n_planet, trend, n_trend, offset, jit2, n_inst, loglike, gparams,
+    # gtrend, goffset, gjit2, stream
+    "exo_rv_loglike_vjp_f64": (ctypes.c_int, [_c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _i64, _i64, _c_dp, _i64, _i32, _c_dp, _i32,
+                                              _c_dp, _c_dp, _i32, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp]),
     "exo_orbit_vector_fwd_f64": (ctypes.c_int, [_c_dp, _i64, _c_dp, _i64, _i32, _u32, _c_dp, _c_dp]),
     "exo_orbit_vector_vjp_f64": (ctypes.c_int, [_c_dp, _i64, _c_dp, _i64, _i32, _u32, _c_dp, _c_dp, _c_dp]),
     # t, n_cad, texp, n_texp, stencil_dt, stencil_w, n_sub, params, ld, n_draw, n_planet, flags, obs, ivar, n_ivar,

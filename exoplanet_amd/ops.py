@@ -1473,6 +1473,146 @@ def radial_velocity(t, params):
 
 
 # ------------------------------------------------------------------------------
+# radial-velocity likelihood: value and every gradient from one launch
+# ------------------------------------------------------------------------------
+RV_MAX_TREND = 4      # include/exoplanet_amd.h EXO_RV_MAX_TREND
+RV_MAX_INST = 8       # EXO_RV_MAX_INST
+_RV_DATA = {}         # rv_loglike: (epochs, error bars, reference time, instruments) -> tau, variances, int32 instruments
+
+
+def _rv_data(t, rv_err, t_ref, instrument):
+    """the per-series arrays of exo_rv_loglike_vjp_f64 -- (tau = t - t_ref, var = rv_err^2 as (1,) or (n_cad,), int32
+    instruments | None, their largest index | None if unchecked) -- made once per series (the indices are checked on the
+    host, a device synchronisation; inside a capture nothing is kept and nothing checked: the kernel answers an index
+    outside its tables with NaN)"""
+    key = (t.data_ptr(), t._version, t.numel(), float(t_ref),
+           rv_err if not isinstance(rv_err, torch.Tensor) else (rv_err.data_ptr(), rv_err._version),
+           None if instrument is None else (instrument.data_ptr(), instrument._version), str(t.device))
+    hit = _RV_DATA.get(key)
+    if hit is not None:
+        return hit[:4]
+    capturing = torch.cuda.is_current_stream_capturing()
+    tau = t - float(t_ref)
+    if isinstance(rv_err, torch.Tensor):
+        err = _dev(rv_err.detach(), "rv_err").reshape(-1)
+        if err.numel() not in (1, t.numel()):
+            raise ValueError("rv_err must be a number or one value per epoch")
+        var = err * err
+    else:
+        var = _const(float(rv_err) ** 2, t.device)
+    inst, hi = None, None
+    if instrument is not None:
+        if not isinstance(instrument, torch.Tensor) or instrument.is_floating_point() or tuple(instrument.shape) != (t.numel(),):
+            raise ValueError("instrument must be an integer tensor with one entry per epoch")
+        inst = instrument.to(device=t.device, dtype=torch.int32).contiguous()
+        if not capturing and inst.numel():
+            lo, hi = int(inst.min()), int(inst.max())
+            if lo < 0 or hi >= RV_MAX_INST:
+                raise ValueError(f"instrument indices must lie in [0, {RV_MAX_INST}): got {lo} .. {hi}")
+    hit = (tau, var, inst, hi, (t, rv_err, instrument))      # (the sources stay alive: their addresses are the key)
+    if not capturing:
+        if len(_RV_DATA) >= 4:      # (an entry keeps its arrays alive: a few series at most)
+            _RV_DATA.clear()
+        _RV_DATA[key] = hit
+    return hit[:4]
+
+
+def _per_draw_inst(x, name, D, device):
+    """``x`` (a number, or a 0-d / (D,) / (D, 1) / (D, n_inst) tensor) as a 2-D tensor of 1 or D rows"""
+    if isinstance(x, (int, float)):
+        return _const(x, device).reshape(1, 1)
+    x = _dev(x, name)
+    x = x.reshape(-1, 1) if x.dim() < 2 else x
+    if x.dim() != 2 or x.shape[0] not in (1, D):
+        raise ValueError(f"radial-velocity likelihood: `{name}` has shape {tuple(x.shape)}, the parameters hold {D} draws -- a number, "
+                         "one value per draw, or (draws, instruments)")
+    return x
+
+
+class _RvLoglike(torch.autograd.Function):
+    """exo_rv_loglike_vjp_f64: the forward pass makes the one call and keeps the gradients, the reverse pass scales them by
+    the incoming cotangent.  ``trend`` (D, T) | None, ``offset`` / ``jit2`` (D, n_inst) | None."""
+
+    @staticmethod
+    def forward(ctx, t, tau, inst, rv, var, params, trend, offset, jit2, n_inst):
+        D, P, _ = params.shape
+        dev = t.device
+        T = 0 if trend is None else trend.shape[1]
+        new = lambda *shape: torch.empty(*shape, dtype=torch.float64, device=dev)  # noqa: E731
+        ll = new(D)
+        gparams = new(D, P, RV_NPAR) if ctx.needs_input_grad[5] else None
+        gtrend = new(D, T) if trend is not None and ctx.needs_input_grad[6] else None
+        goffset = new(D, n_inst) if offset is not None and ctx.needs_input_grad[7] else None
+        gjit2 = new(D, n_inst) if jit2 is not None and ctx.needs_input_grad[8] else None
+        _call("exo_rv_loglike_vjp_f64", dev, _ptr(t), _ptr(tau), _ptr(inst), _ptr(rv), _ptr(var), t.numel(), var.numel(),
+              _ptr(params), D, P, _ptr(trend), T, _ptr(offset), _ptr(jit2), n_inst, _ptr(ll), _ptr(gparams), _ptr(gtrend),
+              _ptr(goffset), _ptr(gjit2), _stream(t))
+        ctx.have = [g is not None for g in (gparams, gtrend, goffset, gjit2)]
+        ctx.save_for_backward(*[g for g in (gparams, gtrend, goffset, gjit2) if g is not None])
+        return ll
+
+    @staticmethod
+    def backward(ctx, gll):
+        gll = gll.contiguous()
+        saved = iter(ctx.saved_tensors)
+        gparams, gtrend, goffset, gjit2 = (next(saved) if have else None for have in ctx.have)
+        col = gll[:, None]
+        return (None, None, None, None, None, None if gparams is None else gll[:, None, None] * gparams,
+                None if gtrend is None else col * gtrend, None if goffset is None else col * goffset,
+                None if gjit2 is None else col * gjit2, None)
+
+
+def rv_loglike(t, params, rv, rv_err, trend=None, t_ref=0.0, offset=None, jitter=None, instrument=None):
+    """Gaussian log-likelihood (n_draw,) of the observed radial velocities ``rv`` (n_cad,) with independent errors ``rv_err``
+    (a number or one value per epoch) for ``n_draw`` parameter sets, value and every gradient in ONE launch
+    (exo_rv_loglike_vjp_f64) -- the reference tutorials' ``pm.Normal("obs", mu=zero_point + trend +
+    orbit.get_radial_velocity(t, K=K), sigma=sqrt(rv_err**2 + exp(2 * log_jitter)), observed=rv)``:
+
+        model = sum over planets of radial_velocity(t, params) + sum_k trend[:, k] (t - t_ref)**k + offset[:, instrument]
+        sigma**2 = rv_err**2 + jitter[:, instrument]**2
+
+    ``params`` (n_draw, n_planet, 6) as for :func:`radial_velocity`; ``trend`` None or (n_draw, T), T <= 4, powers
+    increasing; ``offset`` and ``jitter`` None, a number, one value per draw or (n_draw, n_inst), n_inst <= 8; ``instrument``
+    None (one instrument) or an integer tensor (n_cad,) of indices into those columns.  Differentiable in ``params``,
+    ``trend``, ``offset`` and ``jitter`` (which enters the kernel squared; the chain rule to it is torch's).  ``rv`` and
+    ``rv_err`` are data: one that requires grad is refused, not silently dropped
+    (KeplerianOrbit.rv_log_likelihood takes the composed route for those)."""
+    t, params, rv = _dev(t, "t").detach(), _dev(params, "params"), _dev(rv, "rv")
+    if t.dim() != 1 or tuple(rv.shape) != tuple(t.shape):
+        raise ValueError("t and rv must be 1-D with one entry per epoch")
+    if params.dim() != 3 or params.shape[-1] != RV_NPAR:
+        raise ValueError(f"params must be (n_draw, n_planet, {RV_NPAR})")
+    D, P, _ = params.shape
+    if not 1 <= P <= MAX_PLANETS:
+        raise ValueError(f"between 1 and {MAX_PLANETS} planets")
+    for name, x in (("rv", rv), ("rv_err", rv_err)):
+        if isinstance(x, torch.Tensor) and x.requires_grad and torch.is_grad_enabled():
+            raise NotImplementedError(
+                f"radial-velocity likelihood: `{name}` requires grad, and the fused kernel differentiates the orbit, the trend, "
+                "the zero points and the jitter only; use KeplerianOrbit.rv_log_likelihood (it falls back to "
+                "get_radial_velocity and torch)")
+    tau, var, inst, hi = _rv_data(t, rv_err, t_ref, instrument)
+    if trend is not None:
+        trend = _dev(trend, "trend")
+        if trend.dim() != 2 or trend.shape[0] not in (1, D) or trend.shape[1] > RV_MAX_TREND:
+            raise ValueError(f"trend must be (n_draw, T) with T <= {RV_MAX_TREND}; got {tuple(trend.shape)} for {D} draws")
+        trend = trend.expand(D, -1).contiguous() if trend.shape[1] else None
+    offset = None if offset is None else _per_draw_inst(offset, "offset", D, t.device)
+    jitter = None if jitter is None else _per_draw_inst(jitter, "jitter", D, t.device)
+    # one column everywhere: the instruments share every parameter, and which epoch is whose does not matter
+    widths = {x.shape[1] for x in (offset, jitter) if x is not None and x.shape[1] > 1}
+    n_inst = max(widths) if widths else 1
+    if len(widths) > 1 or n_inst > RV_MAX_INST or (n_inst > 1 and (inst is None or (hi is not None and hi >= n_inst))):
+        raise ValueError(f"offset / jitter with {sorted(widths)} columns need `instrument` with indices below that one number of "
+                         f"columns (at most {RV_MAX_INST}); the indices go up to {hi}")
+    if n_inst == 1:
+        inst = None
+    offset = None if offset is None else offset.expand(D, n_inst).contiguous()
+    jit2 = None if jitter is None else (jitter * jitter).expand(D, n_inst).contiguous()
+    return _RvLoglike.apply(t, tau, inst, rv.detach(), var, params, trend, offset, jit2, n_inst)
+
+
+# ------------------------------------------------------------------------------
 # record packing: KeplerianOrbit.__init__ algebra + get_cl + windows as one kernel
 # ------------------------------------------------------------------------------
 class _PackRecords(torch.autograd.Function):

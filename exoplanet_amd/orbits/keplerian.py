@@ -67,6 +67,53 @@ def _vec(x, like=None):
     return x.reshape(1) if x.dim() == 0 else x
 
 
+_MIDDLE = {}
+
+
+def _middle(t):
+    """the middle of the series ``t`` as a number, read back once per series (a device synchronisation, which a hipGraph
+    capture does not allow: the warm-up call before the capture has left it here, or the caller passes ``t_ref``)"""
+    key = (t.data_ptr(), t._version, t.numel(), str(t.device))
+    if key not in _MIDDLE:
+        if t.is_cuda and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("rv_log_likelihood: pass t_ref, or call once with these times before capturing a graph")
+        if len(_MIDDLE) >= 16:
+            _MIDDLE.clear()
+        # (the series stays alive with its entry: its address is the key)
+        _MIDDLE[key] = (0.5 * (float(t.min()) + float(t.max())) if t.numel() else 0.0, t)
+    return _MIDDLE[key][0]
+
+
+def _rv_loglike_composed(t, params, rv, rv_err, trend=None, t_ref=0.0, offset=None, jitter=None, instrument=None):
+    """ops.rv_loglike written out -- the radial-velocity op and torch -- for what the fused kernel does not differentiate
+    (``rv``, a per-epoch ``rv_err``)"""
+    m = ops.radial_velocity(t, params).sum(-1)                      # (draws, epochs)
+    tau = t - float(t_ref)
+    idx = None if instrument is None else instrument.to(device=t.device, dtype=torch.long)
+
+    def per_epoch(x):
+        """a number, one value per draw or (draws, instruments) against (draws, epochs)"""
+        if not isinstance(x, torch.Tensor):
+            return x
+        x = x.reshape(-1, 1) if x.dim() < 2 else x
+        if x.shape[1] > 1:
+            if idx is None:
+                raise ValueError("zero_point / jitter with a column per instrument need `instrument`")
+            return x[:, idx]
+        return x
+
+    if trend is not None:
+        for k in range(trend.shape[1]):
+            m = m + trend[:, k:k + 1] * tau ** k
+    if offset is not None:
+        m = m + per_epoch(offset)
+    s2 = as_tensor(rv_err, t).to(t.device) ** 2 + torch.zeros_like(m)
+    if jitter is not None:
+        s2 = s2 + per_epoch(jitter) ** 2
+    r = rv - m
+    return -0.5 * (r * r / s2 + torch.log(s2) + math.log(_TWO_PI)).sum(-1)
+
+
 class KeplerianOrbit:
     """A system of bodies on Keplerian orbits around a common central body.
 
@@ -461,6 +508,66 @@ class KeplerianOrbit:
             cw, sw, e = self.cos_omega.unsqueeze(-2), self.sin_omega.unsqueeze(-2), self.ecc.unsqueeze(-2)
             return (K * (cw * cosf - sw * sinf + e * cw)).squeeze()
         return -m_per_s_per_Rsun_per_day * self.get_star_velocity(t)[2]
+
+    def _rv_records(self, K):
+        """the EXO_RV_* records ``(params (D, P, 6), batch shape)`` as the fused route of get_radial_velocity builds them:
+        from the packing kernel for the standard parameterisation with ``K``, from the attributes otherwise (``K`` or the
+        mass-based amplitude); a circular orbit is ECC = 0, COSW = 1, SINW = 0"""
+        if K is not None and self._standard and not self._ready:
+            rec, _, batch, _ = self.kernel_inputs(0.0, (0.0, 0.0))
+            amp = _vec(K, rec).expand(tuple(batch) + (rec.shape[1],)).reshape(-1, rec.shape[1], 1)
+            return torch.cat([rec[..., ops.P_N:ops.P_SINW + 1], amp], dim=-1), tuple(batch)
+        amp = _vec(K, self.n) if K is not None else m_per_s_per_Rsun_per_day * self.sin_incl * self.K0 * self.m_planet
+        e, cw, sw = self._ew()
+        cols = torch.broadcast_tensors(self.n, self.t_periastron, e, cw, sw, amp)
+        shape = cols[0].shape
+        return torch.stack(cols, dim=-1).reshape(-1, shape[-1], ops.RV_NPAR).contiguous(), tuple(shape[:-1])
+
+    def rv_log_likelihood(self, t, rv, rv_err, K=None, zero_point=None, trend=None, t_ref=None, jitter=None, instrument=None):
+        """Gaussian log-likelihood (one value per draw) of the observed radial velocities ``rv`` with independent errors
+        ``rv_err`` -- what the reference's tutorials write as ``rv_model = zero_point + trend +
+        orbit.get_radial_velocity(t, K=K)`` (summed over the planets), ``sigma = sqrt(rv_err**2 + exp(2 * log_jitter))``,
+        ``pm.Normal("obs", mu=rv_model, sigma=sigma, observed=rv)`` -- value and every gradient in ONE launch
+        (ops.rv_loglike), no (draws, epochs, planets) array anywhere.
+
+        ``K``: the semi-amplitudes, or None for the mass-based form in m/s (as get_radial_velocity).  ``zero_point`` and
+        ``jitter``: None, a number, one value per draw or (draws, n_inst), a column per instrument, with ``instrument`` an
+        integer vector giving every epoch its column.  ``trend``: (T,) or (draws, T) polynomial coefficients in
+        ``t - t_ref``, powers increasing, T <= 4; ``t_ref`` defaults to the middle of ``t``.  ``rv_err``: a number or one
+        value per epoch.  All of the orbit, ``K``, ``zero_point``, ``trend`` and ``jitter`` are differentiable.  Draw counts
+        that do not agree raise a ValueError.  What the fused form cannot differentiate -- an ``rv`` or a per-epoch
+        ``rv_err`` that requires grad -- takes the radial-velocity op and torch: slower, never a partial gradient.  An
+        orbit that warps its times (TTVOrbit) is refused: NotImplementedError."""
+        if type(self)._warp_times is not KeplerianOrbit._warp_times:
+            raise NotImplementedError("rv_log_likelihood needs a KeplerianOrbit without timing variations: the radial-velocity "
+                                      "kernels take no time warp")
+        t = as_tensor(t, next((x for x in self._args.values() if isinstance(x, torch.Tensor)), None)).detach()
+        if t.dim() != 1:
+            raise ValueError("t must be 1-D (n_cad,)")
+        params, batch = self._rv_records(K)
+        rv = as_tensor(rv, t).to(t.device)
+        if t_ref is None:
+            t_ref = _middle(t)
+        if isinstance(trend, torch.Tensor) and trend.dim() == 1:
+            trend = trend.reshape(1, -1)
+        # draws of the zero points, jitters and trend of ONE system: the records are repeated
+        extra = [x.shape[0] for x in (zero_point, jitter, trend) if isinstance(x, torch.Tensor) and x.dim() >= 1]
+        D = params.shape[0]
+        if D == 1 and max(extra + [1]) > 1:
+            D = max(extra)
+            params = params.expand(D, -1, -1).contiguous()
+        for name, x in (("zero_point", zero_point), ("jitter", jitter), ("trend", trend)):
+            if isinstance(x, torch.Tensor) and x.dim() >= 1 and x.shape[0] not in (1, D):
+                raise ValueError(f"rv_log_likelihood: `{name}` holds {x.shape[0]} draws, the parameters {D}")
+        needs = lambda x: isinstance(x, torch.Tensor) and x.requires_grad and torch.is_grad_enabled()  # noqa: E731
+        route = _rv_loglike_composed if needs(rv) or needs(rv_err) else ops.rv_loglike
+        ll = route(t, params, rv, rv_err, trend=trend, t_ref=t_ref, offset=zero_point, jitter=jitter, instrument=instrument)
+        n = 1
+        for b in batch:
+            n *= int(b)
+        if ll.numel() == n:
+            return ll.reshape(batch)
+        return ll
 
     def _get_acceleration(self, a, m, t):
         fused = self._fused_vector((self.K0 * m) ** 2 / a, t, velocity=False, acceleration=True)

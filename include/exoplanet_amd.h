@@ -50,8 +50,9 @@ extern "C" {
  * 16: period search -- exo_bls_workspace_bytes, exo_bls_power_f64, exo_lomb_scargle_power_f64.
  * 17: priors and constrained parameters -- exo_prior_block, EXO_PRIOR_*, exo_prior_transform_f64 / _vjp_f64.
  * 18: the white-noise likelihood with a sampled mean and jitter -- exo_transit_noise_vjp_f64, exo_transit_noise_ttv_vjp_f64,
- *     exo_white_noise_terms_f64, exo_white_noise_workspace_bytes; a slightly larger exo_transit_flux_workspace_bytes. */
-#define EXO_ABI_VERSION 18
+ *     exo_white_noise_terms_f64, exo_white_noise_workspace_bytes; a slightly larger exo_transit_flux_workspace_bytes.
+ * 19: the radial-velocity likelihood -- exo_rv_loglike_vjp_f64, EXO_RV_MAX_TREND, EXO_RV_MAX_INST. */
+#define EXO_ABI_VERSION 19
 int32_t exo_abi_version(void);
 
 /* ---------------------------------------------------------------------------
@@ -482,6 +483,34 @@ int exo_radial_velocity_fwd_f64(const double* t, int64_t n_cad, const double* pa
                                 int32_t n_planet, double* rv, void* stream);
 int exo_radial_velocity_vjp_f64(const double* t, int64_t n_cad, const double* params, int64_t n_draw,
                                 int32_t n_planet, const double* grv, double* gparams, void* stream);
+
+/* ---------------------------------------------------------------------------
+ * Gaussian log-likelihood of an observed radial-velocity series, value and every gradient in ONE launch -- the tutorials'
+ *   rv_model = zero_point + orbit.get_radial_velocity(t, K=semiamp) [+ trend];  sigma = sqrt(rv_err**2 + exp(2 log_jitter));
+ *   pm.Normal("obs", mu=rv_model, sigma=sigma, observed=rv_obs)
+ * for n_draw parameter sets.  With g(t; rec) = COSW (cos f + ECC) - SINW sin f of the records above:
+ *   m[d][n]  = sum_p AMP[d][p] g(t_n; rec[d][p]) + sum_{k < n_trend} trend[d][k] tau_n^k + offset[d][inst_n]
+ *   s2[d][n] = var[n_var == 1 ? 0 : n] + jit2[d][inst_n],    w = 1 / s2,    rho = w (rv_n - m)
+ *   loglike[d]    = -1/2 sum_n (w (rv_n - m)^2 + log s2) - n_cad / 2 log(2 pi)
+ *   gparams[d][p] = d loglike / d rec[d][p]      (EXO_RV_NPAR doubles: the reverse pass of the radial velocity with cotangent rho)
+ *   gtrend[d][k]  = sum_n rho tau_n^k
+ *   goffset[d][i] = sum over the epochs of instrument i of rho
+ *   gjit2[d][i]   = 1/2 sum over the epochs of instrument i of (rho^2 - w)
+ * t [n_cad] are the epochs the orbit is evaluated at; tau [n_cad] = t - t_ref is formed by the caller (the kernel subtracts no
+ * large numbers; may be null when n_trend <= 1).  inst: int32 [n_cad], the instrument of every epoch, in [0, n_inst) (an index
+ * outside gives NaN in every draw; may be null when n_inst == 1).  rv [n_cad]; var [n_var], n_var = 1 or n_cad.  params
+ * [n_draw][n_planet][EXO_RV_NPAR], n_planet <= EXO_MAX_PLANETS.  trend [n_draw][n_trend], 0 <= n_trend <= EXO_RV_MAX_TREND,
+ * powers increasing.  offset, jit2 [n_draw][n_inst], 1 <= n_inst <= EXO_RV_MAX_INST; either may be null (zero).  A null
+ * gradient output is not written.  An instrument without epochs gets gradients of exactly 0; ECC outside [0, 1) gives NaN in
+ * that draw only.  No workspace: one workgroup per draw, whose width depends on n_cad alone, every sum in a fixed order
+ * (bit-reproducible, and a draw's results do not depend on the batch it is in).  n_draw == 0: EXO_OK, nothing launched.
+ * ------------------------------------------------------------------------- */
+#define EXO_RV_MAX_TREND 4
+#define EXO_RV_MAX_INST 8
+int exo_rv_loglike_vjp_f64(const double* t, const double* tau, const int32_t* inst, const double* rv, const double* var,
+                           int64_t n_cad, int64_t n_var, const double* params, int64_t n_draw, int32_t n_planet,
+                           const double* trend, int32_t n_trend, const double* offset, const double* jit2, int32_t n_inst,
+                           double* loglike, double* gparams, double* gtrend, double* goffset, double* gjit2, void* stream);
 
 /* ---------------------------------------------------------------------------
  * Position / velocity vectors in the observer frame from the same solve.  Replaces, for n_draw parameter sets, the
