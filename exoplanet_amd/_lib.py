@@ -10,7 +10,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # EXOPLANET_AMD_LIB selects another in-tree build of the same ABI (A/B measurements)
 LIB_PATH = os.environ.get("EXOPLANET_AMD_LIB") or os.path.join(_HERE, "lib", "libexoplanet_amd.so")
-ABI_VERSION = 19
+ABI_VERSION = 20
 
 _c_dp = ctypes.c_void_p  # device pointers travel as integers
 _i64 = ctypes.c_int64
@@ -130,6 +130,10 @@ _SIGNATURES = {
     # work_doubles, stream
     "exo_celerite_predict_var_f64": (ctypes.c_int, [_c_dp, _c_dp, _i64, _i64, _c_dp, _i32, _c_dp, _i32, _c_dp, _c_dp, _i64,
                                                     _c_dp, _i64, _c_dp, _c_dp, _i64, _c_dp]),
+    "exo_celerite_solve_work_doubles": (_i64, [_i64, _i32, _i32, _i64]),
+    # t, diag, n_diag, n, coef_real, n_real, coef_complex, n_complex, pair_kind, n_draw, y, alpha, work, work_doubles, stream
+    "exo_celerite_solve_f64": (ctypes.c_int, [_c_dp, _c_dp, _i64, _i64, _c_dp, _i32, _c_dp, _i32, _c_dp, _i64, _c_dp, _c_dp,
+                                              _c_dp, _i64, _c_dp]),
     "exo_bls_workspace_bytes": (_i64, [_i64, _i64, _i64, _i64]),
     # t, y, yerr, n_yerr, n, n_series, periods, n_period, min_bins, max_bins, duration_bins (host), n_duration, delta,
     # oversample, objective, out, workspace, workspace_bytes, stream

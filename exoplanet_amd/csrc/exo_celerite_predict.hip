@@ -28,6 +28,16 @@ __global__ __launch_bounds__(kWave) void celerite_predict_var_kernel(const doubl
   predict_var_lane<J>(t, diag, n_diag, n, cf, slot_mask, tq, m, var, work, n_draw, draw);
 }
 
+template <int J>
+__global__ __launch_bounds__(kWave) void celerite_solve_kernel(const double* __restrict__ t, const double* __restrict__ diag,
+                                                               int64_t n_diag, int64_t n, Coefs cf, int64_t n_draw,
+                                                               const double* __restrict__ y, double* __restrict__ alpha,
+                                                               double* __restrict__ work) {
+  const int64_t draw = (int64_t)blockIdx.x * kWave + threadIdx.x;
+  if (draw >= n_draw) return;
+  solve_lane<J>(t, diag, n_diag, n, cf, y, alpha, work, n_draw, draw);
+}
+
 // (the next three: as in exo_celerite.hip)
 inline int launch_status() { return hipGetLastError() == hipSuccess ? EXO_OK : EXO_ERR_LAUNCH; }
 
@@ -72,6 +82,30 @@ int exo_celerite_predict_var_f64(const double* t, const double* diag, int64_t n_
   if (!with_J<1, EXO_GP_MAX_J>(cf.J(), [&](auto jj) {
         hipLaunchKernelGGL((celerite_predict_var_kernel<decltype(jj)::value>), grid, block, 0, (hipStream_t)stream, t, diag, n_diag,
                            n, cf, slot_mask, n_draw, tq, m, var, work);
+      }))
+    return EXO_ERR_INVALID_ARGUMENT;
+  return launch_status();
+}
+
+int64_t exo_celerite_solve_work_doubles(int64_t n, int32_t n_real, int32_t n_complex, int64_t n_draw) {
+  const int J = n_real + 2 * n_complex;
+  if (n < 1 || n_draw < 0 || n_real < 0 || n_complex < 0 || J < 1 || J > EXO_GP_MAX_J) return -1;
+  return solve_work_doubles(n, J, n_draw);
+}
+
+int exo_celerite_solve_f64(const double* t, const double* diag, int64_t n_diag, int64_t n, const double* coef_real, int32_t n_real,
+                           const double* coef_complex, int32_t n_complex, const int32_t* pair_kind, int64_t n_draw, const double* y,
+                           double* alpha, double* work, int64_t work_doubles, void* stream) {
+  if (n_draw == 0) return EXO_OK;
+  if (!gp_args_ok(n, n_diag, n_real, n_complex, n_draw) || !t || !diag || !y || !alpha || !work || y == alpha ||
+      (n_real > 0 && !coef_real) || (n_complex > 0 && !coef_complex))
+    return EXO_ERR_INVALID_ARGUMENT;
+  if (work_doubles < solve_work_doubles(n, n_real + 2 * n_complex, n_draw)) return EXO_ERR_WORKSPACE;
+  const Coefs cf{coef_real, coef_complex, pair_kind, n_real, n_complex, t};
+  const dim3 grid((unsigned)((n_draw + kWave - 1) / kWave)), block(kWave);
+  if (!with_J<1, EXO_GP_MAX_J>(cf.J(), [&](auto jj) {
+        hipLaunchKernelGGL((celerite_solve_kernel<decltype(jj)::value>), grid, block, 0, (hipStream_t)stream, t, diag, n_diag, n, cf,
+                           n_draw, y, alpha, work);
       }))
     return EXO_ERR_INVALID_ARGUMENT;
   return launch_status();

@@ -29,6 +29,46 @@ EXO_HDH int64_t predict_var_work_doubles(int64_t n, int64_t m, int J, int64_t n_
   return (n + m) * (int64_t)(J + 1) * n_draw;
 }
 
+// The backward pass carries B in double-double (an unevaluated sum hi + lo of two doubles, ~106 bits).  B holds the information
+// of the data after a cadence: its entries reach 1 / d_i (1e4 at diag = 1e-4, 5e11 at a repeated time stamp under diag = 1e-12),
+// and the update  X - U y^T - y U^T + s U U^T  as well as the query's  r*^T B r*  are differences of terms of that size whose
+// result is of order 1 / k(0): in plain doubles the absolute error eps max |B_i| shows wherever r* is not small -- before the
+// first datum, next to a repeated stamp -- at up to 1e-9 k(0).  The inputs (U, W, 1 / d, the
+// propagators, r*) stay doubles: with them exact the result is within a few eps of the dense definition.
+// The error-free transformations below rely on every product and sum being rounded as written: no contraction into fma
+// across them (hipcc's default would fuse  p + e  with the product behind p, and the low word would be lost).
+#if defined(__clang__)
+#define EXO_DD_EXACT _Pragma("clang fp contract(off)")
+#else
+#define EXO_DD_EXACT
+#endif
+struct DD {
+  double h, l;
+};
+EXO_HD DD dd_fast_two_sum(double a, double b) {   // |a| >= |b| or a == 0
+  EXO_DD_EXACT
+  const double s = a + b;
+  return DD{s, b - (s - a)};
+}
+EXO_HD DD dd_two_sum(double a, double b) {
+  EXO_DD_EXACT
+  const double s = a + b, bb = s - a;
+  return DD{s, (a - (s - bb)) + (b - bb)};
+}
+EXO_HD DD dd_add(DD a, DD b) {
+  EXO_DD_EXACT
+  DD s = dd_two_sum(a.h, b.h);
+  const DD t = dd_two_sum(a.l, b.l);
+  s = dd_fast_two_sum(s.h, s.l + t.h);
+  return dd_fast_two_sum(s.h, s.l + t.l);
+}
+EXO_HD DD dd_sub(DD a, DD b) { return dd_add(a, DD{-b.h, -b.l}); }
+EXO_HD DD dd_mul_d(DD a, double b) {
+  EXO_DD_EXACT
+  const double p = a.h * b;
+  return dd_fast_two_sum(p, fma(a.l, b, fma(a.h, b, -p)));
+}
+
 // the predicted state indices: slot_mask (nullptr: all) holds one flag per real slot, then one per pair slot
 template <int J, int NR>
 EXO_HD double predict_keep(const DrawCoef<J, NR>& co, const Coefs& cf, const int32_t* EXO_RESTRICT slot_mask, double* keep) {
@@ -120,23 +160,23 @@ EXO_HD void predict_var_lane(const double* EXO_RESTRICT t, const double* EXO_RES
   }
   // backward: B from the last cadence down; a query after cadence i is finished while B is B_(i+1), at t_(i+1)
   double* EXO_RESTRICT out = var + draw * m;
-  Sym<J> B;
+  Sym<J> Bh, Bl;   // B = Bh + Bl
 #pragma unroll
-  for (int k = 0; k < J * (J + 1) / 2; ++k) B.v[k] = 0.0;
+  for (int k = 0; k < J * (J + 1) / 2; ++k) Bh.v[k] = Bl.v[k] = 0.0;
   auto query_bwd = [&](int64_t q, bool have, double tb) {
     const double* EXO_RESTRICT o = wk + (n + q) * row;
     double r[J];
 #pragma unroll
     for (int j = 0; j < J; ++j) r[j] = have ? o[(j + 1) * n_draw] * exp(-co.k[j].c * (tb - tq[q])) : 0.0;
-    double quad = 0.0;
+    DD res{o[0], 0.0};
 #pragma unroll
     for (int j = 0; j < J; ++j) {
-      double s = 0.0;
+      DD s{0.0, 0.0};
 #pragma unroll
-      for (int l = 0; l < J; ++l) s = fma(B(j, l), r[l], s);
-      quad = fma(r[j], s, quad);
+      for (int l = 0; l < J; ++l) s = dd_add(s, dd_mul_d(DD{Bh(j, l), Bl(j, l)}, r[l]));
+      res = dd_sub(res, dd_mul_d(s, r[j]));
     }
-    out[q] = ok ? o[0] - quad : __builtin_nan("");
+    out[q] = ok ? res.h : __builtin_nan("");
   };
   Phi<J> phb;
   double U[J], V[J], W[J];
@@ -151,30 +191,106 @@ EXO_HD void predict_var_lane(const double* EXO_RESTRICT t, const double* EXO_RES
 #pragma unroll
       for (int j = 0; j < J; ++j)
 #pragma unroll
-        for (int l = j; l < J; ++l) B(j, l) *= phb.v[j] * phb.v[l];
+        for (int l = j; l < J; ++l) {   // (one factor at a time: each product exact to the double-double's precision)
+          const DD x = dd_mul_d(dd_mul_d(DD{Bh(j, l), Bl(j, l)}, phb.v[j]), phb.v[l]);
+          Bh(j, l) = x.h;
+          Bl(j, l) = x.l;
+        }
     }
     co.uv(ti, U, V);
     const double* EXO_RESTRICT o = wk + i * row;
     const double id = o[0];
 #pragma unroll
     for (int j = 0; j < J; ++j) W[j] = o[(j + 1) * n_draw];
-    double y[J], s = 0.0;
+    DD y[J], s{id, 0.0};
 #pragma unroll
     for (int j = 0; j < J; ++j) {
-      double v = 0.0;
+      DD v{0.0, 0.0};
 #pragma unroll
-      for (int l = 0; l < J; ++l) v = fma(B(j, l), W[l], v);
+      for (int l = 0; l < J; ++l) v = dd_add(v, dd_mul_d(DD{Bh(j, l), Bl(j, l)}, W[l]));
       y[j] = v;
-      s = fma(W[j], v, s);
+      s = dd_add(s, dd_mul_d(v, W[j]));
     }
-    s += id;
 #pragma unroll
     for (int j = 0; j < J; ++j)
 #pragma unroll
-      for (int l = j; l < J; ++l) B(j, l) = fma(s * U[j], U[l], B(j, l) - fma(U[j], y[l], y[j] * U[l]));
+      for (int l = j; l < J; ++l) {
+        DD x = dd_mul_d(dd_mul_d(s, U[j]), U[l]);
+        x = dd_sub(x, dd_add(dd_mul_d(y[l], U[j]), dd_mul_d(y[j], U[l])));
+        x = dd_add(DD{Bh(j, l), Bl(j, l)}, x);
+        Bh(j, l) = x.h;
+        Bl(j, l) = x.l;
+      }
   }
 #pragma unroll 1
   for (; q >= 0; --q) query_bwd(q, true, t[0]);
+}
+
+// alpha = (K + diag)^-1 y per draw by the published recurrences, one lane per draw, sequential in time: the factorisation with
+// the lower sweep beside it (Fwd<J>: z_i = y_i - U_i . F_i), z / d, then the upper sweep
+//   G_i = E(t_(i+1) - t_i) (G_(i+1) + U_(i+1) alpha_(i+1)),   alpha_i = z_i / d_i - W_i . G_i.
+// The likelihood's reverse pass gives the same vector as a gradient, but its backward error is not that of these sweeps
+// (DESIGN.md section 13.3).  work: W_i, n J doubles per draw laid out [cadence][j][draw].  A draw that meets d <= 0: NaN.
+EXO_HDH int64_t solve_work_doubles(int64_t n, int J, int64_t n_draw) { return n * (int64_t)J * n_draw; }
+
+template <int J>
+EXO_HD void solve_lane(const double* EXO_RESTRICT t, const double* EXO_RESTRICT diag, int64_t n_diag, int64_t n, const Coefs& cf,
+                       const double* EXO_RESTRICT y, double* EXO_RESTRICT alpha, double* EXO_RESTRICT work, int64_t n_draw,
+                       int64_t draw) {
+  DrawCoef<J> co;
+  co.init(cf, draw);
+  const double asum = co.asum();
+  const double* EXO_RESTRICT dg = diag + (n_diag == 1 ? 0 : cf.at(draw) * n);
+  const double* EXO_RESTRICT yr = y + draw * n;
+  double* EXO_RESTRICT ar = alpha + draw * n;
+  double* EXO_RESTRICT wk = work + draw;
+  const int64_t row = (int64_t)J * n_draw;
+  Fwd<J> f;
+#pragma unroll
+  for (int j = 0; j < J; ++j) f.F[j] = f.W[j] = f.U[j] = f.V[j] = 0.0;
+#pragma unroll
+  for (int k = 0; k < J * (J + 1) / 2; ++k) f.S.v[k] = 0.0;
+  f.d = 1.0;
+  f.z = 0.0;
+  Phi<J> phi;
+  bool ok = true;
+#pragma unroll 1
+  for (int64_t i = 0; i < n; ++i) {
+    const double ti = t[i];
+    if (i > 0) {
+      phi.set(co, ti - t[i - 1]);
+      f.advance(phi.v);
+    }
+    co.uv(ti, f.U, f.V);
+    f.measure(yr[i], dg[i] + asum);
+    ok = ok && f.d > 0.0;
+    ar[i] = f.z * f.id;
+    double* EXO_RESTRICT o = wk + i * row;
+#pragma unroll
+    for (int j = 0; j < J; ++j) o[j * n_draw] = f.W[j];
+  }
+  double G[J], U[J], V[J];
+#pragma unroll
+  for (int j = 0; j < J; ++j) G[j] = 0.0;
+  Phi<J> phb;
+#pragma unroll 1
+  for (int64_t i = n - 2; i >= 0; --i) {
+    phb.set(co, t[i + 1] - t[i]);
+    co.uv(t[i + 1], U, V);
+    const double a1 = ar[i + 1];
+    const double* EXO_RESTRICT o = wk + i * row;
+    double acc = ar[i];
+#pragma unroll
+    for (int j = 0; j < J; ++j) {
+      G[j] = phb.v[j] * fma(U[j], a1, G[j]);
+      acc = fma(-o[j * n_draw], G[j], acc);
+    }
+    ar[i] = acc;
+  }
+  if (!ok) {
+#pragma unroll 1
+    for (int64_t i = 0; i < n; ++i) ar[i] = __builtin_nan("");
+  }
 }
 
 }  // namespace gp

@@ -301,13 +301,34 @@ def _known_sorted(t):
 
 
 def _inverse(t, resid, diag, real, cplx, kind):
-    """(K + diag)^-1 resid per draw (detached), resid (D, N): minus the gradient of the log-likelihood with respect to
-    resid -- one forward and one reverse pass of the recurrences"""
-    with torch.enable_grad():
-        r = resid.detach().requires_grad_(True)
-        ll = celerite_loglike(t.detach(), r, diag.detach().contiguous(), real.detach(), cplx.detach(), pair_kind=kind)
-        (g,) = torch.autograd.grad(ll.sum(), r)
-    return -g
+    """(K + diag)^-1 resid per draw (detached), resid (D, N): exo_celerite_solve_f64, the published recurrences (lower
+    sweep, divide by d, upper sweep), one lane per draw.  Not the likelihood's reverse pass, which gives the same vector as
+    minus its gradient with respect to resid: as a SOLVE the time-parallel plan is up to a thousand times further from
+    A alpha = resid than these sweeps (1.6e-8 against 1.5e-11 at N = 1500, diag = 1e-6), K(t*, t) alpha amplifies that, and
+    on a two-minute cadence at a signal-to-noise of 1e6 the sequential reverse pass misses too.
+    Not on the per-step path."""
+    t, y, diag = _dev(t.detach(), "t"), _dev(resid.detach(), "resid"), _dev(diag.detach(), "diag")
+    real, cplx = _dev(real.detach(), "coef_real"), _dev(cplx.detach(), "coef_complex")
+    D, N = y.shape
+    n_real, n_complex = real.shape[1], cplx.shape[1]
+    if t.shape != (N,) or diag.dim() != 2 or diag.shape[1] != N or diag.shape[0] not in (1, D):
+        raise ValueError("shapes: t (N,), resid (D,N), diag (1|D, N)")
+    if real.shape != (D, n_real, 2) or cplx.shape != (D, n_complex, 4):
+        raise ValueError("coef_real (D,Jr,2), coef_complex (D,Jc,4)")
+    if kind is not None:
+        if not kind.is_cuda or kind.dtype != torch.int32 or tuple(kind.shape) != (D, n_complex):
+            raise ValueError("pair_kind must be an int32 device tensor of shape (D, Jc)")
+        kind = kind.contiguous()
+    if not 1 <= n_real + 2 * n_complex <= MAX_J:
+        raise ValueError(f"celerite state width J = {n_real + 2 * n_complex} outside 1..{MAX_J}")
+    lib = _lib.load()
+    nwork = lib.exo_celerite_solve_work_doubles(N, n_real, n_complex, D)
+    work, alpha = _buffer(nwork, device=t.device), _buffer(D, N, device=t.device)
+    with torch.cuda.device(t.device):
+        _lib.check(lib.exo_celerite_solve_f64(_ptr(t), _ptr(diag), diag.shape[0], N, _ptr(real), n_real, _ptr(cplx), n_complex,
+                                              _ptr(kind), D, _ptr(y), _ptr(alpha), _ptr(work), nwork, _stream(t)),
+                   "exo_celerite_solve_f64")
+    return alpha
 
 
 # GaussianProcess.predict(return_var=True): the draws go to exo_celerite_predict_var_f64 in slices whose workspace
@@ -467,8 +488,8 @@ class GaussianProcess:
         return ll[0] if squeeze else ll
 
     def apply_inverse(self, y):
-        """alpha = (K + diag)^-1 (y - mean), per draw (detached).  It is minus the gradient of the
-        log-likelihood with respect to y, i.e. one forward + one reverse pass of the recurrences."""
+        """alpha = (K + diag)^-1 (y - mean), per draw (detached): the published recurrences, one lane per draw
+        (exo_celerite_solve_f64)."""
         t, _, resid, real, cplx, squeeze, _, kind = self._prepare(y)
         alpha = _inverse(t, resid, self._diag, real, cplx, kind)
         return alpha[0] if squeeze else alpha
@@ -643,8 +664,8 @@ class GaussianProcess:
         diag = self._diag.detach()
         lib = _lib.load()
         # bytes per query time of a block: its column of K2(t, t*), the right-hand side and the solution (D x N each), and the
-        # likelihood's state for D right-hand sides
-        per = 8 * (3 * D * N + lib.exo_celerite_state_doubles(N, D, real.shape[1], cplx.shape[1], 0))
+        # scratch of the solve for D right-hand sides
+        per = 8 * (3 * D * N + lib.exo_celerite_solve_work_doubles(N, real.shape[1], cplx.shape[1], D))
         blk = int(max(1, min(M, PREDICT_COV_WORK_BYTES // per)))
         whole = 8 * D * N * M <= PREDICT_COV_WORK_BYTES      # K2(t, t*) for every query time at once
         k_all = _k2_dense(*comp, tt[:, None] - tq[None, :]) if whole else None

@@ -51,8 +51,9 @@ extern "C" {
  * 17: priors and constrained parameters -- exo_prior_block, EXO_PRIOR_*, exo_prior_transform_f64 / _vjp_f64.
  * 18: the white-noise likelihood with a sampled mean and jitter -- exo_transit_noise_vjp_f64, exo_transit_noise_ttv_vjp_f64,
  *     exo_white_noise_terms_f64, exo_white_noise_workspace_bytes; a slightly larger exo_transit_flux_workspace_bytes.
- * 19: the radial-velocity likelihood -- exo_rv_loglike_vjp_f64, EXO_RV_MAX_TREND, EXO_RV_MAX_INST. */
-#define EXO_ABI_VERSION 19
+ * 19: the radial-velocity likelihood -- exo_rv_loglike_vjp_f64, EXO_RV_MAX_TREND, EXO_RV_MAX_INST.
+ * 20: the solve -- exo_celerite_solve_work_doubles, exo_celerite_solve_f64. */
+#define EXO_ABI_VERSION 20
 int32_t exo_abi_version(void);
 
 /* ---------------------------------------------------------------------------
@@ -744,6 +745,23 @@ int exo_celerite_predict_var_f64(const double* t, const double* diag, int64_t n_
                                  int32_t n_complex, const int32_t* pair_kind, const int32_t* slot_mask,
                                  int64_t n_draw, const double* tq, int64_t m, double* var, double* work,
                                  int64_t work_doubles, void* stream);
+
+/* ---------------------------------------------------------------------------
+ * The solve (ABI 20; celerite2's GaussianProcess.apply_inverse):  alpha[d] = (K + diag)^-1 y[d]  by the
+ * published recurrences -- the factorisation with the lower sweep beside it, z / d, the upper sweep --
+ * one lane per draw, sequential in time, O(n J^2).  Its backward error max |A alpha - y| / max |y| is
+ * that of the sequential algorithm, which the reverse pass of the likelihood (the same vector as minus
+ * the gradient with respect to y) does not reach on every input.  t [n] sorted; y, alpha [n_draw][n],
+ * not the same array.  Coefficients, pair kinds and diag as for exo_celerite_loglike_fwd_f64 (n >= 1).
+ * work: device scratch of exo_celerite_solve_work_doubles(n, n_real, n_complex, n_draw) = n J n_draw
+ * doubles, laid out [cadence][j][draw]; its content before the call does not matter (EXO_ERR_WORKSPACE:
+ * too small).  A draw whose factorisation meets d <= 0 gets NaN everywhere.
+ * ------------------------------------------------------------------------- */
+int64_t exo_celerite_solve_work_doubles(int64_t n, int32_t n_real, int32_t n_complex, int64_t n_draw);
+int exo_celerite_solve_f64(const double* t, const double* diag, int64_t n_diag, int64_t n, const double* coef_real,
+                           int32_t n_real, const double* coef_complex, int32_t n_complex,
+                           const int32_t* pair_kind, int64_t n_draw, const double* y, double* alpha,
+                           double* work, int64_t work_doubles, void* stream);
 
 /* ---------------------------------------------------------------------------
  * Record packing: the O(planets) algebra of KeplerianOrbit.__init__

@@ -1430,6 +1430,95 @@ def celerite_loglike(t, y, diag, coeffs):
 
 
 # ---------------------------------------------------------------------------------------------
+# The conditional half (celerite2's apply_inverse / dot_tril / predict) by the published recurrences of SURVEY
+# Appendix B, plain and sequential: the float64 yardstick of tests/gp_cond_cases.py.  No chunks, nothing shared with csrc/.
+# The phases of U, V take t - t[0] (exact for BJD times and spans of years; the kernel depends on time differences only).
+# A pair slot of two real terms (pair_kind 1) is two entries of (ar, cr) here.
+# ---------------------------------------------------------------------------------------------
+def _celerite_uvp(t, coeffs):
+    """(a0, U, V, P): a0 = sum of the amplitudes, U, V (N, J) with the phases of t - t[0], P (N - 1, J) = exp(-c dt)"""
+    t = np.asarray(t, dtype=np.float64)
+    c, a, U, V = celerite_matrices(t - t[0], np.zeros_like(t), coeffs)
+    return a[0], U, V, np.exp(-c[None, :] * np.diff(t)[:, None])
+
+
+def celerite_factor(t, diag, coeffs):
+    """(d (N,), W (N, J)) with K + diag = L diag(d) L^T, L = I + strict_tril(U W^T o P); d <= 0 -> NaN from there on"""
+    a0, U, V, P = _celerite_uvp(t, coeffs)
+    N, J = U.shape
+    a = np.asarray(diag, dtype=np.float64) + np.zeros(N) + a0
+    d = np.empty(N); W = np.empty((N, J))
+    S = np.zeros((J, J))
+    d[0] = a[0]; W[0] = V[0] / d[0]
+    for n in range(1, N):
+        S = np.outer(P[n - 1], P[n - 1]) * (S + d[n - 1] * np.outer(W[n - 1], W[n - 1]))
+        u = S @ U[n]
+        d[n] = a[n] - U[n] @ u
+        if not d[n] > 0:
+            d[n:] = np.nan; W[n:] = np.nan
+            break
+        W[n] = (V[n] - u) / d[n]
+    return d, W
+
+
+def celerite_solve(t, diag, coeffs, y):
+    """(K + diag)^-1 y, y (N,) or (N, R): lower sweep, divide by d, upper sweep"""
+    _, U, V, P = _celerite_uvp(t, coeffs)
+    d, W = celerite_factor(t, diag, coeffs)
+    y = np.asarray(y, dtype=np.float64)
+    z = np.array(y.reshape(y.shape[0], -1))
+    N, J = U.shape
+    F = np.zeros((J, z.shape[1]))
+    for n in range(1, N):
+        F = P[n - 1][:, None] * (F + np.outer(W[n - 1], z[n - 1]))
+        z[n] -= U[n] @ F
+    z /= d[:, None]
+    G = np.zeros((J, z.shape[1]))
+    for n in range(N - 2, -1, -1):
+        G = P[n][:, None] * (G + np.outer(U[n + 1], z[n + 1]))
+        z[n] -= W[n] @ G
+    return z.reshape(y.shape)
+
+
+def celerite_dot_tril(t, diag, coeffs, x):
+    """L sqrt(d) x with K + diag = (L sqrt(d)) (L sqrt(d))^T: a draw from N(0, K + diag) for white x"""
+    _, U, V, P = _celerite_uvp(t, coeffs)
+    d, W = celerite_factor(t, diag, coeffs)
+    y = np.sqrt(d) * np.asarray(x, dtype=np.float64)
+    z = y.copy()
+    F = np.zeros(U.shape[1])
+    for n in range(1, U.shape[0]):
+        F = P[n - 1] * (F + W[n - 1] * y[n - 1])
+        z[n] += U[n] @ F
+    return z
+
+
+def celerite_predict_mean(t, coeffs2, alpha, tq):
+    """K2(tq, t) alpha with the dense cross kernel of the predicted terms ``coeffs2``"""
+    t, tq = np.asarray(t, dtype=np.float64), np.asarray(tq, dtype=np.float64)
+    return celerite_kernel(tq[:, None] - t[None, :], *coeffs2) @ np.asarray(alpha, dtype=np.float64)
+
+
+def celerite_predict_cov(t, diag, coeffs, coeffs2, tq):
+    """K2(tq, tq) - K2(tq, t) (K + diag)^-1 K2(t, tq): one solve per query time"""
+    t, tq = np.asarray(t, dtype=np.float64), np.asarray(tq, dtype=np.float64)
+    K2 = celerite_kernel(t[:, None] - tq[None, :], *coeffs2)
+    if tq.size == 0:
+        return np.zeros((0, 0))
+    return celerite_kernel(tq[:, None] - tq[None, :], *coeffs2) - K2.T @ celerite_solve(t, diag, coeffs, K2)
+
+
+def celerite_predict_var(t, diag, coeffs, coeffs2, tq):
+    """k2(0) - sum_n K2[n] solve(K2)[n] per query time"""
+    t, tq = np.asarray(t, dtype=np.float64), np.asarray(tq, dtype=np.float64)
+    K2 = celerite_kernel(t[:, None] - tq[None, :], *coeffs2)
+    k0 = celerite_kernel(np.zeros(1), *coeffs2)[0]
+    if tq.size == 0:
+        return np.zeros(0)
+    return k0 - np.sum(K2 * celerite_solve(t, diag, coeffs, K2), axis=0)
+
+
+# ---------------------------------------------------------------------------------------------
 # Not a reference function: the conjunction-window bound of the HIP path (exoplanet_amd/csrc/exo_transit.hip,
 # transit_window_kernel), restated so that its defining property -- the window holds every true anomaly at which
 # the disks can overlap -- can be checked on the CPU against brute force (tests/test_window_bound.py).  The

@@ -587,6 +587,16 @@ int harness_gp_dot_tril(const double* t, const double* diag, int64_t n_diag, int
       case 4: gp::dot_tril_lane<4>(t, diag, n_diag, n, cf, x, z, d); break;
       case 5: gp::dot_tril_lane<5>(t, diag, n_diag, n, cf, x, z, d); break;
       case 6: gp::dot_tril_lane<6>(t, diag, n_diag, n, cf, x, z, d); break;
+      case 7: gp::dot_tril_lane<7>(t, diag, n_diag, n, cf, x, z, d); break;
+      case 8: gp::dot_tril_lane<8>(t, diag, n_diag, n, cf, x, z, d); break;
+      case 9: gp::dot_tril_lane<9>(t, diag, n_diag, n, cf, x, z, d); break;
+      case 10: gp::dot_tril_lane<10>(t, diag, n_diag, n, cf, x, z, d); break;
+      case 11: gp::dot_tril_lane<11>(t, diag, n_diag, n, cf, x, z, d); break;
+      case 12: gp::dot_tril_lane<12>(t, diag, n_diag, n, cf, x, z, d); break;
+      case 13: gp::dot_tril_lane<13>(t, diag, n_diag, n, cf, x, z, d); break;
+      case 14: gp::dot_tril_lane<14>(t, diag, n_diag, n, cf, x, z, d); break;
+      case 15: gp::dot_tril_lane<15>(t, diag, n_diag, n, cf, x, z, d); break;
+      case 16: gp::dot_tril_lane<16>(t, diag, n_diag, n, cf, x, z, d); break;
       default: return -1;
     }
   return 0;
@@ -603,6 +613,16 @@ int harness_gp_predict(const double* t, int64_t n, const double* alpha, const do
       case 4: gp::predict_lane<4>(t, n, alpha, cf, tq, m, mu, d); break;
       case 5: gp::predict_lane<5>(t, n, alpha, cf, tq, m, mu, d); break;
       case 6: gp::predict_lane<6>(t, n, alpha, cf, tq, m, mu, d); break;
+      case 7: gp::predict_lane<7>(t, n, alpha, cf, tq, m, mu, d); break;
+      case 8: gp::predict_lane<8>(t, n, alpha, cf, tq, m, mu, d); break;
+      case 9: gp::predict_lane<9>(t, n, alpha, cf, tq, m, mu, d); break;
+      case 10: gp::predict_lane<10>(t, n, alpha, cf, tq, m, mu, d); break;
+      case 11: gp::predict_lane<11>(t, n, alpha, cf, tq, m, mu, d); break;
+      case 12: gp::predict_lane<12>(t, n, alpha, cf, tq, m, mu, d); break;
+      case 13: gp::predict_lane<13>(t, n, alpha, cf, tq, m, mu, d); break;
+      case 14: gp::predict_lane<14>(t, n, alpha, cf, tq, m, mu, d); break;
+      case 15: gp::predict_lane<15>(t, n, alpha, cf, tq, m, mu, d); break;
+      case 16: gp::predict_lane<16>(t, n, alpha, cf, tq, m, mu, d); break;
       default: return -1;
     }
   return 0;

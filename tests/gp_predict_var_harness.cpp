@@ -1,9 +1,10 @@
-// Test harness ONLY: compiles the predictive-variance lane functions (exoplanet_amd/csrc/exo_celerite_predict.hpp) for the
+// Test harness ONLY: compiles the predictive-variance and solve lane functions (exoplanet_amd/csrc/exo_celerite_predict.hpp) for the
 // host (g++) and runs them draw by draw, with the workspace laid out as on the device ([row][quantity][draw]), so that
 // tests/test_gp_predict_var_host.py can check them against the dense definition without a GPU.  Not part of the product.
 #define EXO_HOST_BUILD 1
 #include "../exoplanet_amd/csrc/exo_celerite_predict.hpp"
 
+#include <type_traits>
 #include <utility>
 
 namespace {
@@ -21,9 +22,30 @@ bool dispatch(int J, std::integer_sequence<int, I...>, const double* t, const do
   return ((J == I + 1 ? (run_J<I + 1>(t, diag, n_diag, n, cf, slot_mask, n_draw, tq, m, var, work), true) : false) || ...);
 }
 
+template <int... I>
+bool dispatch_solve(int J, std::integer_sequence<int, I...>, const double* t, const double* diag, int64_t n_diag, int64_t n,
+                    const gp::Coefs& cf, int64_t n_draw, const double* y, double* alpha, double* work) {
+  auto run = [&](auto jj) {
+    for (int64_t d = 0; d < n_draw; ++d) gp::solve_lane<decltype(jj)::value>(t, diag, n_diag, n, cf, y, alpha, work, n_draw, d);
+    return true;
+  };
+  return ((J == I + 1 ? run(std::integral_constant<int, I + 1>{}) : false) || ...);
+}
+
 }  // namespace
 
 extern "C" {
+
+int64_t harness_solve_work_doubles(int64_t n, int J, int64_t n_draw) { return gp::solve_work_doubles(n, J, n_draw); }
+
+// 0: done; 1: J outside 1 .. 16
+int harness_solve(const double* t, const double* diag, int64_t n_diag, int64_t n, const double* coef_real, int n_real,
+                  const double* coef_complex, int n_complex, const int32_t* pair_kind, int64_t n_draw, const double* y,
+                  double* alpha, double* work) {
+  const gp::Coefs cf{coef_real, coef_complex, pair_kind, n_real, n_complex, t};
+  return dispatch_solve(cf.J(), std::make_integer_sequence<int, 16>{}, t, diag, n_diag, n, cf, n_draw, y, alpha, work) ? 0 : 1;
+}
+
 
 int64_t harness_predict_var_work_doubles(int64_t n, int64_t m, int J, int64_t n_draw) {
   return gp::predict_var_work_doubles(n, m, J, n_draw);

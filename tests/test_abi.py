@@ -55,6 +55,17 @@ def test_abi_version_and_host_side_helpers(lib):
     assert lib.exo_celerite_state_doubles(150000, 1024, 0, 1, 64) != a
     assert lib.exo_celerite_state_doubles(100, 3, 0, 0, 0) == -1
     assert lib.exo_celerite_state_doubles(100, 3, 0, 1, -2) == -1
+    # the solve: W of every cadence
+    assert lib.exo_celerite_solve_work_doubles(100, 1, 2, 3) == 100 * 5 * 3
+    assert lib.exo_celerite_solve_work_doubles(100, 0, 0, 3) == -1 and lib.exo_celerite_solve_work_doubles(0, 0, 1, 3) == -1
+    # ... and its argument checks, which return before anything is launched (the pointers are never followed)
+    p = [0x1000 * (k + 1) for k in range(6)]       # t, diag, coef_complex, y, alpha, work
+    call = lambda n_draw, y, alpha, nwork: lib.exo_celerite_solve_f64(p[0], p[1], 1, 100, None, 0, p[2], 1, None, n_draw, y,  # noqa: E731
+                                                                      alpha, p[5], nwork, None)
+    assert call(0, p[3], p[4], 0) == 0                               # no draws: nothing to do
+    assert call(3, p[3], p[3], 100 * 2 * 3) == 1                     # in place: EXO_ERR_INVALID_ARGUMENT
+    assert call(3, p[3], p[4], 100 * 2 * 3 - 1) == 3                 # workspace one double short: EXO_ERR_WORKSPACE
+    assert call(3, None, p[4], 100 * 2 * 3) == 1 and call(-1, p[3], p[4], 100 * 2 * 3) == 1
 
 
 def test_header_layout_constants_match_python(lib):
