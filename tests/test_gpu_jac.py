@@ -53,24 +53,34 @@ def test_jacobian_route_equals_two_sweeps(dev, planets, secondary, window, cmajo
     assert torch.equal(gpa == 0, gpb == 0)
 
 
-def test_jacobian_route_vs_oracle(dev):
-    """the C5 geometry (long cadence, 7 sub-exposures, transit + occultation) through the Jacobian route against the C port"""
+def _route_vs_oracle(dev, D, N, oracle):
     from exoplanet_amd import ops
 
     rng = np.random.default_rng(7)
-    D, N = 6, 20_000
     tt = np.arange(N) * (29.4 / 1440.0)
     rec, c = system(rng, D, 1, True)
     dt, w = P.exposure_stencil(7, 0)
     g = rng.normal(size=(D, N))
-    want_f, want_gp, want_gl = C.transit(tt, rec, c, g, texp=29.4 / 1440.0, stencil_dt=dt, stencil_w=w, secondary=True)
+    want_f, want_gp, want_gl = oracle(tt, rec, c, g, texp=29.4 / 1440.0, stencil_dt=dt, stencil_w=w, secondary=True)
     rt, ct = T(rec, dev).requires_grad_(True), T(c, dev).requires_grad_(True)
+    n_before = ops._JAC_CALLS[0]
     flux = ops.transit_flux(T(tt, dev), rt, ct, flags=ops.FLAG_SECONDARY, texp=T([29.4 / 1440.0], dev), stencil_dt=T(dt, dev),
                             stencil_w=T(w, dev))
-    assert ops._JAC_CALLS[0] > 0
+    assert ops._JAC_CALLS[0] > n_before
     gp, gl = torch.autograd.grad(flux, (rt, ct), grad_outputs=T(g, dev))
     assert want_f.min() < -1e-3
     assert np.abs(flux.detach().cpu().numpy() - want_f).max() < 1e-12
     sl = list(P.GRAD_SLOTS)
     np.testing.assert_allclose(gp.cpu().numpy()[..., sl], want_gp[..., sl], rtol=1e-9, atol=1e-9 * np.abs(want_gp[..., sl]).max())
     np.testing.assert_allclose(gl.cpu().numpy(), want_gl, rtol=1e-9, atol=1e-9 * np.abs(want_gl).max())
+
+
+def test_jacobian_route_vs_oracle(dev):
+    """the C5 geometry (long cadence, 7 sub-exposures, transit + occultation) through the Jacobian route against the C port"""
+    _route_vs_oracle(dev, 6, 20_000, C.transit)
+
+
+def test_jacobian_route_when_a_block_finishes_its_own_draw(dev):
+    """the same geometry at 512 draws x 300 cadences (two transits, two occultations): a draw is one block's work, the value
+    sweep scatters its own values and the contraction's partials need no summing -- against the oracle's numpy port"""
+    _route_vs_oracle(dev, 512, 300, P.transit_flux_vjp)

@@ -42,7 +42,7 @@ class System:
             self.leaves = dict(period=_leaf(period, rng, dev, sh, 1e-4), t0=_leaf(t0, rng, dev, sh, 1e-3),
                                b=_leaf([0.3, 0.5, 0.1], rng, dev, sh), ecc=_leaf([0.1, 0.2, 0.3], rng, dev, sh),
                                omega=_leaf([0.5, -1.0, 2.0], rng, dev, sh), r=_leaf([0.1, 0.06, 0.08], rng, dev, sh))
-        elif name in ("ttv", "record_ttv"):
+        elif name in ("ttv", "record_ttv", "ttv_exposure"):
             self.t = _t(dev, 40.0)
             self.leaves = dict(period=_leaf(3.3, rng, dev, sh), t0=_leaf(0.9, rng, dev, sh), b=_leaf(0.3, rng, dev, sh),
                                r=_leaf(0.08, rng, dev, sh))
@@ -55,7 +55,7 @@ class System:
             # through the records (ops.white_noise_loglike)
             self.leaves["rho_star"] = _leaf(1.3, rng, dev, (draws, 1), 1e-2)
         self.u1, self.u2 = _leaf(0.3, rng, dev, (draws,), 1e-2), _leaf(0.2, rng, dev, (draws,), 1e-2)
-        if name == "exposure":
+        if name.endswith("exposure"):
             self.kw = dict(texp=0.02, oversample=5)
         elif name == "in_transit":
             self.kw = dict(use_in_transit=True)
@@ -257,6 +257,50 @@ def test_fused_likelihood_matches_the_dense_route(dev, name, combo):
         both = (per != 0).sum(-1)
         assert int((both > 1).sum()) > 50, "no simultaneous transits in the test system"
     compare(s, *noise_args(s, combo))
+
+
+def oracle_loglike(s, row, mean, yerr, jitter):
+    """the log-likelihood of one draw from oracle/numpy_port.py's light curve of that draw's parameters"""
+    from oracle import numpy_port as P
+
+    leaf = {k: v[row].detach().cpu().numpy() for k, v in s.leaves.items()}
+    r = leaf.pop("r")
+    if s.ttvs is not None:
+        orbit = P.TTVOrbit(ttvs=[s.ttvs[row].detach().cpu().numpy()], **leaf)
+    else:
+        orbit = P.KeplerianOrbit(**leaf)
+    kw = dict(s.kw)
+    kw.setdefault("use_in_transit", False)
+    f = P.LimbDarkLightCurve(float(s.u1[row].detach()), float(s.u2[row].detach())).get_light_curve(orbit=orbit, r=r, t=s.t.cpu().numpy(), **kw).sum(-1)
+    var = np.broadcast_to(np.asarray(yerr.cpu() if isinstance(yerr, torch.Tensor) else yerr) ** 2 + jitter ** 2, f.shape)
+    res = s.y.cpu().numpy() - mean - f
+    return -0.5 * (res * res / var).sum() - 0.5 * np.log(var).sum() - 0.5 * N * math.log(2 * math.pi)
+
+
+# (system, draws): the routes of the likelihood's launches on both sides of "a block finishes its own draw" (>= 512 draws)
+# that the tests above leave out -- one evaluation per solved cadence with timing tables / light delay, three sweeps without
+# and with timing tables
+ROUTES = [("one_planet", 512), ("ttv", 512), ("light_delay", 512), ("three_planets", 512), ("exposure", 512),
+          ("ttv_exposure", 3), ("ttv_exposure", 512)]
+
+
+@pytest.mark.parametrize("sampled", [False, True], ids=["fixed", "sampled"])
+@pytest.mark.parametrize("name,draws", ROUTES)
+def test_likelihood_routes_by_batch_size(dev, name, draws, sampled):
+    """a fixed mean and no jitter (exo_transit_chi2[_ttv]_vjp_f64) and a sampled mean and jitter (exo_transit_noise[_ttv]_vjp_f64)
+    against the dense route, and the first and last draw's value against the oracle's light curve"""
+    s = system(name, dev, draws)
+    rs = np.random.default_rng(17)
+    if sampled:
+        mean = torch.as_tensor(1 + 1e-4 * rs.normal(size=(draws, 1)), device=dev).requires_grad_(True)
+        jitter = torch.as_tensor(2e-4 * rs.uniform(0.5, 1.5, size=(draws, 1)), device=dev).requires_grad_(True)
+    else:
+        mean, jitter = 1.0 + 5e-5, None
+    ll = compare(s, mean, s.yerr_cad, jitter).detach()
+    for row in (0, draws - 1):
+        m, j = (float(mean[row]), float(jitter[row])) if sampled else (mean, 0.0)
+        want = oracle_loglike(s, row, m, s.yerr_cad, j)
+        assert abs(float(ll[row]) - want) <= 1e-10 * abs(want), (row, float(ll[row]), want)
 
 
 @pytest.mark.parametrize("name", ["one_planet", "three_planets", "ttv"])

@@ -179,3 +179,39 @@ def test_empty_and_ragged(dev):
         t = 1.0 + np.linspace(-0.2, 0.2, n)
         f = ops.transit_flux(T(t, dev), T(rec, dev), T(c, dev))
         np.testing.assert_allclose(f.cpu().numpy(), P.transit_flux(t, rec, c), rtol=0, atol=2e-13)
+
+
+@pytest.mark.parametrize("secondary", [False, True])
+def test_empty_series_gradients_are_zero(dev, secondary):
+    """no cadences, some draws: every gradient entry zeroes its outputs (nothing else is launched, no workspace is needed)"""
+    from exoplanet_amd import _lib, ops
+
+    lib = _lib.load()
+    D, Pn, n_edge = 3, 2, 4
+    flags = ops.FLAG_SECONDARY if secondary else 0
+    rec = torch.zeros(D, Pn, P.NPAR, dtype=torch.float64, device=dev)
+    ld = torch.zeros(D, 6 if secondary else 3, dtype=torch.float64, device=dev)
+    edges = torch.zeros(D, Pn, n_edge, dtype=torch.float64, device=dev)
+    shift = torch.zeros(D, Pn, n_edge + 1, dtype=torch.float64, device=dev)
+    nan = lambda *shape: torch.full(shape, float("nan"), dtype=torch.float64, device=dev)   # noqa: E731
+    p = lambda x: x.data_ptr()                                                              # noqa: E731
+    series = (None, 0, None, 0, None, None, 1, p(rec), p(ld), D, Pn)
+    calls = {
+        "vjp": lambda gp, gl, fd, gs: lib.exo_transit_flux_vjp_f64(*series, flags, None, None, p(gp), p(gl), p(fd), None, 0, None),
+        "jac_vjp": lambda gp, gl, fd, gs: lib.exo_transit_flux_jac_vjp_f64(None, 0, D, Pn, flags, None, None, 0, p(gp), p(gl), p(fd),
+                                                                           None),
+        "vjp_sparse": lambda gp, gl, fd, gs: lib.exo_transit_flux_vjp_sparse_f64(*series, flags | ops.FLAG_SPARSE, None, p(gp), p(gl),
+                                                                                 p(fd), None, 0, 0, None),
+        "ttv_vjp": lambda gp, gl, fd, gs: lib.exo_transit_flux_ttv_vjp_f64(*series, flags, p(edges), p(shift), n_edge, None, None,
+                                                                           p(gp), p(gl), p(gs), p(fd), None, 0, None),
+    }
+    for name, entry in calls.items():
+        gp, gl, fd, gs = nan(D, Pn, P.NPAR), nan(*ld.shape), nan(D), nan(*shift.shape)
+        assert entry(gp, gl, fd, gs) == 0, name
+        torch.cuda.synchronize()
+        for out in (gp, gl, fd) + ((gs,) if name == "ttv_vjp" else ()):
+            assert bool((out == 0).all()), name
+    # ... and through the op (which allocates its own outputs)
+    f, gp, gl = ops.transit_flux_value_and_vjp(torch.zeros(0, dtype=torch.float64, device=dev), rec, ld,
+                                               torch.zeros(D, 0, dtype=torch.float64, device=dev), flags=flags)
+    assert f.shape == (D, 0) and gp.shape == rec.shape and bool((gp == 0).all()) and bool((gl == 0).all())
