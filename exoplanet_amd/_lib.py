@@ -10,7 +10,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # EXOPLANET_AMD_LIB selects another in-tree build of the same ABI (A/B measurements)
 LIB_PATH = os.environ.get("EXOPLANET_AMD_LIB") or os.path.join(_HERE, "lib", "libexoplanet_amd.so")
-ABI_VERSION = 20
+ABI_VERSION = 21
 
 _c_dp = ctypes.c_void_p  # device pointers travel as integers
 _i64 = ctypes.c_int64
@@ -147,6 +147,10 @@ _SIGNATURES = {
     # gtrend, goffset, gjit2, stream
     "exo_rv_loglike_vjp_f64": (ctypes.c_int, [_c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _i64, _i64, _c_dp, _i64, _i32, _c_dp, _i32,
                                               _c_dp, _c_dp, _i32, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp]),
+    # t, rho, cos_theta, sin_theta, var_rho, n_var_rho, var_theta, n_var_theta, n_cad, params, n_draw, jit2_rho, jit2_theta,
+    # loglike, gparams, gjit2_rho, gjit2_theta, stream
+    "exo_astrometry_loglike_vjp_f64": (ctypes.c_int, [_c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _i64, _c_dp, _i64, _i64, _c_dp, _i64,
+                                                      _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp]),
     "exo_orbit_vector_fwd_f64": (ctypes.c_int, [_c_dp, _i64, _c_dp, _i64, _i32, _u32, _c_dp, _c_dp]),
     "exo_orbit_vector_vjp_f64": (ctypes.c_int, [_c_dp, _i64, _c_dp, _i64, _i32, _u32, _c_dp, _c_dp, _c_dp]),
     # t, n_cad, texp, n_texp, stencil_dt, stencil_w, n_sub, params, ld, n_draw, n_planet, flags, obs, ivar, n_ivar,

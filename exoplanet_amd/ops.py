@@ -1613,6 +1613,123 @@ def rv_loglike(t, params, rv, rv_err, trend=None, t_ref=0.0, offset=None, jitter
 
 
 # ------------------------------------------------------------------------------
+# astrometric likelihood (separation and position angle): value and every gradient from one launch
+# ------------------------------------------------------------------------------
+_AST_DATA = {}        # astrometry_loglike: (position angles, error bars) -> cos theta, sin theta, the two variances
+_AST_CAPTURED = {}    # the entries of _AST_DATA that a capture was served from: a graph replays their addresses
+
+
+def _astrometry_data(theta, rho_err, theta_err):
+    """the per-series arrays of exo_astrometry_loglike_vjp_f64 -- (cos theta, sin theta, var_rho, var_theta), the variances
+    as (1,) or (n_cad,) -- made once per series.  Inside a capture nothing new is kept (what is made there belongs to the
+    graph's pool).  An entry that a capture is served from -- GraphedStep warms up eagerly, so the series is here before the
+    capture -- is in the graph by its addresses and held by nothing else, so it moves to _AST_CAPTURED, which is never
+    emptied: a replay after any number of other series reads the arrays it captured (a few kB per captured series, for the
+    life of the process)."""
+    err_key = lambda e: e if not isinstance(e, torch.Tensor) else (e.data_ptr(), e._version, e.numel())  # noqa: E731
+    key = (theta.data_ptr(), theta._version, theta.numel(), err_key(rho_err), err_key(theta_err), str(theta.device))
+    hit = _AST_CAPTURED.get(key) or _AST_DATA.get(key)
+    if hit is not None:
+        if key not in _AST_CAPTURED and torch.cuda.is_current_stream_capturing():
+            _AST_CAPTURED[key] = hit
+        return hit[:4]
+
+    def variance(err, name):
+        if isinstance(err, torch.Tensor):
+            err = _dev(err.detach(), name).reshape(-1)
+            if err.numel() not in (1, theta.numel()):
+                raise ValueError(f"{name} must be a number or one value per epoch")
+            return err * err
+        return _const(float(err) ** 2, theta.device)
+
+    hit = (torch.cos(theta), torch.sin(theta), variance(rho_err, "rho_err"), variance(theta_err, "theta_err"),
+           (theta, rho_err, theta_err))      # (the sources stay alive: their addresses are the key)
+    if not torch.cuda.is_current_stream_capturing():
+        if len(_AST_DATA) >= 4:      # (an entry keeps its arrays alive: a few series at most)
+            _AST_DATA.clear()
+        _AST_DATA[key] = hit
+    return hit[:4]
+
+
+def _ast_per_draw(x, name, D, device):
+    """``x`` (a number, or a 0-d / (1,) / (D,) / (D, 1) tensor) as a 1-D tensor of 1 or D entries"""
+    if isinstance(x, (int, float)):
+        return _const(x, device)
+    x = _dev(x, name)
+    if x.dim() > 2 or (x.dim() == 2 and x.shape[1] != 1):
+        raise ValueError(f"astrometric likelihood: `{name}` has shape {tuple(x.shape)} -- a number or one value per draw, "
+                         "(draws,) or (draws, 1)")
+    x = x.reshape(-1)
+    if x.numel() not in (1, D):
+        raise ValueError(f"astrometric likelihood: `{name}` holds {x.numel()} values, the parameters {D} draws -- a number or "
+                         "one value per draw")
+    return x
+
+
+class _AstrometryLoglike(torch.autograd.Function):
+    """exo_astrometry_loglike_vjp_f64: the forward pass makes the one call and keeps the gradients, the reverse pass scales
+    them by the incoming cotangent.  ``params`` (D, 10), ``jit2_rho`` / ``jit2_theta`` (D,) | None."""
+
+    @staticmethod
+    def forward(ctx, t, rho, cos_theta, sin_theta, var_rho, var_theta, params, jit2_rho, jit2_theta):
+        D = params.shape[0]
+        dev = t.device
+        new = lambda *shape: torch.empty(*shape, dtype=torch.float64, device=dev)  # noqa: E731
+        ll = new(D)
+        gparams = new(D, OV_NPAR) if ctx.needs_input_grad[6] else None
+        gjr = new(D) if jit2_rho is not None and ctx.needs_input_grad[7] else None
+        gjt = new(D) if jit2_theta is not None and ctx.needs_input_grad[8] else None
+        _call("exo_astrometry_loglike_vjp_f64", dev, _ptr(t), _ptr(rho), _ptr(cos_theta), _ptr(sin_theta), _ptr(var_rho),
+              var_rho.numel(), _ptr(var_theta), var_theta.numel(), t.numel(), _ptr(params), D, _ptr(jit2_rho), _ptr(jit2_theta),
+              _ptr(ll), _ptr(gparams), _ptr(gjr), _ptr(gjt), _stream(t))
+        ctx.have = [g is not None for g in (gparams, gjr, gjt)]
+        ctx.save_for_backward(*[g for g in (gparams, gjr, gjt) if g is not None])
+        return ll
+
+    @staticmethod
+    def backward(ctx, gll):
+        gll = gll.contiguous()
+        saved = iter(ctx.saved_tensors)
+        gparams, gjr, gjt = (next(saved) if have else None for have in ctx.have)
+        return (None, None, None, None, None, None, None if gparams is None else gll[:, None] * gparams,
+                None if gjr is None else gll * gjr, None if gjt is None else gll * gjt)
+
+
+def astrometry_loglike(t, params, rho, rho_err, theta, theta_err, rho_jitter=None, theta_jitter=None):
+    """Gaussian log-likelihood (n_draw,) of the observed separations ``rho`` and position angles ``theta`` (n_cad,) of ONE
+    companion, with independent errors ``rho_err`` / ``theta_err`` (each a number or one value per epoch), for ``n_draw``
+    parameter sets, value and every gradient in ONE launch (exo_astrometry_loglike_vjp_f64) -- the reference tutorial's
+
+        rho_model, theta_model = orbit.get_relative_angles(t, parallax)
+        pm.Normal("rho_obs", mu=rho_model, sd=sqrt(rho_err**2 + rho_jitter**2), observed=rho)
+        theta_diff = arctan2(sin(theta_model - theta), cos(theta_model - theta))
+        pm.Normal("theta_obs", mu=theta_diff, sd=sqrt(theta_err**2 + theta_jitter**2), observed=0)
+
+    ``params`` (n_draw, 10) with slots EXO_OV_* as for :func:`orbit_vector` (amplitude -a, times parallax au_per_R_sun for
+    arcseconds).  ``theta`` in any 2 pi convention: the kernel sees its cosine and sine, formed once per series.  Each
+    jitter None, a number or one value per draw.  Differentiable in ``params`` and the jitters (which enter the kernel
+    squared; the chain rule to them is torch's).  ``rho``, ``theta`` and the error bars are data: one that requires grad is
+    refused, not silently dropped (KeplerianOrbit.astrometry_log_likelihood takes the composed route for those)."""
+    t, params, rho, theta = _dev(t, "t").detach(), _dev(params, "params"), _dev(rho, "rho"), _dev(theta, "theta")
+    if t.dim() != 1 or tuple(rho.shape) != tuple(t.shape) or tuple(theta.shape) != tuple(t.shape):
+        raise ValueError("t, rho and theta must be 1-D with one entry per epoch")
+    if params.dim() != 2 or params.shape[-1] != OV_NPAR:
+        raise ValueError(f"params must be (n_draw, {OV_NPAR}): one companion per call")
+    D = params.shape[0]
+    for name, x in (("rho", rho), ("theta", theta), ("rho_err", rho_err), ("theta_err", theta_err)):
+        if isinstance(x, torch.Tensor) and x.requires_grad and torch.is_grad_enabled():
+            raise NotImplementedError(
+                f"astrometric likelihood: `{name}` requires grad, and the fused kernel differentiates the orbit and the jitters "
+                "only; use KeplerianOrbit.astrometry_log_likelihood (it falls back to get_relative_angles and torch)")
+    cos_theta, sin_theta, var_rho, var_theta = _astrometry_data(theta.detach(), rho_err, theta_err)
+    jit2 = []
+    for name, x in (("rho_jitter", rho_jitter), ("theta_jitter", theta_jitter)):
+        x = None if x is None else _ast_per_draw(x, name, D, t.device)
+        jit2.append(None if x is None else (x * x).expand(D).contiguous())
+    return _AstrometryLoglike.apply(t, rho.detach(), cos_theta, sin_theta, var_rho, var_theta, params, jit2[0], jit2[1])
+
+
+# ------------------------------------------------------------------------------
 # record packing: KeplerianOrbit.__init__ algebra + get_cl + windows as one kernel
 # ------------------------------------------------------------------------------
 class _PackRecords(torch.autograd.Function):

@@ -114,6 +114,34 @@ def _rv_loglike_composed(t, params, rv, rv_err, trend=None, t_ref=0.0, offset=No
     return -0.5 * (r * r / s2 + torch.log(s2) + math.log(_TWO_PI)).sum(-1)
 
 
+def _astrometry_loglike_composed(t, params, rho, rho_err, theta, theta_err, rho_jitter=None, theta_jitter=None):
+    """ops.astrometry_loglike written out -- the position op and torch, with the tutorial's wrap of the angle difference --
+    for what the fused kernel does not differentiate (``rho``, ``theta``, per-epoch error bars)"""
+    out = ops.orbit_vector(t, params[:, None, :])                   # (draws, epochs, 1, 3)
+    X, Y = out[:, :, 0, 0], out[:, :, 0, 1]
+    rho_m, theta_m = torch.sqrt(X * X + Y * Y), torch.atan2(Y, X)
+    diff = theta_m - theta
+    delta = torch.atan2(torch.sin(diff), torch.cos(diff))
+
+    def variance(err, jitter):
+        s2 = as_tensor(err, t).to(t.device) ** 2 + torch.zeros_like(rho_m)
+        if jitter is None:
+            return s2
+        return s2 + (jitter.reshape(-1, 1) if isinstance(jitter, torch.Tensor) else jitter) ** 2
+
+    s2r, s2t = variance(rho_err, rho_jitter), variance(theta_err, theta_jitter)
+    r = rho - rho_m
+    return -0.5 * (r * r / s2r + torch.log(s2r) + delta * delta / s2t + torch.log(s2t)).sum(-1) - t.numel() * math.log(_TWO_PI)
+
+
+def _per_draw_count(name, x):
+    """the number of draws of a per-draw argument of astrometry_log_likelihood: a (D,) or (D, 1) tensor, nothing wider"""
+    if x.dim() > 2 or (x.dim() == 2 and x.shape[1] != 1):
+        raise ValueError(f"astrometry_log_likelihood: `{name}` has shape {tuple(x.shape)}; a number or one value per draw, "
+                         "(draws,) or (draws, 1)")
+    return int(x.shape[0])
+
+
 class KeplerianOrbit:
     """A system of bodies on Keplerian orbits around a common central body.
 
@@ -366,6 +394,16 @@ class KeplerianOrbit:
         e = self.ecc.unsqueeze(-2) + torch.zeros_like(M)
         return ops.kepler(M.contiguous(), e.contiguous())
 
+    def _ov_records(self, amp):
+        """the EXO_OV_* records ``(params (D, P, 10), broadcast shape (..., P))`` for the amplitude ``amp``: without an Omega
+        COSO = 1, SINO = 0; a circular orbit is ECC = 0, COSW = 1, SINW = 0"""
+        e, cw, sw = self._ew()
+        one, zero = torch.ones_like(self.n), torch.zeros_like(self.n)
+        cO, sO = (one, zero) if self.Omega is None else (self.cos_Omega, self.sin_Omega)
+        cols = torch.broadcast_tensors(self.n, self.t_periastron, e, cw, sw, self.cos_incl, self.sin_incl, amp, cO, sO)
+        shape = cols[0].shape
+        return torch.stack(cols, dim=-1).reshape(-1, shape[-1], ops.OV_NPAR).contiguous(), shape
+
     def _fused_vector(self, amp, t, velocity, acceleration=False):
         """(X, Y, Z) through ops.orbit_vector -- one launch each way instead of the solve, the radius, three
         rotations and their broadcasts as ~40 launch-bound torch kernels -- or None when the times are not a
@@ -376,12 +414,7 @@ class KeplerianOrbit:
             return None
         if t.requires_grad:      # the op has no cotangent for the times (keplerian_test.py:91-131 differentiates them)
             return None
-        e, cw, sw = self._ew()
-        one, zero = torch.ones_like(self.n), torch.zeros_like(self.n)
-        cO, sO = (one, zero) if self.Omega is None else (self.cos_Omega, self.sin_Omega)
-        cols = torch.broadcast_tensors(self.n, self.t_periastron, e, cw, sw, self.cos_incl, self.sin_incl, amp, cO, sO)
-        shape = cols[0].shape
-        params = torch.stack(cols, dim=-1).reshape(-1, shape[-1], ops.OV_NPAR).contiguous()
+        params, shape = self._ov_records(amp)
         out = ops.orbit_vector(t, params, velocity=velocity, acceleration=acceleration)
         out = out.reshape(tuple(shape[:-1]) + (t.shape[0], shape[-1], 3))
         return out[..., 0], out[..., 1], out[..., 2]
@@ -562,6 +595,74 @@ class KeplerianOrbit:
         needs = lambda x: isinstance(x, torch.Tensor) and x.requires_grad and torch.is_grad_enabled()  # noqa: E731
         route = _rv_loglike_composed if needs(rv) or needs(rv_err) else ops.rv_loglike
         ll = route(t, params, rv, rv_err, trend=trend, t_ref=t_ref, offset=zero_point, jitter=jitter, instrument=instrument)
+        n = 1
+        for b in batch:
+            n *= int(b)
+        if ll.numel() == n:
+            return ll.reshape(batch)
+        return ll
+
+    def astrometry_log_likelihood(self, t, rho, rho_err, theta, theta_err, parallax=None, rho_jitter=None, theta_jitter=None,
+                                  planet=None):
+        """Gaussian log-likelihood (one value per draw) of the observed separations ``rho`` and position angles ``theta`` of
+        one companion with independent errors -- what the reference's astrometry tutorial writes as ``rho_model, theta_model
+        = orbit.get_relative_angles(t, parallax)``, ``pm.Normal("rho_obs", mu=rho_model, sd=sqrt(rho_err**2 + exp(2 *
+        log_rho_s)), observed=rho)``, ``theta_diff = arctan2(sin(theta_model - theta), cos(theta_model - theta))``,
+        ``pm.Normal("theta_obs", mu=theta_diff, sd=sqrt(theta_err**2 + exp(2 * log_theta_s)), observed=0)`` -- value and every
+        gradient in ONE launch (ops.astrometry_loglike).
+
+        ``rho`` is in the units of ``a`` (R_sun), or in arcseconds when ``parallax`` (arcseconds; a number or one value per
+        draw, differentiable) is given.  A per-draw ``parallax`` -- (draws,) or (draws, 1), as the per-draw jitters -- needs an
+        orbit with at most one batch dimension, (draws, planets): with more, a ValueError.  ``theta`` in radians, in any 2 pi convention -- [0, 2 pi) as position angles are
+        usually tabulated, or (-pi, pi] as get_relative_angles returns them: the difference is wrapped.  ``rho_err`` and
+        ``theta_err``: a number or one value per epoch.  ``rho_jitter`` and ``theta_jitter``: None, a number or one value per
+        draw.  ``planet``: for an orbit with several companions the index of the one the data belong to (several companions
+        are several calls).  All of the orbit, ``parallax`` and the jitters are differentiable.  Draw counts that do not
+        agree raise a ValueError.  What the fused form cannot differentiate -- ``rho``, ``theta`` or a per-epoch error bar
+        that requires grad -- takes the position op and torch: slower, never a partial gradient.  An orbit that warps its
+        times (TTVOrbit) is refused: NotImplementedError."""
+        if type(self)._warp_times is not KeplerianOrbit._warp_times:
+            raise NotImplementedError("astrometry_log_likelihood needs a KeplerianOrbit without timing variations: the "
+                                      "position kernels take no time warp")
+        t = as_tensor(t, next((x for x in self._args.values() if isinstance(x, torch.Tensor)), None)).detach()
+        if t.dim() != 1:
+            raise ValueError("t must be 1-D (n_cad,)")
+        amp = -self.a
+        if parallax is not None:
+            par = as_tensor(parallax, amp)
+            if par.dim() >= 1:
+                _per_draw_count("parallax", par)
+                par = par.reshape(-1, 1)      # one value per draw, against (draws, planets)
+                draws = amp.shape[0] if amp.dim() > 1 else 1
+                if amp.dim() > 2 or (par.shape[0] != 1 and draws != 1 and par.shape[0] != draws):
+                    raise ValueError(f"astrometry_log_likelihood: `parallax` holds {par.shape[0]} draws, the orbit has shape "
+                                     f"{tuple(amp.shape)}")
+            amp = amp * par * au_per_R_sun
+        params, shape = self._ov_records(amp)
+        batch, P = tuple(shape[:-1]), int(shape[-1])
+        if planet is None:
+            if P > 1:
+                raise ValueError(f"astrometry_log_likelihood: the orbit has {P} companions; `planet` says whose the data are")
+            planet = 0
+        if not 0 <= int(planet) < P:
+            raise ValueError(f"astrometry_log_likelihood: planet = {planet} of {P} companions")
+        params = params[:, int(planet), :]
+        rho, theta = as_tensor(rho, t).to(t.device), as_tensor(theta, t).to(t.device)
+        # draws of the jitters of ONE system: the record is repeated
+        jitters = (("rho_jitter", rho_jitter), ("theta_jitter", theta_jitter))
+        counts = {name: _per_draw_count(name, x) for name, x in jitters if isinstance(x, torch.Tensor) and x.dim() >= 1}
+        extra = list(counts.values())
+        D = params.shape[0]
+        if D == 1 and max(extra + [1]) > 1:
+            D = max(extra)
+            params = params.expand(D, -1)
+        for name, n_jit in counts.items():
+            if n_jit not in (1, D):
+                raise ValueError(f"astrometry_log_likelihood: `{name}` holds {n_jit} draws, the parameters {D}")
+        needs = lambda x: isinstance(x, torch.Tensor) and x.requires_grad and torch.is_grad_enabled()  # noqa: E731
+        composed = needs(rho) or needs(theta) or needs(rho_err) or needs(theta_err)
+        route = _astrometry_loglike_composed if composed else ops.astrometry_loglike
+        ll = route(t, params.contiguous(), rho, rho_err, theta, theta_err, rho_jitter=rho_jitter, theta_jitter=theta_jitter)
         n = 1
         for b in batch:
             n *= int(b)

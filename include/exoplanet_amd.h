@@ -52,8 +52,9 @@ extern "C" {
  * 18: the white-noise likelihood with a sampled mean and jitter -- exo_transit_noise_vjp_f64, exo_transit_noise_ttv_vjp_f64,
  *     exo_white_noise_terms_f64, exo_white_noise_workspace_bytes; a slightly larger exo_transit_flux_workspace_bytes.
  * 19: the radial-velocity likelihood -- exo_rv_loglike_vjp_f64, EXO_RV_MAX_TREND, EXO_RV_MAX_INST.
- * 20: the solve -- exo_celerite_solve_work_doubles, exo_celerite_solve_f64. */
-#define EXO_ABI_VERSION 20
+ * 20: the solve -- exo_celerite_solve_work_doubles, exo_celerite_solve_f64.
+ * 21: the astrometric likelihood -- exo_astrometry_loglike_vjp_f64. */
+#define EXO_ABI_VERSION 21
 int32_t exo_abi_version(void);
 
 /* ---------------------------------------------------------------------------
@@ -547,6 +548,43 @@ int exo_orbit_vector_fwd_f64(const double* t, int64_t n_cad, const double* param
                              uint32_t flags, double* out, void* stream);
 int exo_orbit_vector_vjp_f64(const double* t, int64_t n_cad, const double* params, int64_t n_draw, int32_t n_planet,
                              uint32_t flags, const double* gout, double* gparams, void* stream);
+
+/* ---------------------------------------------------------------------------
+ * Gaussian log-likelihood of an observed astrometric series -- separation rho_n and position angle theta_n of ONE companion
+ * at the epochs t_n, with independent errors -- value and every gradient in ONE launch: the tutorial's
+ *   rho_model, theta_model = orbit.get_relative_angles(t, parallax);
+ *   pm.Normal("rho_obs", mu=rho_model, sd=sqrt(rho_err**2 + exp(2 log_rho_s)), observed=rho_data)
+ *   theta_diff = arctan2(sin(theta_model - theta_data), cos(theta_model - theta_data))      (the wrap across the branch cut)
+ *   pm.Normal("theta_obs", mu=theta_diff, sd=sqrt(theta_err**2 + exp(2 log_theta_s)), observed=0)
+ * for n_draw parameter sets.  rec[d] is an EXO_OV_* record (above) and (X, Y) = AMP R (u, v) the sky-plane position of the
+ * position mode (flags = 0) at t_n:
+ *   rho_m   = sqrt(X^2 + Y^2)
+ *   delta   = atan2(Y c_n - X s_n,  X c_n + Y s_n)          (c_n, s_n) = (cos, sin) theta_n
+ *           = atan2(sin(theta_m - theta_n), cos(theta_m - theta_n)),  theta_m = atan2(Y, X), in (-pi, pi]: theta_m is never
+ *             formed, the data's cos / sin are formed once by the caller, and theta_n may be given in any 2 pi convention
+ *   s2r = var_rho[n_var_rho == 1 ? 0 : n] + jit2_rho[d]        wr = 1 / s2r     r = rho_n - rho_m     kappa  = wr r
+ *   s2t = var_theta[n_var_theta == 1 ? 0 : n] + jit2_theta[d]  wt = 1 / s2t                           lambda = -wt delta
+ *   loglike[d]     = -1/2 sum_n (wr r^2 + log s2r + wt delta^2 + log s2t) - n_cad log(2 pi)
+ *   gparams[d]     = d loglike / d rec[d]      (EXO_OV_NPAR doubles: the reverse pass of the position with the cotangents
+ *                    d loglike / d (X, Y, Z) = (kappa X / rho_m - lambda Y / rho_m^2, kappa Y / rho_m + lambda X / rho_m^2, 0))
+ *   gjit2_rho[d]   = 1/2 sum_n (kappa^2 - wr)
+ *   gjit2_theta[d] = 1/2 sum_n (lambda^2 - wt)
+ * t, rho, cos_theta, sin_theta [n_cad]; var_rho [n_var_rho], var_theta [n_var_theta], each count 1 or n_cad.  params
+ * [n_draw][EXO_OV_NPAR]: one companion per call (AMP = -a, times parallax au_per_R_sun for arcseconds; COSO = 1, SINO = 0
+ * without an Omega; ECC = 0, COSW = 1, SINW = 0 when circular).  jit2_rho, jit2_theta [n_draw]; either may be null (zero).
+ * loglike [n_draw]; gparams [n_draw][EXO_OV_NPAR], gjit2_rho, gjit2_theta [n_draw]: a null gradient output is not written,
+ * and without gparams the reverse arithmetic is skipped.  ECC outside [0, 1) gives NaN in that draw only; so does a model
+ * separation of exactly 0 (no direction).  No workspace: one workgroup per draw, whose width depends on n_cad alone, every sum
+ * in a fixed order (bit-reproducible, and a draw's results do not depend on the batch it is in).  Sizes are checked first,
+ * then the required pointers, before any launch; n_draw == 0: EXO_OK, nothing launched.  n_cad == 0 with n_draw > 0 (n_var_*
+ * = 1; the series' pointers are not read and may be null): the sums are empty -- loglike = 0 and every gradient output that is
+ * passed is written as 0.  A gradient output of a jitter may be passed where that jit2 is null: it is the derivative at zero.
+ * ------------------------------------------------------------------------- */
+int exo_astrometry_loglike_vjp_f64(const double* t, const double* rho, const double* cos_theta, const double* sin_theta,
+                                   const double* var_rho, int64_t n_var_rho, const double* var_theta, int64_t n_var_theta,
+                                   int64_t n_cad, const double* params, int64_t n_draw, const double* jit2_rho,
+                                   const double* jit2_theta, double* loglike, double* gparams, double* gjit2_rho,
+                                   double* gjit2_theta, void* stream);
 
 /* ---------------------------------------------------------------------------
  * celerite GP log-likelihood, value + VJP, for n_draw independent (kernel,
