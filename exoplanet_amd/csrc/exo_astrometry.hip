@@ -23,11 +23,6 @@ namespace {
 
 using namespace exo::ast;
 
-__device__ __forceinline__ double wave_sum(double v) {
-  for (int o = kWave / 2; o > 0; o >>= 1) v += __shfl_down(v, o, kWave);
-  return v;
-}
-
 template <int BLOCK>
 __global__ __launch_bounds__(BLOCK) void astrometry_loglike_kernel(
     const double* __restrict__ t, const double* __restrict__ rho, const double* __restrict__ cos_theta,

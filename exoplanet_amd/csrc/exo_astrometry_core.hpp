@@ -6,18 +6,21 @@
 // exo_rv_core.hpp's ov_sample<0> / ov_vjp_term<0>.  Definitions: include/exoplanet_amd.h, exo_astrometry_loglike_vjp_f64.
 #pragma once
 #include "../../include/exoplanet_amd.h"
+#include "exo_draw_block.hpp"
 #include "exo_math.hpp"
 #include "exo_rv_core.hpp"
 
 namespace exo {
 namespace ast {
 
-constexpr int kWave = 64;
-constexpr int kNarrowCad = 128;   // up to this many epochs one wave takes the draw, above four do (exo_rv_like_core.hpp's rule)
-constexpr int kNarrow = 64, kWide = 256;
-
-// the width of a draw's workgroup: from the length of the series alone, never from the number of draws
-constexpr int block_threads(int64_t n_cad) { return n_cad <= kNarrowCad ? kNarrow : kWide; }
+using draw::block_threads;
+using draw::kNarrow;
+using draw::kNarrowCad;
+using draw::kWave;
+using draw::kWide;
+#ifndef EXO_HOST_BUILD
+using draw::wave_sum;
+#endif
 
 // slots of the per-draw reduction: the halves of the value, the record's cotangent, the two jitters
 constexpr int kChiR = 0, kLogR = 1, kChiT = 2, kLogT = 3, kRec = 4, kJitR = kRec + EXO_OV_NPAR, kJitT = kJitR + 1,

@@ -7,13 +7,15 @@
 #include <stdint.h>
 
 #include "../../include/exoplanet_amd.h"
+#include "exo_draw_block.hpp"
 #include "exo_estimators_core.hpp"
 
 namespace {
 
 using namespace est;
+using exo::draw::kWave;
+using exo::draw::wave_sum;
 
-constexpr int kWave = 64;
 constexpr int kPrepThreads = 1024;
 constexpr int kBlsThreads = 256;     // histogram in LDS: one workgroup per (period, series)
 constexpr int kSlabThreads = 1024;   // histogram in the workspace: persistent workgroups, one slab each
@@ -37,11 +39,6 @@ struct Layout {
   __host__ __device__ int64_t wy(int64_t b) const { return head() + n + n_w * n + b * n; }
   __host__ __device__ int64_t slabs() const { return head() + n + n_w * n + n_series * n; }
 };
-
-__device__ __forceinline__ double wave_sum(double v) {
-  for (int o = kWave / 2; o > 0; o >>= 1) v += __shfl_down(v, o, kWave);
-  return v;
-}
 
 // sum over the workgroup, valid in thread 0 (scratch: one double per wave)
 __device__ __forceinline__ double block_sum(double v, double* scratch) {

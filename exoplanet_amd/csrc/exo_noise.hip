@@ -14,22 +14,19 @@
 #include <stdint.h>
 
 #include "../../include/exoplanet_amd.h"
+#include "exo_draw_block.hpp"
 #include "exo_noise_core.hpp"
 
 namespace {
 
 using namespace nz;
+using exo::draw::kWave;
+using exo::draw::wave_sum;
 
-constexpr int kWave = 64;
 constexpr int kSeriesThreads = 1024;
 constexpr int kThreads = 256;
 constexpr int kTile = 4;          // draws per lane: 4 x (4 sums + mantissa product + exponent) = 44 registers of accumulators
 constexpr int kMaxBlocksX = 64;   // blocks along the cadences
-
-__device__ __forceinline__ double wave_sum(double v) {
-  for (int o = kWave / 2; o > 0; o >>= 1) v += __shfl_down(v, o, kWave);
-  return v;
-}
 
 // sum over the workgroup in a fixed order, valid in every thread (scratch: one double per wave + 1)
 __device__ __forceinline__ double block_sum_all(double v, double* scratch) {

@@ -27,11 +27,6 @@ using namespace exo::rvl;
 
 constexpr int kSlots = kScalars + EXO_MAX_PLANETS * EXO_RV_NPAR;
 
-__device__ __forceinline__ double wave_sum(double v) {
-  for (int o = kWave / 2; o > 0; o >>= 1) v += __shfl_down(v, o, kWave);
-  return v;
-}
-
 template <int BLOCK>
 __global__ __launch_bounds__(BLOCK) void rv_loglike_kernel(
     const double* __restrict__ t, const double* __restrict__ tau, const int32_t* __restrict__ inst, const double* __restrict__ rv,

@@ -6,19 +6,23 @@
 // Definitions: include/exoplanet_amd.h, exo_rv_loglike_vjp_f64.
 #pragma once
 #include "../../include/exoplanet_amd.h"
+#include "exo_draw_block.hpp"
 #include "exo_math.hpp"
 #include "exo_rv_core.hpp"
 
 namespace exo {
 namespace rvl {
 
-constexpr int kWave = 64;
-constexpr int kTile = 1024;       // epochs whose rho is kept (LDS) between the two passes
-constexpr int kNarrowCad = 128;   // up to this many epochs one wave takes the draw, above four do
-constexpr int kNarrow = 64, kWide = 256;
+using draw::block_threads;
+using draw::kNarrow;
+using draw::kNarrowCad;
+using draw::kWave;
+using draw::kWide;
+#ifndef EXO_HOST_BUILD
+using draw::wave_sum;
+#endif
 
-// the width of a draw's workgroup: from the length of the series alone, never from the number of draws
-constexpr int block_threads(int64_t n_cad) { return n_cad <= kNarrowCad ? kNarrow : kWide; }
+constexpr int kTile = 1024;       // epochs whose rho is kept (LDS) between the two passes
 
 // slots of the per-draw reduction: the two halves of the value, then the gradients
 constexpr int kChi = 0, kLog = 1, kTrend = 2, kOff = kTrend + EXO_RV_MAX_TREND, kJit = kOff + EXO_RV_MAX_INST,

@@ -248,10 +248,9 @@ class LimbDarkLightCurve:
 
         if orbit is None or r is None or t is None or y is None or yerr is None:
             raise ValueError("orbit, r, t, y and yerr are required")
-        needs = lambda x: isinstance(x, torch.Tensor) and x.requires_grad and torch.is_grad_enabled()  # noqa: E731
         n_cad = as_tensor(t).numel()
         per_draw = ops.per_draw_yerr(yerr, n_cad) is not None
-        if needs(y) or (needs(yerr) and not per_draw):
+        if ops.needs_grad(y) or (ops.needs_grad(yerr) and not per_draw):
             lc = self.get_light_curve(orbit=orbit, r=r, t=t, texp=texp, oversample=oversample, order=order,
                                       use_in_transit=use_in_transit, light_delay=light_delay, total=True)
             # (a (draws,) mean / jitter is per draw, as on the fused route: a column against the (draws, cadences) curve)

@@ -18,6 +18,7 @@ has value + gradient (torch.autograd).  There is no CPU / eager fallback.
 import ctypes
 import os
 import warnings
+from types import SimpleNamespace
 from typing import NamedTuple, Optional
 
 import numpy as np
@@ -47,6 +48,25 @@ _SORTED = {}
 _VOUCHED = {}
 
 
+def _capturing():
+    """whether the current stream is being captured into a hipGraph (the one place that asks)"""
+    return torch.cuda.is_current_stream_capturing()
+
+
+def needs_grad(x):
+    """whether autograd will want a gradient with respect to ``x``"""
+    return isinstance(x, torch.Tensor) and x.requires_grad and torch.is_grad_enabled()
+
+
+def _refuse_data_grad(what, differentiates, instead, **named):
+    """the data of the likelihood ``what`` carry no gradient through its fused kernels: one of ``named`` that requires grad
+    is refused rather than answered with a partial gradient"""
+    for name, x in named.items():
+        if needs_grad(x):
+            raise NotImplementedError(f"{what}: `{name}` requires grad, and the fused kernels differentiate {differentiates} "
+                                      f"only; use {instead}")
+
+
 def _series_key(t):
     return (t.device.index, t.data_ptr(), t.numel(), t.stride(0) if t.dim() else 0)
 
@@ -61,7 +81,7 @@ def vouch_sorted(t):
     ``release_sorted(t)`` takes the word back."""
     if not (torch.is_tensor(t) and t.is_cuda):
         raise RuntimeError("vouch_sorted: a device tensor, please")
-    if torch.cuda.is_current_stream_capturing():
+    if _capturing():
         raise RuntimeError("vouch_sorted looks at the array (a host synchronisation): call it before the capture")
     if t.numel() > 1 and not bool((t[1:] >= t[:-1]).all()):
         raise ValueError("vouch_sorted: the times are not non-decreasing (or hold a NaN)")
@@ -102,7 +122,7 @@ def known_sorted(t, unknown=True, nan_ok=True):
         return unknown
     hit = _SORTED.get(key)
     if hit is None:
-        if torch.cuda.is_current_stream_capturing():
+        if _capturing():
             return unknown   # cannot look during a capture; the warm-up runs before it did
         both = torch.stack([~(t[1:] < t[:-1]).any(), (t[1:] >= t[:-1]).all()]).cpu()     # one synchronisation
         if len(_SORTED) >= 8:      # (an entry keeps its time array alive: a handful of series, not dozens -- ADVICE r2)
@@ -122,7 +142,7 @@ def _sorted_flag(t):
         return 0
     if _series_key(t) in _VOUCHED:
         return FLAG_SORTED_TIMES
-    if torch.cuda.is_current_stream_capturing():
+    if _capturing():
         return 0
     return FLAG_SORTED_TIMES if known_sorted(t, unknown=False, nan_ok=False) else 0
 
@@ -409,7 +429,7 @@ def _jac_fits(nbytes, device):
     if hit is not None:
         return hit
     try:
-        if torch.cuda.is_current_stream_capturing():
+        if _capturing():
             return True          # (no warm-up call asked before this capture: nothing to agree with; not remembered)
         free, _ = torch.cuda.mem_get_info(device)
         free += torch.cuda.memory_reserved(device) - torch.cuda.memory_allocated(device)
@@ -646,18 +666,61 @@ class _TransitChi2(torch.autograd.Function):
         return (None, None, None, None, gchi2[:, None, None] * gparams, gchi2[:, None] * gld, None, None, None, None, gshift)
 
 
-_CONSTS = {}
-_WN_CACHE = {}     # white_noise_loglike: (series, error bars, mean) -> residuals, weights, constants
+class _SeriesCache:
+    """What a likelihood derives from the data alone (residuals, variances, cos / sin of the angles, int32 instruments), made
+    once per series: a sampler calls with the same series thousands of times.  One rule for every likelihood:
+
+    * the key is (address, version, shape, strides, device) of every source tensor and the value of every number; the entry
+      holds its sources, so an address cannot pass to another series while the entry lives;
+    * at most ``capacity`` entries are kept; a further one empties the store first (a few series at most: no LRU);
+    * a miss while the stream is being captured into a hipGraph is made and returned but not kept: its arrays belong to the
+      graph's pool;
+    * a hit while capturing -- GraphedStep warms up eagerly, so the series is here before the capture -- is in the graph by
+      its addresses and held by nothing else, so the entry moves to ``pinned``, which is never emptied: a replay after any
+      number of other series reads the arrays it captured (a few kB per captured series, for the life of the process).
+
+    ``capturing``: the question, injectable so that the rule can be tested without a device."""
+
+    def __init__(self, capacity=4, capturing=_capturing):
+        self.capacity, self.capturing = capacity, capturing
+        self.kept, self.pinned = {}, {}
+
+    @staticmethod
+    def key(sources):
+        return tuple((x.data_ptr(), x._version, x.shape, x.stride(), x.device) if isinstance(x, torch.Tensor)
+                     else x if x is None or isinstance(x, str) else float(x) for x in sources)
+
+    def get(self, sources, make):
+        """the entry of ``sources`` (tensors, numbers, None): ``.value`` is what ``make()`` returned, ``.sources`` the sources"""
+        key = self.key(sources)
+        entry = self.pinned.get(key)
+        if entry is not None:
+            return entry
+        entry = self.kept.get(key)
+        capturing = self.capturing()
+        if entry is None:
+            entry = SimpleNamespace(sources=sources, value=make())
+            if not capturing:
+                if len(self.kept) >= self.capacity:
+                    self.kept.clear()
+                self.kept[key] = entry
+        elif capturing:
+            self.pinned[key] = self.kept.pop(key)
+        return entry
+
+
+_CONSTS = _SeriesCache(capacity=256)    # a handful of error bars in practice: never let a sweep over values grow it
+_WN_TERMS = _SeriesCache()     # white_noise_loglike: (series, error bars, mean) -> residuals, weights, constants
+_NZ_DATA = _SeriesCache()      # sampled mean / jitter: (series, error bars) -> _NoiseData
+_RV_SERIES = _SeriesCache()    # rv_loglike: (epochs, error bars, reference time, instruments) -> tau, variances, int32 instruments
+_AST_SERIES = _SeriesCache()   # astrometry_loglike: (position angles, error bars) -> cos theta, sin theta, the two variances
 
 
 def _const(value, device):
-    """a one-element float64 device tensor holding ``value`` (cached per device: created once, outside any capture)"""
-    key = (float(value), str(device))
-    if key not in _CONSTS:
-        if len(_CONSTS) >= 256:      # a handful of error bars in practice: never let a sweep over values grow it
-            _CONSTS.clear()
-        _CONSTS[key] = torch.tensor([float(value)], dtype=torch.float64, device=device)
-    return _CONSTS[key]
+    """a one-element float64 device tensor holding ``value`` (cached per device: created once, outside any capture; one that
+    a capture was handed stays for good, like a captured series)"""
+    value = float(value)
+    return _CONSTS.get((value, str(device)), lambda: torch.tensor([value], dtype=torch.float64, device=device)).value
 
 
 def transit_chi2(t, params, ld, obs, ivar, texp=None, stencil_dt=None, stencil_w=None, flags=0, ttv=None):
@@ -675,32 +738,24 @@ def transit_chi2(t, params, ld, obs, ivar, texp=None, stencil_dt=None, stencil_w
 def _white_noise_terms(y, yerr, mean):
     """(y - mean, weights, sum w (y - mean)^2, sum log(w / 2 pi), and the likelihood's constant term (the last minus the
     one before, halved)) of a white-noise likelihood"""
-    # what depends on the data alone (residual series, weights, the two constants of the likelihood) is computed once per
-    # (y, yerr, mean): a sampler calls this thousands of times with the same series
-    key = None
-    if isinstance(mean, (int, float)) and not y.requires_grad and (isinstance(yerr, (int, float)) or not yerr.requires_grad):
-        # (keyed by the tensor OBJECTS, which the entry keeps alive -- an address alone could be handed to another series)
-        key = (id(y), y._version, float(mean),
-               float(yerr) if isinstance(yerr, (int, float)) else (id(yerr), yerr._version))
-    hit = _WN_CACHE.get(key) if key is not None else None
-    if hit is not None and not (hit[4] is y and (isinstance(yerr, (int, float)) or hit[5] is yerr)):
-        hit = None
-    if hit is None:
-        if isinstance(yerr, (int, float)):
+    number = isinstance(yerr, (int, float))
+
+    def make():
+        if number:
             ivar = _const(1.0 / (float(yerr) * float(yerr)), y.device)      # cached: no upload inside a hipGraph capture
         else:
-            yerr = _dev(yerr, "yerr")
-            ivar = (1.0 / (yerr * yerr)).reshape(-1)
+            err = _dev(yerr, "yerr")
+            ivar = (1.0 / (err * err)).reshape(-1)
         obs = y - mean
         n = y.numel()
         const = (ivar * obs * obs).sum() if ivar.numel() == n else ivar[0] * (obs * obs).sum()
         lognorm = torch.log(ivar / (2.0 * torch.pi)).sum() * (1.0 if ivar.numel() == n else float(n))
-        hit = (obs, ivar, const, lognorm, y, yerr, 0.5 * (lognorm - const))
-        if key is not None:
-            if len(_WN_CACHE) >= 4:      # (an entry keeps y, its residuals and weights alive: a few series at most)
-                _WN_CACHE.clear()
-            _WN_CACHE[key] = hit
-    return hit[:4] + (hit[6],)
+        return obs, ivar, const, lognorm, 0.5 * (lognorm - const)
+
+    # what depends on the data alone is computed once per (y, yerr, mean) -- where nothing of it requires grad
+    if isinstance(mean, (int, float)) and not y.requires_grad and (number or not yerr.requires_grad):
+        return _WN_TERMS.get((y, yerr, mean), make).value
+    return make()
 
 
 def per_draw_yerr(yerr, n_cad):
@@ -714,16 +769,16 @@ def per_draw_yerr(yerr, n_cad):
     return None
 
 
+_WN = "white-noise likelihood"
+_WN_INSTEAD = ("LimbDarkLightCurve.white_noise_log_likelihood (it falls back to the dense light curve) or "
+               "get_light_curve(total=True) with torch")
+
+
 def _check_data_terms(y, yerr, mean):
     """the data-side terms of the white-noise likelihood carry no gradient through the fused kernels: refuse rather than
     return a partial gradient (jitter per chain: a (n_draw, 1) ``yerr``; anything else: the dense light curve + torch)"""
-    for name, x in (("y", y), ("yerr", yerr), ("mean", mean)):
-        if isinstance(x, torch.Tensor) and x.requires_grad and torch.is_grad_enabled():
-            raise NotImplementedError(
-                f"white-noise likelihood: `{name}` requires grad, and the fused kernels differentiate only the orbit / "
-                "limb-darkening parameters (plus per-draw error bars, yerr of shape (n_draw, 1)); use "
-                "LimbDarkLightCurve.white_noise_log_likelihood (it falls back to the dense light curve) or "
-                "get_light_curve(total=True) with torch")
+    _refuse_data_grad(_WN, "the orbit, the limb darkening and per-draw error bars (yerr of shape (n_draw, 1))", _WN_INSTEAD,
+                      y=y, yerr=yerr, mean=mean)
 
 
 def _scaled_loglike(unit_fn, y, yerr_d, mean):
@@ -742,14 +797,7 @@ def _scaled_loglike(unit_fn, y, yerr_d, mean):
     return -0.5 * w * (chi2 + s2) + 0.5 * n * torch.log(w / (2.0 * torch.pi))
 
 
-# sampled mean / jitter: (series, error bars) -> variances and the per-series sums of the data terms.  Like _WN_CACHE's
-# residuals and weights, the variances of an entry live as long as the entry (or the caller's own tensors) does: a captured
-# graph that read them must not be replayed after the entry is gone.  The per-series sums (64 B) outlive the entry once a
-# graph holds their address: a capture after a warm-up reads the sums the warm-up filled and pins them in _NZ_PINNED; a
-# capture without one gets a buffer from the graph's own pool and fills it on every replay.
-_NZ_CACHE = {}
-_NZ_PINNED = {}
-_NOISE_SERIES = 8   # doubles of exo_white_noise_terms_f64's `series`
+_NOISE_SERIES = 8  # doubles of exo_white_noise_terms_f64's `series`
 _LOG_2PI = 1.8378770664093453
 
 
@@ -758,41 +806,44 @@ class _NoiseData:
     exo_white_noise_terms_f64 fills on its first eager call on a stream and reads in every later call on THAT stream
     (one buffer per stream: a call on another stream never reads sums that are still being written)"""
 
-    def __init__(self, y, yerr, var):
-        self.y, self.yerr, self.var = y, yerr, var
+    def __init__(self, y, var):
+        self.y, self.var = y, var
         self.series = {}     # stream -> filled buffer
 
 
 def _noise_data(y, yerr):
-    """the :class:`_NoiseData` of a series and its error bars (a number or a per-cadence tensor), kept per (y, yerr) like
-    :func:`_white_noise_terms` keeps its constants: a sampler calls with the same series thousands of times"""
-    number = isinstance(yerr, (int, float))
-    key = (id(y), y._version, float(yerr) if number else (id(yerr), yerr._version))
-    hit = _NZ_CACHE.get(key)
-    if hit is not None and hit.y is y and (number or hit.yerr is yerr):
-        return hit
-    if number:
-        var = _const(float(yerr) * float(yerr), y.device)
-    else:
-        yerr = _dev(yerr, "yerr")
-        var = (yerr * yerr).reshape(-1)
+    """the :class:`_NoiseData` of a series and its error bars (a number or a per-cadence tensor), made once per (y, yerr)"""
+    def make():
+        if isinstance(yerr, (int, float)):
+            return _NoiseData(y, _const(float(yerr) * float(yerr), y.device))
+        err = _dev(yerr, "yerr")
+        var = (err * err).reshape(-1)
         if var.numel() not in (1, y.numel()):
             raise ValueError("yerr must be a number, one entry per cadence, or per draw: (n_draw, 1)")
-    hit = _NoiseData(y, yerr, var)
-    if len(_NZ_CACHE) >= 4:      # (an entry keeps y and its variances alive: a few series at most)
-        _NZ_CACHE.clear()
-    _NZ_CACHE[key] = hit
-    return hit
+        return _NoiseData(y, var)
+
+    return _NZ_DATA.get((y, yerr), make).value
 
 
-def _per_draw(x, name, D, device):
-    """``x`` (a number, or a 0-d / (D,) / (D, 1) / (1, 1) tensor) as a (1,) or (D,) tensor"""
+def _dev_or_number(x, name):
+    return x if isinstance(x, (int, float)) else _dev(x, name)
+
+
+def _per_draw(x, name, D, device, what, columns=False):
+    """``x`` -- a number, or a 0-d / (1,) / (D,) / (D, 1) / (1, 1) device tensor -- as a 1-D tensor of 1 or D entries, one
+    per draw of the likelihood ``what``; ``columns``: a (D, k) tensor as well, and the result is 2-D, of 1 or D rows"""
     if isinstance(x, (int, float)):
-        return _const(x, device)
-    x = _dev(x, name).reshape(-1).contiguous()
-    if x.numel() not in (1, D):
-        raise ValueError(f"white-noise likelihood: `{name}` holds {x.numel()} draws, the parameters {D} -- one value, or one per draw")
-    return x
+        x = _const(x, device)
+        return x.reshape(1, 1) if columns else x
+    if x.dim() > 2 or (x.dim() == 2 and not columns and x.shape[1] != 1):
+        raise ValueError(f"{what}: `{name}` has shape {tuple(x.shape)} -- a number, one value per draw, or "
+                         + ("(draws, instruments)" if columns else "(draws,) or (draws, 1)"))
+    n = x.shape[0] if x.dim() == 2 else x.numel()
+    if n not in (1, D):
+        raise ValueError(f"{what}: `{name}` holds {n} draws, the parameters {D} -- one value, or one per draw")
+    if columns:
+        return x if x.dim() == 2 else x.reshape(-1, 1)
+    return x if x.dim() == 1 else x.reshape(-1)
 
 
 def _noise_launch(a, flags, ttv_edges, ttv_shift, data, var, mean, jit2):
@@ -815,7 +866,7 @@ def _noise_launch(a, flags, ttv_edges, ttv_shift, data, var, mean, jit2):
         _call("exo_transit_noise_ttv_vjp_f64", dev, *a.head(flags), _ptr(edges), _ptr(shift), n_edge, *noise, _ptr(gshift), *tail)
     else:
         _call("exo_transit_noise_vjp_f64", dev, *a.head(flags), *noise, *tail)
-    # the sums over all cadences: per-series sums once per (y, yerr) and stream where the weight separates (see _NZ_CACHE)
+    # the sums over all cadences: per-series sums once per (y, yerr) and stream where the weight separates
     separable = n_jit == 0 or var.numel() == 1
     terms = torch.empty(5, a.D, dtype=torch.float64, device=dev)
     tws, tbytes = None, 0
@@ -823,15 +874,14 @@ def _noise_launch(a, flags, ttv_edges, ttv_shift, data, var, mean, jit2):
         tbytes = int(_lib.load().exo_white_noise_workspace_bytes(a.N, a.D))
         tws = torch.empty(tbytes // 8, dtype=torch.float64, device=dev)
     stream = _stream(a.t)
-    capturing = torch.cuda.is_current_stream_capturing()
+    capturing = _NZ_DATA.capturing()
     keep = separable and data.var is var
     series = None
     if keep and capturing:
         # sums that an eager call (the warm-up) filled before the capture began -- torch.cuda.graph waits for the device on
-        # entry -- pinned for good: the graph holds their address
+        # entry; the graph holds their address, and the entry that holds them is pinned (_SeriesCache).  A capture without a
+        # warm-up gets a buffer from the graph's own pool and fills it on every replay.
         series = next(iter(data.series.values()), None)
-        if series is not None:
-            _NZ_PINNED[series.data_ptr()] = series
     elif keep:
         series = data.series.get(stream)
     ready = series is not None
@@ -895,21 +945,23 @@ def sampled_noise(mean, jitter):
 def _noise_inputs(y, yerr, mean, jitter, D):
     """(data, var, mean, jit2) of the sampled-mean / jitter likelihood for ``D`` draws: a per-draw ``yerr`` is a jitter on
     top of a zero variance"""
-    for name, x in (("y", y), ("yerr", yerr)):
-        if isinstance(x, torch.Tensor) and x.requires_grad and torch.is_grad_enabled() and (name == "y" or per_draw_yerr(x, y.numel()) is None):
-            raise NotImplementedError(
-                f"white-noise likelihood: `{name}` requires grad, and the fused kernels differentiate the orbit, the limb "
-                "darkening, `mean`, `jitter` and per-draw error bars only; use LimbDarkLightCurve.white_noise_log_likelihood "
-                "(it falls back to the dense light curve) or get_light_curve(total=True) with torch")
+    yd = per_draw_yerr(yerr, y.numel())
+    _refuse_data_grad(_WN, "the orbit, the limb darkening, `mean`, `jitter` and per-draw error bars", _WN_INSTEAD,
+                      y=y, yerr=yerr if yd is None else None)
     dev = y.device
-    mean = _per_draw(mean, "mean", D, dev)
+
+    def per_draw(x, name):      # (any shape that holds one value or one per draw, as this likelihood always took them)
+        if isinstance(x, torch.Tensor) and x.dim() > 1 and tuple(x.shape[1:]) != (1,):
+            x = x.reshape(-1)
+        return _per_draw(_dev_or_number(x, name), name, D, dev, _WN)
+
+    mean = per_draw(mean, "mean")
     jit2 = None
     if jitter is not None:
-        jit2 = _per_draw(jitter, "jitter", D, dev)
+        jit2 = per_draw(jitter, "jitter")
         jit2 = jit2 * jit2 if isinstance(jitter, torch.Tensor) else _const(float(jitter) ** 2, dev)
-    yd = per_draw_yerr(yerr, y.numel())
     if yd is not None:
-        yd = _per_draw(yd, "yerr", D, dev)
+        yd = per_draw(yd, "yerr")
         jit2 = yd * yd if jit2 is None else yd * yd + jit2
         data = _noise_data(y, 0.0)
     else:
@@ -1477,89 +1529,62 @@ def radial_velocity(t, params):
 # ------------------------------------------------------------------------------
 RV_MAX_TREND = 4      # include/exoplanet_amd.h EXO_RV_MAX_TREND
 RV_MAX_INST = 8       # EXO_RV_MAX_INST
-_RV_DATA = {}         # rv_loglike: (epochs, error bars, reference time, instruments) -> tau, variances, int32 instruments
 
 
-def _rv_data(t, rv_err, t_ref, instrument):
-    """the per-series arrays of exo_rv_loglike_vjp_f64 -- (tau = t - t_ref, var = rv_err^2 as (1,) or (n_cad,), int32
-    instruments | None, their largest index | None if unchecked) -- made once per series (the indices are checked on the
-    host, a device synchronisation; inside a capture nothing is kept and nothing checked: the kernel answers an index
-    outside its tables with NaN)"""
-    key = (t.data_ptr(), t._version, t.numel(), float(t_ref),
-           rv_err if not isinstance(rv_err, torch.Tensor) else (rv_err.data_ptr(), rv_err._version),
-           None if instrument is None else (instrument.data_ptr(), instrument._version), str(t.device))
-    hit = _RV_DATA.get(key)
-    if hit is not None:
-        return hit[:4]
-    capturing = torch.cuda.is_current_stream_capturing()
-    tau = t - float(t_ref)
-    if isinstance(rv_err, torch.Tensor):
-        err = _dev(rv_err.detach(), "rv_err").reshape(-1)
-        if err.numel() not in (1, t.numel()):
-            raise ValueError("rv_err must be a number or one value per epoch")
-        var = err * err
-    else:
-        var = _const(float(rv_err) ** 2, t.device)
-    inst, hi = None, None
-    if instrument is not None:
-        if not isinstance(instrument, torch.Tensor) or instrument.is_floating_point() or tuple(instrument.shape) != (t.numel(),):
-            raise ValueError("instrument must be an integer tensor with one entry per epoch")
-        inst = instrument.to(device=t.device, dtype=torch.int32).contiguous()
-        if not capturing and inst.numel():
-            lo, hi = int(inst.min()), int(inst.max())
-            if lo < 0 or hi >= RV_MAX_INST:
-                raise ValueError(f"instrument indices must lie in [0, {RV_MAX_INST}): got {lo} .. {hi}")
-    hit = (tau, var, inst, hi, (t, rv_err, instrument))      # (the sources stay alive: their addresses are the key)
-    if not capturing:
-        if len(_RV_DATA) >= 4:      # (an entry keeps its arrays alive: a few series at most)
-            _RV_DATA.clear()
-        _RV_DATA[key] = hit
-    return hit[:4]
-
-
-def _per_draw_inst(x, name, D, device):
-    """``x`` (a number, or a 0-d / (D,) / (D, 1) / (D, n_inst) tensor) as a 2-D tensor of 1 or D rows"""
-    if isinstance(x, (int, float)):
-        return _const(x, device).reshape(1, 1)
-    x = _dev(x, name)
-    x = x.reshape(-1, 1) if x.dim() < 2 else x
-    if x.dim() != 2 or x.shape[0] not in (1, D):
-        raise ValueError(f"radial-velocity likelihood: `{name}` has shape {tuple(x.shape)}, the parameters hold {D} draws -- a number, "
-                         "one value per draw, or (draws, instruments)")
-    return x
-
-
-class _RvLoglike(torch.autograd.Function):
-    """exo_rv_loglike_vjp_f64: the forward pass makes the one call and keeps the gradients, the reverse pass scales them by
-    the incoming cotangent.  ``trend`` (D, T) | None, ``offset`` / ``jit2`` (D, n_inst) | None."""
+class _DrawLoglike(torch.autograd.Function):
+    """A likelihood whose value (n_draw,) and every gradient come from ONE library call: the forward pass makes the call and
+    keeps the gradients that will be asked for, the reverse pass scales each by the incoming cotangent.  ``entry``: the
+    library entry; ``args(ll, grads)``: its arguments up to the stream, ``grads`` holding a tensor or None per pair of
+    ``wanted`` -- (index into ``inputs``, shape of that input's gradient), first dimension the draws; ``inputs``: the time
+    array, then what is differentiated (None: absent)."""
 
     @staticmethod
-    def forward(ctx, t, tau, inst, rv, var, params, trend, offset, jit2, n_inst):
-        D, P, _ = params.shape
-        dev = t.device
-        T = 0 if trend is None else trend.shape[1]
-        new = lambda *shape: torch.empty(*shape, dtype=torch.float64, device=dev)  # noqa: E731
-        ll = new(D)
-        gparams = new(D, P, RV_NPAR) if ctx.needs_input_grad[5] else None
-        gtrend = new(D, T) if trend is not None and ctx.needs_input_grad[6] else None
-        goffset = new(D, n_inst) if offset is not None and ctx.needs_input_grad[7] else None
-        gjit2 = new(D, n_inst) if jit2 is not None and ctx.needs_input_grad[8] else None
-        _call("exo_rv_loglike_vjp_f64", dev, _ptr(t), _ptr(tau), _ptr(inst), _ptr(rv), _ptr(var), t.numel(), var.numel(),
-              _ptr(params), D, P, _ptr(trend), T, _ptr(offset), _ptr(jit2), n_inst, _ptr(ll), _ptr(gparams), _ptr(gtrend),
-              _ptr(goffset), _ptr(gjit2), _stream(t))
-        ctx.have = [g is not None for g in (gparams, gtrend, goffset, gjit2)]
-        ctx.save_for_backward(*[g for g in (gparams, gtrend, goffset, gjit2) if g is not None])
+    def forward(ctx, entry, args, wanted, n_draw, *inputs):
+        t = inputs[0]
+        new = lambda *shape: torch.empty(*shape, dtype=torch.float64, device=t.device)  # noqa: E731
+        ll = new(n_draw)
+        grads = [new(*shape) if inputs[i] is not None and ctx.needs_input_grad[4 + i] else None for i, shape in wanted]
+        _call(entry, t.device, *args(ll, grads), _stream(t))
+        ctx.slots = [4 + i for (i, _), g in zip(wanted, grads) if g is not None]
+        ctx.n_in = 4 + len(inputs)
+        ctx.save_for_backward(*[g for g in grads if g is not None])
         return ll
 
     @staticmethod
     def backward(ctx, gll):
         gll = gll.contiguous()
-        saved = iter(ctx.saved_tensors)
-        gparams, gtrend, goffset, gjit2 = (next(saved) if have else None for have in ctx.have)
-        col = gll[:, None]
-        return (None, None, None, None, None, None if gparams is None else gll[:, None, None] * gparams,
-                None if gtrend is None else col * gtrend, None if goffset is None else col * goffset,
-                None if gjit2 is None else col * gjit2, None)
+        out = [None] * ctx.n_in
+        for slot, g in zip(ctx.slots, ctx.saved_tensors):
+            out[slot] = gll.reshape((-1,) + (1,) * (g.dim() - 1)) * g
+        return tuple(out)
+
+
+def _rv_data(t, rv_err, t_ref, instrument):
+    """the per-series arrays of exo_rv_loglike_vjp_f64 -- (tau = t - t_ref, var = rv_err^2 as (1,) or (n_cad,), int32
+    instruments | None, their largest index | None if unchecked) -- made once per series (the indices are checked on the
+    host, a device synchronisation; inside a capture nothing is checked: the kernel answers an index outside its tables
+    with NaN)"""
+    def make():
+        tau = t - float(t_ref)
+        if isinstance(rv_err, torch.Tensor):
+            err = _dev(rv_err.detach(), "rv_err").reshape(-1)
+            if err.numel() not in (1, t.numel()):
+                raise ValueError("rv_err must be a number or one value per epoch")
+            var = err * err
+        else:
+            var = _const(float(rv_err) ** 2, t.device)
+        inst, hi = None, None
+        if instrument is not None:
+            if instrument.is_floating_point() or tuple(instrument.shape) != (t.numel(),):
+                raise ValueError("instrument must be an integer tensor with one entry per epoch")
+            inst = instrument.to(device=t.device, dtype=torch.int32).contiguous()
+            if not _RV_SERIES.capturing() and inst.numel():
+                lo, hi = int(inst.min()), int(inst.max())
+                if lo < 0 or hi >= RV_MAX_INST:
+                    raise ValueError(f"instrument indices must lie in [0, {RV_MAX_INST}): got {lo} .. {hi}")
+        return tau, var, inst, hi
+
+    return _RV_SERIES.get((t, rv_err, t_ref, instrument), make).value
 
 
 def rv_loglike(t, params, rv, rv_err, trend=None, t_ref=0.0, offset=None, jitter=None, instrument=None):
@@ -1585,20 +1610,17 @@ def rv_loglike(t, params, rv, rv_err, trend=None, t_ref=0.0, offset=None, jitter
     D, P, _ = params.shape
     if not 1 <= P <= MAX_PLANETS:
         raise ValueError(f"between 1 and {MAX_PLANETS} planets")
-    for name, x in (("rv", rv), ("rv_err", rv_err)):
-        if isinstance(x, torch.Tensor) and x.requires_grad and torch.is_grad_enabled():
-            raise NotImplementedError(
-                f"radial-velocity likelihood: `{name}` requires grad, and the fused kernel differentiates the orbit, the trend, "
-                "the zero points and the jitter only; use KeplerianOrbit.rv_log_likelihood (it falls back to "
-                "get_radial_velocity and torch)")
+    what = "radial-velocity likelihood"
+    _refuse_data_grad(what, "the orbit, the trend, the zero points and the jitter",
+                      "KeplerianOrbit.rv_log_likelihood (it falls back to get_radial_velocity and torch)", rv=rv, rv_err=rv_err)
     tau, var, inst, hi = _rv_data(t, rv_err, t_ref, instrument)
     if trend is not None:
         trend = _dev(trend, "trend")
         if trend.dim() != 2 or trend.shape[0] not in (1, D) or trend.shape[1] > RV_MAX_TREND:
             raise ValueError(f"trend must be (n_draw, T) with T <= {RV_MAX_TREND}; got {tuple(trend.shape)} for {D} draws")
         trend = trend.expand(D, -1).contiguous() if trend.shape[1] else None
-    offset = None if offset is None else _per_draw_inst(offset, "offset", D, t.device)
-    jitter = None if jitter is None else _per_draw_inst(jitter, "jitter", D, t.device)
+    offset = None if offset is None else _per_draw(_dev_or_number(offset, "offset"), "offset", D, t.device, what, columns=True)
+    jitter = None if jitter is None else _per_draw(_dev_or_number(jitter, "jitter"), "jitter", D, t.device, what, columns=True)
     # one column everywhere: the instruments share every parameter, and which epoch is whose does not matter
     widths = {x.shape[1] for x in (offset, jitter) if x is not None and x.shape[1] > 1}
     n_inst = max(widths) if widths else 1
@@ -1609,31 +1631,22 @@ def rv_loglike(t, params, rv, rv_err, trend=None, t_ref=0.0, offset=None, jitter
         inst = None
     offset = None if offset is None else offset.expand(D, n_inst).contiguous()
     jit2 = None if jitter is None else (jitter * jitter).expand(D, n_inst).contiguous()
-    return _RvLoglike.apply(t, tau, inst, rv.detach(), var, params, trend, offset, jit2, n_inst)
+    rv, T = rv.detach(), 0 if trend is None else trend.shape[1]
+
+    def args(ll, grads):
+        return (_ptr(t), _ptr(tau), _ptr(inst), _ptr(rv), _ptr(var), t.numel(), var.numel(), _ptr(params), D, P, _ptr(trend), T,
+                _ptr(offset), _ptr(jit2), n_inst, _ptr(ll), *map(_ptr, grads))
+
+    wanted = [(1, (D, P, RV_NPAR)), (2, (D, T)), (3, (D, n_inst)), (4, (D, n_inst))]
+    return _DrawLoglike.apply("exo_rv_loglike_vjp_f64", args, wanted, D, t, params, trend, offset, jit2)
 
 
 # ------------------------------------------------------------------------------
 # astrometric likelihood (separation and position angle): value and every gradient from one launch
 # ------------------------------------------------------------------------------
-_AST_DATA = {}        # astrometry_loglike: (position angles, error bars) -> cos theta, sin theta, the two variances
-_AST_CAPTURED = {}    # the entries of _AST_DATA that a capture was served from: a graph replays their addresses
-
-
 def _astrometry_data(theta, rho_err, theta_err):
     """the per-series arrays of exo_astrometry_loglike_vjp_f64 -- (cos theta, sin theta, var_rho, var_theta), the variances
-    as (1,) or (n_cad,) -- made once per series.  Inside a capture nothing new is kept (what is made there belongs to the
-    graph's pool).  An entry that a capture is served from -- GraphedStep warms up eagerly, so the series is here before the
-    capture -- is in the graph by its addresses and held by nothing else, so it moves to _AST_CAPTURED, which is never
-    emptied: a replay after any number of other series reads the arrays it captured (a few kB per captured series, for the
-    life of the process)."""
-    err_key = lambda e: e if not isinstance(e, torch.Tensor) else (e.data_ptr(), e._version, e.numel())  # noqa: E731
-    key = (theta.data_ptr(), theta._version, theta.numel(), err_key(rho_err), err_key(theta_err), str(theta.device))
-    hit = _AST_CAPTURED.get(key) or _AST_DATA.get(key)
-    if hit is not None:
-        if key not in _AST_CAPTURED and torch.cuda.is_current_stream_capturing():
-            _AST_CAPTURED[key] = hit
-        return hit[:4]
-
+    as (1,) or (n_cad,) -- made once per series"""
     def variance(err, name):
         if isinstance(err, torch.Tensor):
             err = _dev(err.detach(), name).reshape(-1)
@@ -1642,57 +1655,10 @@ def _astrometry_data(theta, rho_err, theta_err):
             return err * err
         return _const(float(err) ** 2, theta.device)
 
-    hit = (torch.cos(theta), torch.sin(theta), variance(rho_err, "rho_err"), variance(theta_err, "theta_err"),
-           (theta, rho_err, theta_err))      # (the sources stay alive: their addresses are the key)
-    if not torch.cuda.is_current_stream_capturing():
-        if len(_AST_DATA) >= 4:      # (an entry keeps its arrays alive: a few series at most)
-            _AST_DATA.clear()
-        _AST_DATA[key] = hit
-    return hit[:4]
+    def make():
+        return torch.cos(theta), torch.sin(theta), variance(rho_err, "rho_err"), variance(theta_err, "theta_err")
 
-
-def _ast_per_draw(x, name, D, device):
-    """``x`` (a number, or a 0-d / (1,) / (D,) / (D, 1) tensor) as a 1-D tensor of 1 or D entries"""
-    if isinstance(x, (int, float)):
-        return _const(x, device)
-    x = _dev(x, name)
-    if x.dim() > 2 or (x.dim() == 2 and x.shape[1] != 1):
-        raise ValueError(f"astrometric likelihood: `{name}` has shape {tuple(x.shape)} -- a number or one value per draw, "
-                         "(draws,) or (draws, 1)")
-    x = x.reshape(-1)
-    if x.numel() not in (1, D):
-        raise ValueError(f"astrometric likelihood: `{name}` holds {x.numel()} values, the parameters {D} draws -- a number or "
-                         "one value per draw")
-    return x
-
-
-class _AstrometryLoglike(torch.autograd.Function):
-    """exo_astrometry_loglike_vjp_f64: the forward pass makes the one call and keeps the gradients, the reverse pass scales
-    them by the incoming cotangent.  ``params`` (D, 10), ``jit2_rho`` / ``jit2_theta`` (D,) | None."""
-
-    @staticmethod
-    def forward(ctx, t, rho, cos_theta, sin_theta, var_rho, var_theta, params, jit2_rho, jit2_theta):
-        D = params.shape[0]
-        dev = t.device
-        new = lambda *shape: torch.empty(*shape, dtype=torch.float64, device=dev)  # noqa: E731
-        ll = new(D)
-        gparams = new(D, OV_NPAR) if ctx.needs_input_grad[6] else None
-        gjr = new(D) if jit2_rho is not None and ctx.needs_input_grad[7] else None
-        gjt = new(D) if jit2_theta is not None and ctx.needs_input_grad[8] else None
-        _call("exo_astrometry_loglike_vjp_f64", dev, _ptr(t), _ptr(rho), _ptr(cos_theta), _ptr(sin_theta), _ptr(var_rho),
-              var_rho.numel(), _ptr(var_theta), var_theta.numel(), t.numel(), _ptr(params), D, _ptr(jit2_rho), _ptr(jit2_theta),
-              _ptr(ll), _ptr(gparams), _ptr(gjr), _ptr(gjt), _stream(t))
-        ctx.have = [g is not None for g in (gparams, gjr, gjt)]
-        ctx.save_for_backward(*[g for g in (gparams, gjr, gjt) if g is not None])
-        return ll
-
-    @staticmethod
-    def backward(ctx, gll):
-        gll = gll.contiguous()
-        saved = iter(ctx.saved_tensors)
-        gparams, gjr, gjt = (next(saved) if have else None for have in ctx.have)
-        return (None, None, None, None, None, None, None if gparams is None else gll[:, None] * gparams,
-                None if gjr is None else gll * gjr, None if gjt is None else gll * gjt)
+    return _AST_SERIES.get((theta, rho_err, theta_err), make).value
 
 
 def astrometry_loglike(t, params, rho, rho_err, theta, theta_err, rho_jitter=None, theta_jitter=None):
@@ -1716,17 +1682,23 @@ def astrometry_loglike(t, params, rho, rho_err, theta, theta_err, rho_jitter=Non
     if params.dim() != 2 or params.shape[-1] != OV_NPAR:
         raise ValueError(f"params must be (n_draw, {OV_NPAR}): one companion per call")
     D = params.shape[0]
-    for name, x in (("rho", rho), ("theta", theta), ("rho_err", rho_err), ("theta_err", theta_err)):
-        if isinstance(x, torch.Tensor) and x.requires_grad and torch.is_grad_enabled():
-            raise NotImplementedError(
-                f"astrometric likelihood: `{name}` requires grad, and the fused kernel differentiates the orbit and the jitters "
-                "only; use KeplerianOrbit.astrometry_log_likelihood (it falls back to get_relative_angles and torch)")
+    what = "astrometric likelihood"
+    _refuse_data_grad(what, "the orbit and the jitters",
+                      "KeplerianOrbit.astrometry_log_likelihood (it falls back to get_relative_angles and torch)",
+                      rho=rho, theta=theta, rho_err=rho_err, theta_err=theta_err)
     cos_theta, sin_theta, var_rho, var_theta = _astrometry_data(theta.detach(), rho_err, theta_err)
     jit2 = []
     for name, x in (("rho_jitter", rho_jitter), ("theta_jitter", theta_jitter)):
-        x = None if x is None else _ast_per_draw(x, name, D, t.device)
+        x = None if x is None else _per_draw(_dev_or_number(x, name), name, D, t.device, what)
         jit2.append(None if x is None else (x * x).expand(D).contiguous())
-    return _AstrometryLoglike.apply(t, rho.detach(), cos_theta, sin_theta, var_rho, var_theta, params, jit2[0], jit2[1])
+    rho = rho.detach()
+
+    def args(ll, grads):
+        return (_ptr(t), _ptr(rho), _ptr(cos_theta), _ptr(sin_theta), _ptr(var_rho), var_rho.numel(), _ptr(var_theta),
+                var_theta.numel(), t.numel(), _ptr(params), D, _ptr(jit2[0]), _ptr(jit2[1]), _ptr(ll), *map(_ptr, grads))
+
+    wanted = [(1, (D, OV_NPAR)), (2, (D,)), (3, (D,))]
+    return _DrawLoglike.apply("exo_astrometry_loglike_vjp_f64", args, wanted, D, t, params, jit2[0], jit2[1])
 
 
 # ------------------------------------------------------------------------------

@@ -142,6 +142,24 @@ def _per_draw_count(name, x):
     return int(x.shape[0])
 
 
+def _repeat_for_draws(what, params, counts):
+    """``params`` (draws first) against the draw counts of the nuisance parameters, {name: count}: the record of ONE system is
+    repeated for the draws of its nuisance parameters; otherwise every count must be 1 or the parameters' -- ValueError"""
+    D = params.shape[0]
+    if D == 1 and max(counts.values(), default=1) > 1:
+        D = max(counts.values())
+        params = params.expand(D, *params.shape[1:])
+    for name, n in counts.items():
+        if n not in (1, D):
+            raise ValueError(f"{what}: `{name}` holds {n} draws, the parameters {D}")
+    return params.contiguous()
+
+
+def _to_batch(ll, batch):
+    """the per-draw values in the orbit's batch shape -- unless ONE system was repeated for more draws than that"""
+    return ll.reshape(batch) if ll.numel() == math.prod(batch) else ll
+
+
 class KeplerianOrbit:
     """A system of bodies on Keplerian orbits around a common central body.
 
@@ -583,24 +601,12 @@ class KeplerianOrbit:
             t_ref = _middle(t)
         if isinstance(trend, torch.Tensor) and trend.dim() == 1:
             trend = trend.reshape(1, -1)
-        # draws of the zero points, jitters and trend of ONE system: the records are repeated
-        extra = [x.shape[0] for x in (zero_point, jitter, trend) if isinstance(x, torch.Tensor) and x.dim() >= 1]
-        D = params.shape[0]
-        if D == 1 and max(extra + [1]) > 1:
-            D = max(extra)
-            params = params.expand(D, -1, -1).contiguous()
-        for name, x in (("zero_point", zero_point), ("jitter", jitter), ("trend", trend)):
-            if isinstance(x, torch.Tensor) and x.dim() >= 1 and x.shape[0] not in (1, D):
-                raise ValueError(f"rv_log_likelihood: `{name}` holds {x.shape[0]} draws, the parameters {D}")
-        needs = lambda x: isinstance(x, torch.Tensor) and x.requires_grad and torch.is_grad_enabled()  # noqa: E731
-        route = _rv_loglike_composed if needs(rv) or needs(rv_err) else ops.rv_loglike
+        nuisance = (("zero_point", zero_point), ("jitter", jitter), ("trend", trend))
+        params = _repeat_for_draws("rv_log_likelihood", params,
+                                   {name: x.shape[0] for name, x in nuisance if isinstance(x, torch.Tensor) and x.dim() >= 1})
+        route = _rv_loglike_composed if ops.needs_grad(rv) or ops.needs_grad(rv_err) else ops.rv_loglike
         ll = route(t, params, rv, rv_err, trend=trend, t_ref=t_ref, offset=zero_point, jitter=jitter, instrument=instrument)
-        n = 1
-        for b in batch:
-            n *= int(b)
-        if ll.numel() == n:
-            return ll.reshape(batch)
-        return ll
+        return _to_batch(ll, batch)
 
     def astrometry_log_likelihood(self, t, rho, rho_err, theta, theta_err, parallax=None, rho_jitter=None, theta_jitter=None,
                                   planet=None):
@@ -648,27 +654,13 @@ class KeplerianOrbit:
             raise ValueError(f"astrometry_log_likelihood: planet = {planet} of {P} companions")
         params = params[:, int(planet), :]
         rho, theta = as_tensor(rho, t).to(t.device), as_tensor(theta, t).to(t.device)
-        # draws of the jitters of ONE system: the record is repeated
         jitters = (("rho_jitter", rho_jitter), ("theta_jitter", theta_jitter))
-        counts = {name: _per_draw_count(name, x) for name, x in jitters if isinstance(x, torch.Tensor) and x.dim() >= 1}
-        extra = list(counts.values())
-        D = params.shape[0]
-        if D == 1 and max(extra + [1]) > 1:
-            D = max(extra)
-            params = params.expand(D, -1)
-        for name, n_jit in counts.items():
-            if n_jit not in (1, D):
-                raise ValueError(f"astrometry_log_likelihood: `{name}` holds {n_jit} draws, the parameters {D}")
-        needs = lambda x: isinstance(x, torch.Tensor) and x.requires_grad and torch.is_grad_enabled()  # noqa: E731
-        composed = needs(rho) or needs(theta) or needs(rho_err) or needs(theta_err)
+        params = _repeat_for_draws("astrometry_log_likelihood", params,
+                                   {name: _per_draw_count(name, x) for name, x in jitters if isinstance(x, torch.Tensor) and x.dim() >= 1})
+        composed = any(ops.needs_grad(x) for x in (rho, theta, rho_err, theta_err))
         route = _astrometry_loglike_composed if composed else ops.astrometry_loglike
-        ll = route(t, params.contiguous(), rho, rho_err, theta, theta_err, rho_jitter=rho_jitter, theta_jitter=theta_jitter)
-        n = 1
-        for b in batch:
-            n *= int(b)
-        if ll.numel() == n:
-            return ll.reshape(batch)
-        return ll
+        ll = route(t, params, rho, rho_err, theta, theta_err, rho_jitter=rho_jitter, theta_jitter=theta_jitter)
+        return _to_batch(ll, batch)
 
     def _get_acceleration(self, a, m, t):
         fused = self._fused_vector((self.K0 * m) ** 2 / a, t, velocity=False, acceleration=True)

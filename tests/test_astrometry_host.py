@@ -25,8 +25,8 @@ def harness():
     os.makedirs(out, exist_ok=True)
     so = os.path.join(out, "astrometry_harness.so")
     csrc = os.path.join(ROOT, "exoplanet_amd", "csrc")
-    srcs = [os.path.join(ROOT, "tests", "astrometry_harness.cpp")] + [os.path.join(csrc, h) for h in
-                                                                      ("exo_astrometry_core.hpp", "exo_rv_core.hpp", "exo_math.hpp")]
+    srcs = [os.path.join(ROOT, "tests", "astrometry_harness.cpp")] + [
+        os.path.join(csrc, h) for h in ("exo_astrometry_core.hpp", "exo_draw_block.hpp", "exo_rv_core.hpp", "exo_math.hpp")]
     if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
         subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-shared", "-fPIC", "-o", so, srcs[0]], check=True)
     lib = ctypes.CDLL(so)

@@ -292,13 +292,13 @@ def test_a_captured_series_outlives_the_cache(dev):
     value_and_grad, draw, _ = _tutorial_inputs(dev, D=4, N=45, seed=61)
     z = draw()
     step = xo.GraphedStep(value_and_grad, z)
-    held = {k: [x.data_ptr() for x in v[:4]] for k, v in ops._AST_CAPTURED.items()}
+    held = {k: [x.data_ptr() for x in e.value] for k, e in ops._AST_SERIES.pinned.items()}
     assert held
     for seed in range(6):                                  # six other series: the cache keeps four
         other, other_draw, _ = _tutorial_inputs(dev, D=4, N=45, seed=70 + seed)
         other(other_draw())
     for k, ptrs in held.items():
-        assert [x.data_ptr() for x in ops._AST_CAPTURED[k][:4]] == ptrs
+        assert [x.data_ptr() for x in ops._AST_SERIES.pinned[k].value] == ptrs
     ll_e, g_e = value_and_grad(z)
     ll_g, g_g = step(z)
     assert float((ll_g - ll_e).abs().max()) <= 1e-12 * float(ll_e.abs().max())

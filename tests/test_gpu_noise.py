@@ -387,6 +387,55 @@ def test_parameter_space_with_mean_and_log_jitter_in_a_graph(dev):
     assert float((g_d - g_e).abs().max()) <= 1e-8 * float(g_d.abs().max())
 
 
+def test_a_captured_series_outlives_the_cache(dev):
+    """a graph holds the per-series arrays (the variances, the per-series sums) by address: after more other series than the
+    cache keeps -- all of them still alive, and the freed blocks of their size overwritten with NaN -- the arrays are still
+    the ones the graph was captured with, and a replay still equals eager (per-cadence yerr, sampled mean and jitter)"""
+    import exoplanet_amd as xo
+    from exoplanet_amd import ops
+
+    s = system("one_planet", dev)
+    fixed = {k: v.detach() for k, v in s.leaves.items()}
+    u1, u2 = s.u1.detach(), s.u2.detach()
+
+    def model(y, yerr):
+        def value_and_grad(z):
+            with torch.enable_grad():
+                zz = z.detach().requires_grad_(True)
+                orbit = xo.KeplerianOrbit(period=zz[:, 0:1], t0=zz[:, 1:2], b=fixed["b"], ecc=fixed["ecc"], omega=fixed["omega"])
+                ll = xo.LimbDarkLightCurve(u1, u2).white_noise_log_likelihood(
+                    orbit=orbit, r=fixed["r"], t=s.t, y=y, yerr=yerr, mean=zz[:, 2:3], jitter=torch.exp(zz[:, 3:4]))
+                (g,) = torch.autograd.grad(ll, zz, grad_outputs=torch.ones_like(ll))
+            return ll.detach(), g
+        return value_and_grad
+
+    rng = np.random.default_rng(12)
+    z = torch.as_tensor(np.array([3.5, 1.0, 1.0, math.log(2e-4)]) * (1 + 1e-4 * rng.normal(size=(D, 4))), device=dev)
+    value_and_grad = model(s.y.clone(), s.yerr_cad.clone())      # (copies: no earlier capture has pinned this series)
+    ll_0, g_0 = value_and_grad(z)
+    before = set(ops._NZ_DATA.pinned)
+    step = xo.GraphedStep(value_and_grad, z)
+    held = {k: (e.value.var.data_ptr(), [x.data_ptr() for x in e.value.series.values()]) for k, e in ops._NZ_DATA.pinned.items()
+            if k not in before}
+    assert len(held) == 1      # this capture's series, pinned by it
+    others = [(s.y + 1e-6 * (k + 1), s.yerr_cad * (1.0 + 0.01 * (k + 1))) for k in range(6)]      # the cache keeps four
+    for y, yerr in others:
+        model(y, yerr)(z)
+    nan = [torch.full((n,), math.nan, dtype=torch.float64, device=dev) for n in (N, ops._NOISE_SERIES) for _ in range(6)]
+    for k, (var, series) in held.items():
+        e = ops._NZ_DATA.pinned[k].value
+        assert e.var.data_ptr() == var and [x.data_ptr() for x in e.series.values()][:len(series)] == series
+    ll_e, g_e = value_and_grad(z)
+    ll_g, g_g = step(z)
+    torch.cuda.synchronize()
+    assert bool(torch.isfinite(ll_e).all()) and bool(torch.isfinite(g_e).all()) and float(g_e[:, -2:].abs().min()) > 0
+    assert float((ll_e - ll_0).abs().max()) <= 1e-12 * float(ll_0.abs().max())      # (eager, before the other series and after)
+    assert float((g_e - g_0).abs().max()) <= 1e-12 * float(g_0.abs().max())
+    assert float((ll_g - ll_e).abs().max()) <= 1e-12 * float(ll_e.abs().max())
+    assert float((g_g - g_e).abs().max()) <= 1e-12 * float(g_e.abs().max())
+    assert len(others) == 6 and all(bool(torch.isnan(x).all()) for x in nan)
+
+
 def test_mismatched_draws_and_data_that_requires_grad(dev):
     from exoplanet_amd import ops
     from oracle import numpy_port as P

@@ -199,12 +199,11 @@ def test_bad_eccentricity_is_nan_in_that_draw_only(dev, g):
     assert np.isnan(got["loglike"][1]) and np.isnan(got["gparams"][1, 0]).all()
 
 
-def test_graph_replay_matches_eager(dev):
-    """one capture of value and gradient (a single chain of launches), replayed twice with changed leaves"""
+def _two_instrument_model(dev, D, N, seed):
+    """(value_and_grad, draw) of a two-instrument model with per-epoch error bars over (draws, 10) leaves"""
     import exoplanet_amd as xo
 
-    D, N = 8, 150
-    rng = np.random.default_rng(29)
+    rng = np.random.default_rng(seed)
     t = T(np.sort(rng.uniform(0.0, 80.0, N)), dev)
     rv, rv_err = T(3.0 * rng.normal(size=N), dev), T(rng.uniform(0.3, 0.7, N), dev)
     inst = torch.as_tensor(rng.integers(0, 2, N), device=dev)
@@ -221,6 +220,14 @@ def test_graph_replay_matches_eager(dev):
     def draw():
         return T(np.array([11.0, 2.0, 0.3, 0.8, 4.0, 0.2, -0.3, 0.1, 1e-3, math.log(0.4)]) * (1 + 0.02 * rng.normal(size=(D, 10))), dev)
 
+    return value_and_grad, draw
+
+
+def test_graph_replay_matches_eager(dev):
+    """one capture of value and gradient (a single chain of launches), replayed twice with changed leaves"""
+    import exoplanet_amd as xo
+
+    value_and_grad, draw = _two_instrument_model(dev, D=8, N=150, seed=29)
     z0 = draw()
     step = xo.GraphedStep(value_and_grad, z0)
     for _ in range(2):
@@ -230,6 +237,38 @@ def test_graph_replay_matches_eager(dev):
         assert bool(torch.isfinite(ll_e).all()) and bool(torch.isfinite(g_e).all())
         assert float((ll_g - ll_e).abs().max()) <= 1e-12 * float(ll_e.abs().max())
         assert float((g_g - g_e).abs().max()) <= 1e-12 * float(g_e.abs().max())
+
+
+def test_a_captured_series_outlives_the_cache(dev):
+    """a graph holds the per-series arrays (tau, the variances, the int32 instruments) by address: after more other series
+    than the cache keeps -- all of them still alive, and the freed blocks of their size overwritten with NaN -- the arrays are
+    still the ones the graph was captured with, and a replay still equals eager"""
+    import exoplanet_amd as xo
+    from exoplanet_amd import ops
+
+    D, N = 4, 20
+    value_and_grad, draw = _two_instrument_model(dev, D, N, seed=31)
+    z = draw()
+    ll_0, g_0 = value_and_grad(z)
+    before = set(ops._RV_SERIES.pinned)
+    step = xo.GraphedStep(value_and_grad, z)
+    held = {k: [x.data_ptr() for x in e.value[:3]] for k, e in ops._RV_SERIES.pinned.items() if k not in before}
+    assert len(held) == 1      # this capture's series, pinned by it
+    others = [_two_instrument_model(dev, D, N, seed=40 + seed) for seed in range(6)]      # the cache keeps four
+    for other, other_draw in others:
+        other(other_draw())
+    nan = [torch.full((n,), math.nan, dtype=torch.float64, device=dev) for n in (N, N, N // 2, N // 2) for _ in range(4)]
+    for k, ptrs in held.items():
+        assert [x.data_ptr() for x in ops._RV_SERIES.pinned[k].value[:3]] == ptrs
+    ll_e, g_e = value_and_grad(z)
+    ll_g, g_g = step(z)
+    torch.cuda.synchronize()
+    assert bool(torch.isfinite(ll_e).all()) and bool(torch.isfinite(g_e).all())
+    assert float((ll_e - ll_0).abs().max()) <= 1e-12 * float(ll_0.abs().max())      # (eager, before the other series and after)
+    assert float((g_e - g_0).abs().max()) <= 1e-12 * float(g_0.abs().max())
+    assert float((ll_g - ll_e).abs().max()) <= 1e-12 * float(ll_e.abs().max())
+    assert float((g_g - g_e).abs().max()) <= 1e-12 * float(g_e.abs().max())
+    assert len(others) == 6 and all(bool(torch.isnan(x).all()) for x in nan)
 
 
 def test_joint_light_curve_and_rv_model_under_nuts(dev):
