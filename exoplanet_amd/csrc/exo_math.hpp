@@ -258,7 +258,7 @@ EXO_HD void sincos_any(double x, double* s, double* c) {
 // (t - tp) n reduced to [-pi, pi] (up to a rounding): t - tp as an exact sum of two doubles (Knuth), its product with n as
 // an exact sum of two (fma), the multiple of 2 pi taken off the leading part exactly, then the tails added.  With BJD-sized
 // t and tp = O(1) the two roundings of the plain product are 2.3e-16 |M| ~ 3e-9 rad at |M| = 3e7; this is good to
-// ~2e-16 (1 + |M| 1e-16).  Used by the radial-velocity, orbit-vector and light-curve kernels (exo_rv_core.hpp, exo_transit.hip).
+// ~2e-16 (1 + |M| 1e-16).  Used by the radial-velocity, orbit-vector and light-curve kernels (exo_rv_core.hpp, exo_transit_sample.hpp).
 EXO_HD double mean_anomaly_reduced(double t, double tp, double n) {
   const double dh = t - tp;
   const double tb = dh - t;

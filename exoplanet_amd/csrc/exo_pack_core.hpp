@@ -1,6 +1,6 @@
 // exo_pack_core.hpp -- the record-packing algebra (KeplerianOrbit.__init__ + get_cl + windows) as device functions, shared by
 // the packing kernels (exo_pack.hip) and the light-curve sweep, which packs the records ITSELF when it is handed the
-// constructor's columns (exo_transit.hip: transit_enum_kernel<.., PACK>, and the packing VJP folded into the sweep's last
+// constructor's columns (exo_transit_runs.hpp: transit_enum_kernel<.., PACK>, and the packing VJP folded into the sweep's last
 // kernel).  Reference lines: exo_pack.hip's header comment.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -1519,8 +1519,8 @@ def celerite_predict_var(t, diag, coeffs, coeffs2, tq):
 
 
 # ---------------------------------------------------------------------------------------------
-# Not a reference function: the conjunction-window bound of the HIP path (exoplanet_amd/csrc/exo_transit.hip,
-# transit_window_kernel), restated so that its defining property -- the window holds every true anomaly at which
+# Not a reference function: the conjunction-window bound of the HIP path (exoplanet_amd/csrc/exo_transit_window.hpp,
+# window_lanes / transit_window_kernel), restated so that its defining property -- the window holds every true anomaly at which
 # the disks can overlap -- can be checked on the CPU against brute force (tests/test_window_bound.py).  The
 # reference has no counterpart: its in_transit (keplerian.py:708-777) solves for the contacts themselves.
 # ---------------------------------------------------------------------------------------------

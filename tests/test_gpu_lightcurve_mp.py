@@ -1,4 +1,4 @@
-"""GPU: the light-curve kernels of exo_transit.hip, forward and reverse, against the multiprecision fixture
+"""GPU: the light-curve kernels of exo_transit.hip (its headers exo_transit_*.hpp: both paths and eval_sample), forward and reverse, against the multiprecision fixture
 tests/golden/lightcurve_mp.npz (tools/make_lightcurve_golden.py) -- every route to the fixture, none merely to another
 route: autograd on the two-sweep and on the Jacobian route, the one-sweep value + VJP (rows, cadence-major cotangent, exact
 scan), transit_flux_dot, transit_chi2, the fused white-noise likelihood with a per-draw mean and jitter, the sparse sweep and

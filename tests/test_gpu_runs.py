@@ -132,6 +132,61 @@ def test_short_and_odd_series(dev):
             assert float((x - y).abs().max()) <= 1e-11 * float(x.abs().max()) + 1e-300
 
 
+_UNEVEN = {}
+
+
+def uneven_case(dev, timed):
+    """a sorted but unevenly sampled series -- sorted uniforms over four periods, more than a period cut out, a handful of
+    repeated time stamps -- and what the list path (no searches at all) makes of it; computed once per table choice"""
+    from exoplanet_amd import ops
+
+    if timed not in _UNEVEN:
+        rng = np.random.default_rng(53)
+        D, period, t0 = 3, 3.5, 1.0
+        t = np.sort(rng.uniform(0.25, 0.25 + 4 * period, 8300))
+        t = t[(t < 5.2) | (t > 9.0)]                       # the transit at 8.0 goes with the gap
+        for i in (7, 1500, 4000, int(np.searchsorted(t, 4.5)), int(np.searchsorted(t, 11.5)), t.size - 2):
+            t[i + 1] = t[i]
+        assert 5500 < t.size < 6500 and bool((np.diff(t) >= 0).all()) and int((np.diff(t) == 0).sum()) >= 6
+        rec, c = system(rng, D)
+        g = rng.normal(size=(D, t.size))
+        kw = {}
+        if timed:
+            # bins around the transits at t0 + k period, each a few minutes early or late
+            edges = t0 + period * (np.arange(4) + 0.5)
+            shift = period * np.arange(5) + 0.01 * rng.normal(size=5)
+            kw = dict(ttv=(T(np.tile(edges, (D, 1, 1)), dev), T(np.tile(shift, (D, 1, 1)), dev)))
+        args = (T(rec, dev), T(c, dev), T(g, dev))
+        ref = ops.transit_flux_value_and_vjp(T(t, dev), *args, flags=ops.FLAG_EXACT_SCAN, **kw)
+        assert float(ref[0].min()) < -1e-3
+        _UNEVEN[timed] = (t, args, kw, ref)
+    return _UNEVEN[timed]
+
+
+@pytest.mark.parametrize("timed", [False, True])
+@pytest.mark.parametrize("vouched", [True, False])
+def test_uneven_sampling_takes_the_search(dev, vouched, timed, monkeypatch):
+    """the position guessed from the mean sampling rate is wrong nearly everywhere: every run's ends come from the
+    bisection -- in the fused launch (vouched), behind the device's own check (unvouched), and bin by bin with timing
+    tables -- and must be the cadences the list path solves"""
+    from exoplanet_amd import ops
+
+    t_np, args, kw, ref = uneven_case(dev, timed)
+    t = T(t_np, dev)
+    monkeypatch.setenv("EXO_CHECK_SORTED_ON_DEVICE", "0" if vouched else "1")
+    if vouched:
+        ops.vouch_sorted(t)
+    try:
+        assert ops._sorted_flag(t) == (ops.FLAG_SORTED_TIMES if vouched else 0)
+        got = ops.transit_flux_value_and_vjp(t, *args, **kw)
+    finally:
+        ops.release_sorted(t)
+    assert same_flux(got[0], ref[0])
+    assert len(got) == len(ref) == (4 if timed else 3)
+    for x, y in zip(got[1:], ref[1:]):
+        assert float((x - y).abs().max()) <= 1e-11 * float(y.abs().max())
+
+
 @pytest.mark.parametrize("planets", [1, 2])
 def test_folded_finish_equals_the_separate_last_kernel(dev, planets):
     """batches of >= 512 draws: a draw is one block's work and that block finishes it (gradients from its partials,
