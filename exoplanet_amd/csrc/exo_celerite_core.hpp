@@ -5,7 +5,7 @@
 // checkpoint in registers).  Nothing here exchanges data between lanes, so the same code compiles
 // for the host (g++, EXO_HOST_BUILD: tests/gp_host_harness.cpp runs the whole time-parallel
 // pipeline on the CPU against the oracle) and for gfx950, where a lane is a (draw, chunk) and the
-// kernels of exo_celerite.hip are thin wrappers.  Algorithm: exo_celerite.hip header comment and
+// kernels of exo_celerite_lane.hpp are thin wrappers.  Algorithm: exo_celerite.hip header comment and
 // docs/DESIGN_r1_r4.md 3.4 / 3.5 (celerite2 is a dependency of the reference, /root/reference/setup.py:36;
 // the recurrences are the published ones).
 #pragma once
@@ -49,6 +49,9 @@ constexpr int kCkptB = 4;   // cadences per block of the one-lane chunk kernels 
 #define EXO_SPAN2_MIN_J 3
 #endif
 EXO_HDH constexpr int ckpt_span(int J) { return J >= EXO_SPAN2_MIN_J ? 2 : 4; }
+// the lanes a draw of state width J takes in the sequential and the lane-group kernels: the next power of two (16: one DPP
+// row, J = 9 .. 16)
+EXO_HDH constexpr int group_width(int J) { return J <= 1 ? 1 : (J <= 2 ? 2 : (J <= 4 ? 4 : (J <= 8 ? 8 : 16))); }
 
 // Term coefficients of a batch of draws, celerite2's Term.get_coefficients() form:
 //   real  [n_draw][n_real][2]     (a, c)
@@ -74,6 +77,17 @@ struct Coefs {
   EXO_HDH int J() const { return n_real + 2 * n_complex; }
   EXO_HDH int64_t at(int64_t draw) const { return row ? (int64_t)row[draw] : draw; }
 };
+
+// the measurement variances of a draw: the one row all draws share (n_diag == 1), or the draw's own of the call's [n_draw][n]
+EXO_HD const double* diag_row(const double* diag, int64_t n_diag, const Coefs& cf, int64_t draw, int64_t n) {
+  return diag + (n_diag == 1 ? 0 : cf.at(draw) * n);
+}
+
+// the log-likelihood from acc = sum z_n^2 / d_n and logdet = sum log d_n; not positive definite -> -inf in band (a sampler
+// rejects the point)
+EXO_HD double loglike_of(double acc, double logdet, bool bad, int64_t n) {
+  return bad ? -INFINITY : fma(-0.5, acc + logdet, -(double)n * kHalfLog2Pi);
+}
 
 // per-state-index view: state index j of a real term (a, c) or of a complex pair (a, b, c, d);
 // `odd` marks the second index of a complex pair; `slot` = where the cotangents of a real term go
@@ -542,7 +556,7 @@ EXO_HDH ChunkGeom chunk_plan(int64_t n, int64_t n_draw, int J, int32_t n_chunks)
     if (C > 512) C = 512;
     if (C < 4) C = 4;
   } else {
-    const int G = J <= 1 ? 1 : (J <= 2 ? 2 : (J <= 4 ? 4 : (J <= 8 ? 8 : 16)));
+    const int G = group_width(J);
     // ~4 waves per SIMD offered to the lane-group chunk kernels of a group of eight (they fit 2-4): the scans over the chunks
     // are trees, so more chunks cost them little.  A row of sixteen (J >= 9): TWO -- its element and reverse kernels fit two
     // waves per SIMD, so 2048 waves are one full round of them, and its wide scan items (a block of 256 threads each) are
@@ -598,7 +612,7 @@ struct Sym {
 
 // Delta_n of one draw from its term coefficients and V_n (block diagonal: 1x1 / 2x2 blocks).
 // Delta is symmetric with Delta_n U_n = V_n: the state covariance of the process the kernel
-// describes, in celerite's rotating frame (exo_celerite.hip, "Time-parallel path").
+// describes, in celerite's rotating frame (exo_celerite_lanegroup.hpp, "Time-parallel path").
 // NR: the term layout, when it is known at compile time -- the first NR state indices are real terms,
 // the rest complex pairs -- or -1: decided per index at run time (pair slots of mixed kinds).  The
 // one-lane kernels pick the variant by a wave vote (with_layout): with the layout a constant, the
@@ -876,7 +890,7 @@ EXO_HD void elem_lane(const double* EXO_RESTRICT t, Series rs, const double* EXO
   DrawCoef<J, NR> co;
   co.init(cf, draw);
   const SeriesRowT<true, SP> y(rs, draw, n);
-  const double* EXO_RESTRICT dg = diag + (n_diag == 1 ? 0 : cf.at(draw) * n);
+  const double* EXO_RESTRICT dg = diag_row(diag, n_diag, cf, draw, n);
   double A[J][J], b[J], eta[J];
   Sym<J> Cm, Jm, Dl;
 #pragma unroll
@@ -1977,7 +1991,7 @@ EXO_HD void chunk1_fwd_lane(const double* EXO_RESTRICT t, Series rs, const doubl
   co.init(cf, draw);
   const double asum = co.asum();
   const SeriesRowT<true, SP> y(rs, draw, n);
-  const double* EXO_RESTRICT dg = diag + (n_diag == 1 ? 0 : cf.at(draw) * n);
+  const double* EXO_RESTRICT dg = diag_row(diag, n_diag, cf, draw, n);
   Fwd<J> f;
 #pragma unroll
   for (int j = 0; j < J; ++j) { f.U[j] = f.V[j] = f.W[j] = 0.0; }
@@ -2057,7 +2071,7 @@ EXO_HD void chunk1_fwd_lane(const double* EXO_RESTRICT t, Series rs, const doubl
     else load_block(y, dg, n_diag, b0 + kCkptB, n1, cur);
   }
   state[ws.part(c, 0, draw)] = acc;
-  state[ws.part(c, 1, draw)] = log(lman) + (double)lsum * 0.69314718055994530942;
+  state[ws.part(c, 1, draw)] = log(lman) + (double)lsum * exo::kLn2;
   state[ws.part(c, 2, draw)] = bad ? 1.0 : 0.0;
   if (EXO_GP_POLISH && save && n1 < n) {
     // what this chunk leaves for the next one: the step from its last cadence into cadence n1 (ChunkWs::polish; a polish
@@ -2098,7 +2112,7 @@ EXO_HD double phase_flux(const CoefT& co, int j, const double* F, const Sym<J>& 
 }
 
 // (C') reverse.  Hand-derived adjoint of the two recurrences (same algebra as celerite_vjp_kernel
-// of exo_celerite.hip, one lane holding every state index): Sb is the SYMMETRISED adjoint of S.
+// of exo_celerite_seq.hpp, one lane holding every state index): Sb is the SYMMETRISED adjoint of S.
 template <int J, int NR = -1>
 struct Rev {
   double Sb[J][J], Fb[J], Wb[J];
@@ -2237,7 +2251,7 @@ EXO_HD void chunk1_vjp_lane(const double* EXO_RESTRICT t, Series rs, const doubl
   const double asum = co.asum();
   const SeriesRowT<false, SP> y(rs, draw, n);
   GradRowT<SP> grow(gresid, rs, draw, n);
-  const double* EXO_RESTRICT dg = diag + (n_diag == 1 ? 0 : cf.at(draw) * n);
+  const double* EXO_RESTRICT dg = diag_row(diag, n_diag, cf, draw, n);
   const double gL = gloglike[cf.at(draw)];
   Rev<J, NR> r;
   const bool from_next = EXO_GP_POLISH && polish && n1 < n;
@@ -2400,7 +2414,7 @@ EXO_HD void chunk1_vjp_lane(const double* EXO_RESTRICT t, Series rs, const doubl
 
 // (C') reverse for wide states (J > 2): the same adjoint with the (symmetrised) adjoint of S PACKED, and
 // (chunkp_vjp_lane) two checkpoints per block.  Hand-derived adjoint of the two recurrences (same algebra as celerite_vjp_kernel
-// of exo_celerite.hip, one lane holding every state index): Sb is the SYMMETRISED adjoint of S.
+// of exo_celerite_seq.hpp, one lane holding every state index): Sb is the SYMMETRISED adjoint of S.
 // STATE_ONLY: the adjoints of the recurrence state alone (chunk_adj_lane): no coefficient cotangents, no phase flux
 template <int J, int NR = -1, bool STATE_ONLY = false>
 struct RevP {
@@ -2562,7 +2576,7 @@ EXO_HD void chunkp_vjp_lane(const double* EXO_RESTRICT t, Series rs, const doubl
   const double asum = co.asum();
   const SeriesRowT<false, SP> y(rs, draw, n);
   GradRowT<SP> grow(gresid, rs, draw, n);
-  const double* EXO_RESTRICT dg = diag + (n_diag == 1 ? 0 : cf.at(draw) * n);
+  const double* EXO_RESTRICT dg = diag_row(diag, n_diag, cf, draw, n);
   const double gL = gloglike[cf.at(draw)];
   RevP<J, NR> r;
   const bool from_next = EXO_GP_POLISH && polish && n1 < n;   // (polish: entered with what the next chunk's reverse recurrences left, chunk1_fwd_lane)
@@ -2771,7 +2785,7 @@ EXO_HD void chunk_adj_lane(const double* EXO_RESTRICT t, Series rs, const double
   co.init(cf, draw);
   const double asum = co.asum();
   const SeriesRowDesc y(rs, draw, n);
-  const double* EXO_RESTRICT dg = diag + (n_diag == 1 ? 0 : cf.at(draw) * n);
+  const double* EXO_RESTRICT dg = diag_row(diag, n_diag, cf, draw, n);
   const double gL = gloglike ? gloglike[cf.at(draw)] : 1.0;   // (null: a cotangent of one -- ChunkGeom::prep)
   constexpr bool all = ALL;
   const bool do_state = all || role == 0, is_R = all || role == J + 1, do_vec = all || role != 0;
@@ -3043,7 +3057,7 @@ EXO_HD void dot_tril_lane(const double* EXO_RESTRICT t, const double* EXO_RESTRI
   DrawCoef<J> co;
   co.init(cf, draw);
   const double asum = co.asum();
-  const double* EXO_RESTRICT dg = diag + (n_diag == 1 ? 0 : cf.at(draw) * n);
+  const double* EXO_RESTRICT dg = diag_row(diag, n_diag, cf, draw, n);
   const double* EXO_RESTRICT xr = x + draw * n;
   double* EXO_RESTRICT zr = z + draw * n;
   Fwd<J> f;

@@ -318,7 +318,7 @@ __device__ __forceinline__ void group_apply(const Grp<J>& g, int r, const ElemRo
 // the current application; no compositions there.  Measured at C5: an application of the chain is 4.6 us (2.3 for the adjoint
 // scan), so eight of them replace three levels' 68 + 40 us with 37 + 18: step 1.87 -> 1.83 ms; from sixteen positions up it is a
 // draw, from 32 a loss.  (For J <= 2 the same idea lost outright: a one-lane item is 5.5 us and a step of the chain 0.5 --
-// exo_celerite.hip.)  The chain is the better conditioned association of the two.
+// exo_celerite_scan.hpp.)  The chain is the better conditioned association of the two.
 template <int J, bool ADJ>
 __device__ __forceinline__ void tree_serial_group(const TreeOp& op, double* state, int64_t draw, const Grp<J>& g) {
   const int64_t nd = op.n_draw;

@@ -1,5 +1,5 @@
 // exo_celerite_predict.hpp -- the predictive variance of a celerite GP at sorted query times, one lane per draw:
-// the Kalman filter the factorisation already is (exo_celerite.hip, "Time-parallel path"), followed by the matching
+// the Kalman filter the factorisation already is (exo_celerite_lanegroup.hpp, "Time-parallel path"), followed by the matching
 // smoother, in O((N + M) J^2) per draw.  Host + device, like exo_celerite_core.hpp, whose Fwd / Phi / DrawCoef it reuses:
 // tests/gp_predict_var_harness.cpp runs the same functions with g++ against the dense definition.
 //
@@ -93,7 +93,7 @@ EXO_HD void predict_var_lane(const double* EXO_RESTRICT t, const double* EXO_RES
   const double asum = co.asum();
   double keep[J];
   const double k0 = predict_keep(co, cf, slot_mask, keep);
-  const double* EXO_RESTRICT dg = diag + (n_diag == 1 ? 0 : cf.at(draw) * n);
+  const double* EXO_RESTRICT dg = diag_row(diag, n_diag, cf, draw, n);
   double* EXO_RESTRICT wk = work + draw;
   const int64_t row = (int64_t)(J + 1) * n_draw;   // (a row's quantity k: wk[r * row + k * n_draw])
   double Uq[J], Vq[J];
@@ -240,7 +240,7 @@ EXO_HD void solve_lane(const double* EXO_RESTRICT t, const double* EXO_RESTRICT 
   DrawCoef<J> co;
   co.init(cf, draw);
   const double asum = co.asum();
-  const double* EXO_RESTRICT dg = diag + (n_diag == 1 ? 0 : cf.at(draw) * n);
+  const double* EXO_RESTRICT dg = diag_row(diag, n_diag, cf, draw, n);
   const double* EXO_RESTRICT yr = y + draw * n;
   double* EXO_RESTRICT ar = alpha + draw * n;
   double* EXO_RESTRICT wk = work + draw;

@@ -71,6 +71,7 @@ constexpr double kHalfPi = 1.57079632679489661923;
 constexpr double kTwoPiHi = 6.283185307179586;       // fl(2 pi)
 constexpr double kTwoPiLo = 2.4492935982947064e-16;  // 2 pi - fl(2 pi)
 constexpr double kTwoThirdsPi = 2.09439510239319549231;
+constexpr double kLn2 = 0.69314718055994530942;
 
 // x - sin(x) for x >= 0 given an independently known sin(x).
 // Taylor series below 0.9 (no cancellation), direct above.

@@ -10,6 +10,8 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "exo_math.hpp"
+
 #ifdef EXO_HOST_BUILD
 #define EXO_NZ_HD inline
 #else
@@ -23,7 +25,6 @@ constexpr int kQ = 0, kLam = 1, kG = 2, kH = 3, kA = 4, kTerms = 5;
 // a running product of mantissas is brought back to [0.5, 1) at least this often: every factor is >= 0.5, so the product
 // stays above 2^-512, far from the subnormals
 constexpr int kRenorm = 512;
-constexpr double kLn2 = 0.693147180559945309417232121458;
 
 // 1 / x: hardware seed (2^-24) and two Newton steps, as exo::fast_rcp; the host takes the division
 EXO_NZ_HD double rcp(double x) {
@@ -108,7 +109,7 @@ EXO_NZ_HD void logprod_renorm(LogProd& p) {
   p.m = frexp(p.m, &e);
   p.e += e;
 }
-EXO_NZ_HD double logprod_value(const LogProd& p) { return fma((double)p.e, kLn2, log(p.m)); }
+EXO_NZ_HD double logprod_value(const LogProd& p) { return fma((double)p.e, exo::kLn2, log(p.m)); }
 
 // ---- (b) element by element -----------------------------------------------------------------------------------------------
 struct Acc {

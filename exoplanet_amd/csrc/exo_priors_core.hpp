@@ -12,6 +12,7 @@
 #include <stdint.h>
 
 #include "../../include/exoplanet_amd.h"
+#include "exo_math.hpp"
 
 #ifdef EXO_HOST_BUILD
 #define EXO_PRI_HD inline
@@ -24,7 +25,6 @@ namespace pri {
 
 constexpr double kHalfLog2Pi = 0.91893853320467274178;    // log(2 pi) / 2
 constexpr double kLog2Pi = 1.83787706640934548356;
-constexpr double kLog2 = 0.69314718055994530942;
 constexpr double kHalfLog2OverPi = -0.22579135264472743236;  // log(2 / pi) / 2
 constexpr double kSqrtHalf = 0.70710678118654752440;
 
@@ -220,7 +220,7 @@ EXO_PRI_HD Elem elem(int kind, int flags, const double* p, double z0, double z1,
       e.d00 = 2.0 * a.s * a.sm;
       e.d10 = e.v1 * 0.5 * (a.sm - a.s);
       e.d11 = w * 2.0 * b.s * b.sm;
-      e.lp = La + (b.ls + b.lsm) + (kLog2 + 0.5 * La);
+      e.lp = La + (b.ls + b.lsm) + (exo::kLn2 + 0.5 * La);
       e.l0 = 1.5 * (a.sm - a.s);
       e.l1 = b.sm - b.s;
       break;

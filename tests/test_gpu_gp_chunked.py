@@ -304,6 +304,40 @@ def test_wide_state_takes_the_time_parallel_path(dev):
                 assert np.abs(g - w).max() / (np.abs(w).max() + 1e-300) < 1e-9
 
 
+@pytest.mark.parametrize("n_real,n_pair", [(1, 1), (0, 2), (2, 1)])
+def test_groups_of_four_take_the_time_parallel_path(dev, n_real, n_pair):
+    """J = 3 (a real term + a pair) and J = 4 -- as two pairs, the all-complex layout in kernels of its own (split_layouts), and as
+    two real terms + a pair, the run-time layout: a group of four lanes in the sequential kernels, the one-lane kernels'
+    layout choice in the chunked ones.  70 draws: two waves of the one-lane kernels, the last one ragged, five of the groups of
+    four.  chunked == sequential == dense"""
+    rng = np.random.default_rng(19 + 10 * n_real + n_pair)
+    N, D = 600, 70
+    t = np.sort(rng.uniform(0, 40, N))
+    y = 0.4 * rng.normal(size=(D, N))
+    diag = np.full((1, N), 0.05)
+    parts = [P.sho_coefficients(*P.sho_from_sigma_rho(s, r, q), q) for s, r, q in ((0.4, 20.0, 2.0), (0.2, 2.0, 0.8))[:n_pair]]
+    co = tuple(np.concatenate(x) for x in zip(*parts))
+    co = (np.array([0.3, 0.15][:n_real]), np.array([0.2, 1.3][:n_real])) + co[2:]
+    cr0, cc0 = _pack(co)
+    assert (cr0.shape[1], cc0.shape[1]) == (n_real, n_pair)
+    cr = np.repeat(cr0, D, 0) * (1 + 0.02 * rng.normal(size=(D,) + cr0.shape[1:]))
+    cc = np.repeat(cc0, D, 0)
+    cc[..., 0] *= 1 + 0.02 * rng.normal(size=cc[..., 0].shape)
+    cc[..., 1] = cc[..., 0] * (cc0[..., 1] / cc0[..., 0])      # keep b / a: SHO terms sit on |b d| = a c
+    with chunks(0):
+        want = value_and_grads(dev, t, y, diag, cr, cc)
+    with chunks(7):
+        got = value_and_grads(dev, t, y, diag, cr, cc)
+    assert not np.array_equal(got[0], want[0])                 # (not the sequential kernels' numbers: the chunked kernels ran)
+    np.testing.assert_allclose(got[0], want[0], rtol=1e-12)
+    for g, w in zip(got[1:], want[1:]):
+        if w.size:
+            assert np.abs(g - w).max() / (np.abs(w).max() + 1e-300) < 2e-9
+    co_d = (cr[0, :, 0], cr[0, :, 1], cc[0, :, 0], cc[0, :, 1], cc[0, :, 2], cc[0, :, 3])
+    ref, _ = P.gp_loglike_dense(t, y[0], diag[0], co_d)
+    assert abs(got[0][0] - ref) < 1e-10 * abs(ref)
+
+
 @pytest.mark.parametrize("J", [9, 10, 11, 12, 13, 14, 15, 16])
 def test_states_wider_than_eight_take_the_time_parallel_path(dev, J):
     """J = 9 .. 16 (round 6): the lane-group element / chunk kernels on a DPP row of sixteen lanes, the scans on blocks of 256

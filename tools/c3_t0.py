@@ -1,6 +1,6 @@
 """C3 step (bench.workload_c3) with the reference transit time moved along the series: python tools/c3_t0.py [t0 ...]
 The draws' transits drift apart away from t0 (their periods differ); where along the series that happens decides which
-chunks' waves are the slow ones on the sparse-mean route (exo_celerite.hip, chunk_of_block).  Prints ms per step."""
+chunks' waves are the slow ones on the sparse-mean route (exo_celerite_lane.hpp, chunk_of_block).  Prints ms per step."""
 import os
 import sys
 
