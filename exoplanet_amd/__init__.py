@@ -9,5 +9,6 @@ from .light_curves import LimbDarkLightCurve, SecondaryEclipseLightCurve  # noqa
 from .orbits import KeplerianOrbit  # noqa: F401
 from .graph import GraphedStep  # noqa: F401
 from .sampling import HMC, NUTS  # noqa: F401
+from .optimize import LBFGS, optimize  # noqa: F401  (xo.optimize is the function; the module: `from exoplanet_amd.optimize import ...`)
 
 __version__ = "0.1.0"

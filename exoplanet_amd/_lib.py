@@ -183,6 +183,9 @@ _SIGNATURES = {
     "exo_ttv_tables_vjp_f64": (ctypes.c_int, [_c_dp, _i64, _i64, _c_dp, _i64, _i64, _c_dp, _c_dp, _c_dp, _i64, _i32, _i32, _c_dp,
                                               _c_dp, _c_dp, _c_dp]),
     "exo_nuts_f64": (ctypes.c_int, [_c_dp, _i64, _i32, _i32, ctypes.c_double, _i32, _c_dp]),
+    # ptrs (host array of device pointers), n_chain, n_param, n_hist, max_linesearch, c1, gtol, ftol, phase, stream
+    "exo_lbfgs_f64": (ctypes.c_int, [_c_dp, _i64, _i32, _i32, _i32, ctypes.c_double, ctypes.c_double, ctypes.c_double, _i32,
+                                     _c_dp]),
     "exo_sho_coefficients_f64": (ctypes.c_int, [_c_dp, _c_dp, _c_dp, _u32, ctypes.c_double, _i64, _c_dp, _c_dp, _c_dp]),
     "exo_sho_coefficients_vjp_f64": (ctypes.c_int, [_c_dp, _c_dp, _c_dp, _u32, ctypes.c_double, _i64, _c_dp, _c_dp, _c_dp,
                                                     _c_dp, _c_dp]),

@@ -628,6 +628,21 @@ class ParameterSpace:
 
         return logp
 
+    def free_mask(self, names):
+        """(n_free,) mask, 1 in the columns of the named BLOCKS (their hyperparameters' columns included) and 0 elsewhere: the
+        ``free=[...]`` of `optimize` / `LBFGS`, what ``vars=`` is to the reference's ``pmx.optimize``"""
+        names = [names] if isinstance(names, str) else list(names)
+        mask = torch.zeros(self.n_free, dtype=torch.float64, device=self.device)
+        ends = [b[2] for b in self.blocks[1:]] + [self.n_free]
+        spans = {b[0]: (b[2], end) for b, end in zip(self.blocks, ends)}
+        for name in names:
+            if name not in spans:
+                owner = [b[0] for b in self.blocks if name in b[1].value_names(b[0]) or str(name).startswith(b[0] + "::")]
+                raise ValueError(f"{name!r} is a value of the block {owner[0]!r}: a mask names whole blocks" if owner else
+                                 f"no block named {name!r} (blocks: {[b[0] for b in self.blocks]})")
+            mask[spans[name][0]:spans[name][1]] = 1.0
+        return mask
+
     def unconstrain(self, D, **values):
         """starting points: the constrained ``values`` (numbers, or tensors of shape (count,), (D,), (D, 1), (1, count) or (D, count);
         a 1-D value is one per element when its length is ``count``, one per chain when it is D, and refused when D == count) of every

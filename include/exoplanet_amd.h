@@ -872,6 +872,27 @@ int exo_pack_records_cols_vjp_f64(const double* const* cols, const int64_t* draw
 int exo_nuts_f64(const void* const* ptrs, int64_t n_chain, int32_t n_param, int32_t n_slot, double max_energy_error,
                  int32_t phase, void* stream);
 
+/* Batched L-BFGS with a backtracking Armijo line search (exoplanet_amd/optimize.py: LBFGS -- the reference climbs to the
+ * posterior mode with pmx.optimize before it samples, docs/tutorials/data-and-models.md:287-296) on (chains, parameters)
+ * arrays that stay on the device: every chain minimises f = -logp on its own, all in lockstep.  The caller evaluates logp
+ * and its gradient at the trial points xt into lpt, gt; then
+ *   phase 0 (after the evaluation at the starting points, xt == x): status 4 for a chain whose value or gradient is not
+ *            finite, 1 for one that is converged already, else the first direction -g, the first step, the first trial point;
+ *   phase 1 (after every later evaluation): accept (history pair, or no history at all if s.y <= eps y.y; move; stop with status 1
+ *            when max |g_i| <= gtol or 2 when f_prev - f <= ftol max(|f_prev|, |f|, 1) for n_hist accepted steps in a
+ *            row; else the two-loop direction, its first scaling per column, and the next trial point) or reject (half the step; after max_linesearch in a row drop the history and restart
+ *            along -g, or stop if there was none: status 3, or 2 right after a small decrease).  A chain with a status other than 0 is left as it is.
+ * The rules in full: DESIGN.md section 15.  ptrs: HOST array of 22 device pointers -- x, g, xt, gt, d, free [D][n] (gt:
+ * in, the gradient of logp at xt; out, -gt * free; free: 0 / 1, a column with 0 never moves); hs, hy [n_hist][n][D] and
+ * hsy, coef [n_hist][D] (the kernels' own: pairs, s.y, workspace); logp, lpt, alpha, gamma, grad_max [D]; status,
+ * n_iter, n_eval, m, head, n_rej, n_small (int32 [D]).  Phase 0 initialises everything but x, xt, gt, lpt, free and the
+ * history's content.  EXO_ERR_INVALID_ARGUMENT: a null table or entry, n_chain < 0, n_param < 1, n_hist outside
+ * 1 .. EXO_LBFGS_MAX_HISTORY, max_linesearch < 1, a phase other than 0 or 1.  n_chain == 0: EXO_OK, nothing launched
+ * (sizes are checked first).  One launch, nothing else enqueued.  (Added without a new ABI number: no caller breaks.)  */
+#define EXO_LBFGS_MAX_HISTORY 32
+int exo_lbfgs_f64(const void* const* ptrs, int64_t n_chain, int32_t n_param, int32_t n_hist, int32_t max_linesearch, double c1,
+                  double gtol, double ftol, int32_t phase, void* stream);
+
 /* Timing tables of a TTVOrbit whose transits are all labelled and given as offsets `ttvs` from the linear ephemeris
  * (orbits/ttv.py:99-170): transit k of planet p of a draw at tt_k = t0 + period k + ttv_k, k < n_transit[p];
  *   edges [n_draw][n_planet][n_edge]      tt_0 - period/2, midpoints of neighbours, tt_last + period/2, then +inf
