@@ -186,6 +186,15 @@ _SIGNATURES = {
     # ptrs (host array of device pointers), n_chain, n_param, n_hist, max_linesearch, c1, gtol, ftol, phase, stream
     "exo_lbfgs_f64": (ctypes.c_int, [_c_dp, _i64, _i32, _i32, _i32, ctypes.c_double, ctypes.c_double, ctypes.c_double, _i32,
                                      _c_dp]),
+    "exo_diag_workspace_bytes": (_i64, [_i64, _i64, _i64]),
+    # x, sorted, sorted_full, n_full, n_param, n_half, n_len, folded, sets, moments, stream
+    "exo_diag_prepare_f64": (ctypes.c_int, [_c_dp, _c_dp, _c_dp, _i64, _i64, _i64, _i64, _c_dp, _c_dp, _c_dp, _c_dp]),
+    # sorted, perm, n_param, n_half, n_len, set, sets, stream
+    "exo_diag_rank_f64": (ctypes.c_int, [_c_dp, _c_dp, _i64, _i64, _i64, _i32, _c_dp, _c_dp]),
+    # sets, n_param, n_half, n_len, block, done, workspace, workspace_bytes, stream
+    "exo_diag_autocov_f64": (ctypes.c_int, [_c_dp, _i64, _i64, _i64, _i64, _c_dp, _c_dp, _i64, _c_dp]),
+    # n_param, n_half, n_len, block, moments, out, done, workspace, workspace_bytes, stream
+    "exo_diag_finish_f64": (ctypes.c_int, [_i64, _i64, _i64, _i64, _c_dp, _c_dp, _c_dp, _c_dp, _i64, _c_dp]),
     "exo_sho_coefficients_f64": (ctypes.c_int, [_c_dp, _c_dp, _c_dp, _u32, ctypes.c_double, _i64, _c_dp, _c_dp, _c_dp]),
     "exo_sho_coefficients_vjp_f64": (ctypes.c_int, [_c_dp, _c_dp, _c_dp, _u32, ctypes.c_double, _i64, _c_dp, _c_dp, _c_dp,
                                                     _c_dp, _c_dp]),

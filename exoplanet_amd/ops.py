@@ -2225,3 +2225,79 @@ def pack_records(orbit_in, ld_in, flags=0):
     limb-darkening coefficients (n_draw, 3|6): KeplerianOrbit.__init__ + get_cl + windows in
     one kernel, differentiable.  Slot order: include/exoplanet_amd.h EXO_IN_*."""
     return _PackRecords.apply(orbit_in, ld_in, int(flags))
+
+
+# ---- chain diagnostics (exo_diag_*_f64; the quantities are stated in exoplanet_amd/diagnostics.py) ------------------------------
+DIAG_LAG_BLOCK = 16   # include/exoplanet_amd.h EXO_DIAG_LAG_BLOCK
+DIAG_SETS = 5         # EXO_DIAG_SETS
+DIAG_MOMENTS = 8      # EXO_DIAG_MOMENTS
+DIAG_OUT = 16         # EXO_DIAG_OUT
+DIAG_COLUMNS = ("mean", "sd", "q05", "q50", "q95", "mcse_mean", "ess_bulk", "ess_tail", "ess_mean", "r_hat", "max_t_bulk",
+                "max_t_low", "max_t_high", "max_t_mean", "r_hat_z", "r_hat_folded")
+
+
+def diag_workspace_bytes(P, M, L):
+    return _lib.load().exo_diag_workspace_bytes(P, M, L)
+
+
+def chain_diagnostics(x_split, x_full, n_half, check_every=4, timings=None):
+    """The split diagnostics of P parameters: ``x_split`` (P, L, n_half) -- the half-chains of every parameter, innermost --
+    and ``x_full`` (P, n) with ALL draws of a parameter (None: no middle draw was dropped, the split values are all there
+    are).  Returns (P, DIAG_OUT), columns DIAG_COLUMNS.  The sorts are torch's, everything else the library's; the host
+    reads the device once per ``check_every`` lag blocks ("is every sequence truncated?").  ``timings``: a dict that receives
+    device events around the stages (tools/time_diagnostics.py)."""
+    x_split = _dev(x_split, "x_split")
+    P, L, M = (int(v) for v in x_split.shape)
+    if M != int(n_half) or M % 2 or L < 2:
+        raise ValueError("x_split must be (P, L, n_half) with an even n_half and L >= 2")
+    dev, S = x_split.device, L * M
+    out = torch.empty((P, DIAG_OUT), dtype=torch.float64, device=dev)
+    if P == 0 or M == 0:
+        return out
+    nbytes = diag_workspace_bytes(P, M, L)
+    if nbytes < 0:
+        raise ValueError("too many parameters for one call, or sizes that cannot be")
+    stream = _stream(x_split)
+
+    def mark(name):
+        if timings is not None:
+            ev = torch.cuda.Event(enable_timing=True)
+            ev.record()
+            timings.setdefault("events", []).append((name, ev))
+
+    mark("start")
+    flat = x_split.reshape(P, S)
+    sv, perm = torch.sort(flat, dim=1)
+    if x_full is None:
+        sf = sv
+    else:
+        sf = torch.sort(_dev(x_full, "x_full").reshape(P, -1), dim=1).values
+    mark("sort")
+    ws = torch.empty(nbytes // 8 + 1, dtype=torch.float64, device=dev)
+    sets = torch.empty((P, DIAG_SETS, S), dtype=torch.float64, device=dev)
+    folded = torch.empty((P, S), dtype=torch.float64, device=dev)
+    moments = torch.empty((P, DIAG_MOMENTS), dtype=torch.float64, device=dev)
+    done = torch.zeros(P * DIAG_SETS, dtype=torch.int32, device=dev)
+    _call("exo_diag_prepare_f64", dev, _ptr(flat), _ptr(sv), _ptr(sf), int(sf.shape[1]), P, M, L, _ptr(folded), _ptr(sets),
+          _ptr(moments), stream)
+    _call("exo_diag_rank_f64", dev, _ptr(sv), _ptr(perm), P, M, L, 0, _ptr(sets), stream)
+    mark("prepare + rank")
+    fsv, fperm = torch.sort(folded, dim=1)
+    mark("sort (folded)")
+    _call("exo_diag_rank_f64", dev, _ptr(fsv), _ptr(fperm), P, M, L, 1, _ptr(sets), stream)
+    mark("rank (folded)")
+    n_blocks = -(-L // DIAG_LAG_BLOCK)
+    check_every = max(int(check_every), 1)
+    used = 0
+    for block in range(n_blocks):
+        if block and block % check_every == 0 and bool(done.all()):
+            break
+        _call("exo_diag_autocov_f64", dev, _ptr(sets), P, M, L, block, _ptr(done), _ptr(ws), nbytes, stream)
+        _call("exo_diag_finish_f64", dev, P, M, L, block, 0, 0, _ptr(done), _ptr(ws), nbytes, stream)
+        used += 1
+    mark("autocovariance blocks + finish")
+    _call("exo_diag_finish_f64", dev, P, M, L, -1, _ptr(moments), _ptr(out), _ptr(done), _ptr(ws), nbytes, stream)
+    mark("assemble")
+    if timings is not None:
+        timings["lag_blocks"] = used
+    return out

@@ -26,7 +26,7 @@ import torch
 
 from .graph import GraphedStep
 
-__all__ = ["HMC", "NUTS"]
+__all__ = ["HMC", "NUTS", "Trace", "sample"]
 
 
 class _ChainSampler:
@@ -145,6 +145,10 @@ class HMC(_ChainSampler):
     parameter (broadcastable to it), default 1.  On a ROCm device the trajectory is replayed as a
     hipGraph (``graph=False`` launches it eagerly); on the CPU it simply runs -- the sampler logic is
     device-agnostic, which is how tests/test_sampling.py checks it without a GPU.
+
+    After ``step()``: ``last_logp``, ``last_accept_prob``, ``last_energy`` (the Hamiltonian at the start of the transition,
+    after the momenta were drawn: -logp(q0) + K(p0), Betancourt's E_n -- PyMC records the energy at the selected point
+    instead) and ``last_diverged`` (the proposal's energy error is not finite or beyond 1000).
     """
 
     def __init__(self, logp_fn, params, step_size, n_leapfrog, mass=None, graph=True, generator=None):
@@ -182,7 +186,8 @@ class HMC(_ChainSampler):
         p0 = torch.randn(q0.shape, dtype=q0.dtype, device=q0.device, generator=self.generator) * torch.sqrt(self._mflat)
         q1, p1, lp0, lp1 = self._graph(q0, p0) if self._graph is not None else self._trajectory(q0, p0)
         kin = lambda p: (0.5 * p * p / self._mflat).sum(1)  # noqa: E731
-        dH = (lp1 - kin(p1)) - (lp0 - kin(p0))                           # -(H1 - H0)
+        k0 = kin(p0)
+        dH = (lp1 - kin(p1)) - (lp0 - k0)                                # -(H1 - H0)
         u = self._rand()
         accept = torch.log(u) < dH                                        # NaN / -inf proposals are rejected
         qnew = torch.where(accept.unsqueeze(1), q1, q0)
@@ -191,6 +196,11 @@ class HMC(_ChainSampler):
         self.n_steps += 1
         self.n_accept += accept.to(self.n_accept.dtype)
         self.last_logp = torch.where(accept, lp1, lp0)
+        # the Hamiltonian at the start of the transition, after the momenta were drawn: -logp(q0) + K(p0), Betancourt's E_n
+        # (PyMC records the energy at the selected point instead); a proposal whose energy error is not finite or beyond 1000
+        # counts as divergent (Stan's threshold -- the fixed-length sampler has no other notion of it)
+        self.last_energy = -lp0 + k0
+        self.last_diverged = ~(dH > -1000.0)
         # acceptance probability min(1, exp(-dH)) of every chain (NaN proposals: 0): what step-size adaptation feeds on
         self.last_accept_prob = torch.nan_to_num(torch.exp(torch.clamp(dH, max=0.0)), nan=0.0)
         self.last_adapt_ok = torch.isfinite(lp0)           # (a chain outside the support says nothing about its step size)
@@ -228,7 +238,9 @@ class NUTS(_ChainSampler):
     along unchanged.  The host looks at the device once per doubling ("any chain still growing?").
 
     After ``step()``: ``last_accept_prob`` (mean over the trajectory's leaves of min(1, exp(H0 - H)): what ``warmup``
-    adapts the step sizes to), ``last_depth``, ``last_diverged``, ``last_logp``; ``n_divergent`` counts per chain.
+    adapts the step sizes to), ``last_depth``, ``last_diverged``, ``last_logp``, ``last_energy`` (the Hamiltonian at the start
+    of the transition, after the momenta were drawn: -logp(q0) + K(p0), Betancourt's E_n -- PyMC records the energy at the
+    selected point instead); ``n_divergent`` counts per chain.
     """
 
     def __init__(self, logp_fn, params, step_size, max_depth=8, mass=None, graph=True, generator=None,
@@ -425,6 +437,7 @@ class NUTS(_ChainSampler):
         self._lp, self._g = st["proplp"].clone(), st["propg"].clone()
         self.n_steps += 1
         self.last_logp = self._lp
+        self.last_energy = H0        # -logp(q0) + K(p0): the energy at the START of the transition (PyMC: at the selected point)
         self.last_depth = st["depth"].clone()
         self.last_diverged = st["diverged"].clone()
         self.last_accept_prob = st["acc"] / torch.clamp(st["accn"], min=1.0)
@@ -442,3 +455,60 @@ class NUTS(_ChainSampler):
     def mean_depth(self):
         """per-chain mean tree depth so far (device tensor)"""
         return self.sum_depth / max(self.n_steps, 1)
+
+
+class Trace:
+    """What `sample` returns.  ``draws`` (n_draws, chains, n): the unconstrained flat array -- all parameter blocks of a chain
+    side by side, as the samplers hold them -- on the sampler's device; ``stats``: {"logp", "energy", "accept_prob",
+    "diverging" and "depth" (NUTS) / "accepted" (HMC)}, each (n_draws, chains); ``eps`` (chains,) and ``mass`` (one tensor per
+    parameter block): the step sizes and masses at the end of the warm-up; ``n_tune``; ``sampler`` ("hmc" / "nuts").
+    Plain tensors: no xarray, no pandas.  `diagnostics.summary` takes a trace as it is."""
+
+    def __init__(self, draws, stats, eps, mass, n_tune, sampler):
+        self.draws, self.stats, self.eps, self.mass, self.n_tune, self.sampler = draws, stats, eps, mass, n_tune, sampler
+
+    def __len__(self):
+        return int(self.draws.shape[0])
+
+    def constrain(self, space):
+        """the draws through ``space.constrain`` (`distributions.ParameterSpace`): {name: (n_draws, chains, count)} and
+        "log_prior" (n_draws, chains)"""
+        n_draws, chains, n = self.draws.shape
+        with torch.no_grad():
+            theta, log_prior = space.constrain(self.draws.reshape(n_draws * chains, n))
+        out = {k: v.reshape(n_draws, chains, *v.shape[1:]) for k, v in theta.items()}
+        out["log_prior"] = log_prior.reshape(n_draws, chains)
+        return out
+
+
+@torch.no_grad()
+def sample(sampler, draws=1000, tune=0, target_accept=0.8, adapt_mass=False):
+    """``draws`` transitions of an `HMC` or `NUTS` sampler, kept: a `Trace`.  ``tune > 0`` runs the sampler's own
+    ``warmup(tune, target_accept=..., adapt_mass=...)`` first.  The draws and the per-draw statistics go into arrays
+    allocated once, before the loop; the loop calls ``step()`` and copies device to device -- it reads nothing on the host
+    (NUTS's one look per doubling is the sampler's own) and takes no random numbers: the chain is, bit for bit, the one
+    that as many plain ``step()`` calls produce from the same generator state."""
+    nuts = isinstance(sampler, NUTS)
+    if not nuts and not isinstance(sampler, HMC):
+        raise TypeError("sample takes an HMC or a NUTS sampler")
+    draws, tune = int(draws), int(tune)
+    if draws < 0 or tune < 0:
+        raise ValueError("need draws >= 0 and tune >= 0")
+    if tune > 0:
+        sampler.warmup(tune, target_accept=target_accept, adapt_mass=adapt_mass)
+    q = sampler._flat(sampler.params)
+    D, dev = sampler.D, q.device
+    out = torch.empty((draws,) + tuple(q.shape), dtype=q.dtype, device=dev)
+    real = lambda: torch.empty((draws, D), dtype=q.dtype, device=dev)  # noqa: E731
+    flag = lambda: torch.empty((draws, D), dtype=torch.bool, device=dev)  # noqa: E731
+    stats = dict(logp=real(), energy=real(), accept_prob=real(), diverging=flag())
+    stats["depth" if nuts else "accepted"] = real() if nuts else flag()
+    for i in range(draws):
+        ret = sampler.step()
+        sampler._flat(sampler.params, out=out[i])
+        stats["logp"][i].copy_(sampler.last_logp)
+        stats["energy"][i].copy_(sampler.last_energy)
+        stats["accept_prob"][i].copy_(sampler.last_accept_prob)
+        stats["diverging"][i].copy_(sampler.last_diverged)
+        stats["depth" if nuts else "accepted"][i].copy_(ret)
+    return Trace(out, stats, sampler.eps.clone(), [m.clone() for m in sampler.mass], tune, "nuts" if nuts else "hmc")

@@ -1046,6 +1046,49 @@ int exo_prior_transform_f64(const double* z, int64_t n_chain, int32_t n_free, co
 int exo_prior_transform_vjp_f64(const double* z, int64_t n_chain, int32_t n_free, const exo_prior_block* table, int32_t n_block,
                                 const double* const* gtheta, const double* glog_prior, double* gz, void* stream);
 
+/* -------------------------------------------------------------------------
+ * Rank-normalised split diagnostics of a batch of chains (Vehtari, Gelman, Simpson, Carpenter & Buerkner 2021): R-hat, bulk /
+ * tail / mean effective sample sizes, the Monte-Carlo standard error of the mean, moments and quantiles, per parameter
+ * (exoplanet_amd/diagnostics.py states every quantity in torch).  A call handles n_param parameters;
+ * after splitting each chain into its first and last halves a parameter is n_half = 2 chains half-chains of n_len draws,
+ * S = n_half n_len values, held pooled as [n_len][n_half] (half-chains innermost).  The caller sorts -- nothing else:
+ *   1. sorted, perm = sort of x [n_param][S]; sorted_full [n_param][n_full] = sort of ALL draws of a parameter (the same
+ *      array when no middle draw was dropped);
+ *   2. exo_diag_prepare_f64: folded [n_param][S] = |x - median|; sets [n_param][EXO_DIAG_SETS][S]: the tail indicators
+ *      1[x <= q05], 1[x <= q95] (sets 2, 3) and x minus a pivot (set 4); moments [n_param][EXO_DIAG_MOMENTS]
+ *      = mean, sd (ddof 1), q05, q50, q95 (linear interpolation), not-finite, constant, the pivot;
+ *   3. exo_diag_rank_f64 with (sorted, perm) into set 0 and with the sort of `folded` into set 1: average ranks (ties share the
+ *      mean of their ranks), z = Phi^-1((r - 3/8) / (S + 1/4)), scattered through perm (int64, values outside 0 .. S - 1
+ *      are skipped);
+ *   4. for block = 0, 1, ...: exo_diag_autocov_f64 (lags block EXO_DIAG_LAG_BLOCK .. + EXO_DIAG_LAG_BLOCK - 1 of every set
+ *      that is not done) then exo_diag_finish_f64 with the same block (rho_t, Geyer's initial positive sequence, and -- once a
+ *      set's sequence has ended -- the monotone sequence, tau, the effective sample size, done[set] = 1); blocks in order,
+ *      until every done [n_param EXO_DIAG_SETS] (int32, zeroed by the caller) is 1: after ceil(n_len / EXO_DIAG_LAG_BLOCK)
+ *      blocks at the latest;
+ *   5. exo_diag_finish_f64 with block = -1: out [n_param][EXO_DIAG_OUT] = mean, sd, q05, q50, q95, mcse_mean, ess_bulk,
+ *      ess_tail, ess_mean, r_hat, max_t of the bulk / lower tail / upper tail / mean sequences, R-hat of z and of folded z.
+ * A parameter with a value that is not finite: NaN everywhere (max_t -1); a constant one: ESS = S, R-hat NaN.
+ * workspace: exo_diag_workspace_bytes(n_param, n_half, n_len) bytes, the same array in every call of steps 4 and 5; -1 for
+ * sizes that cannot be.  EXO_ERR_INVALID_ARGUMENT, before any launch: negative sizes, n_len < 2, an odd n_half, n_param
+ * EXO_DIAG_SETS > 65535, n_full < S, a set other than 0 or 1, a block outside the series, a null pointer;
+ * EXO_ERR_WORKSPACE: too small.  n_param == 0 or n_half == 0: EXO_OK, nothing launched (sizes are checked first).
+ * Kernels only; every sum in a fixed order, no atomics: bit-reproducible.  (Added without a new ABI number: no caller
+ * breaks.)
+ * ------------------------------------------------------------------------- */
+#define EXO_DIAG_LAG_BLOCK 16
+#define EXO_DIAG_SETS 5
+#define EXO_DIAG_MOMENTS 8
+#define EXO_DIAG_OUT 16
+int64_t exo_diag_workspace_bytes(int64_t n_param, int64_t n_half, int64_t n_len);
+int exo_diag_prepare_f64(const double* x, const double* sorted, const double* sorted_full, int64_t n_full, int64_t n_param,
+                         int64_t n_half, int64_t n_len, double* folded, double* sets, double* moments, void* stream);
+int exo_diag_rank_f64(const double* sorted, const int64_t* perm, int64_t n_param, int64_t n_half, int64_t n_len, int32_t set,
+                      double* sets, void* stream);
+int exo_diag_autocov_f64(const double* sets, int64_t n_param, int64_t n_half, int64_t n_len, int64_t block, const int32_t* done,
+                         void* workspace, int64_t workspace_bytes, void* stream);
+int exo_diag_finish_f64(int64_t n_param, int64_t n_half, int64_t n_len, int64_t block, const double* moments, double* out,
+                        int32_t* done, void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
