@@ -208,25 +208,30 @@ def error(c, q, got):
     assert got.shape == c.want[q].shape, (c.name, q, got.shape, c.want[q].shape)
     if not np.all(np.isfinite(got)):
         return np.inf
-    return float(np.abs(got - c.want[q]).max() / c.scale[q]) if got.size else 0.0
+    if not got.size:
+        return 0.0
+    # (the scale may be an array, one per element: tests/gp_like_cases.py; a zero scale admits only an exact zero)
+    d, sc = np.abs(got - c.want[q]), np.broadcast_to(np.asarray(c.scale[q], dtype=np.float64), got.shape)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return float(np.where(sc > 0, d / sc, np.where(d == 0, 0.0, np.inf)).max())
 
 
-def factor(name, q):
-    return ENTRY_FACTOR.get((name, q.split("_m")[0]), FACTOR)
+def factor(name, q, table=None):
+    return (ENTRY_FACTOR if table is None else table).get((name, q.split("_m")[0]), FACTOR)
 
 
 def tol(c, q):
-    return max(factor(c.name, q) * c.unit[q], FLOOR)
+    """(a case of another fixture carries its own table of factors as ``ENTRY_FACTOR``)"""
+    return max(factor(c.name, q, getattr(c, "ENTRY_FACTOR", None)) * c.unit[q], FLOOR)
 
 
 def check(label, c, got, skip=()):
-    """print unit, tolerance and error of every quantity in ``got`` (dict), then assert them against the fixture"""
+    """print unit, tolerance and error of every quantity in ``got`` (dict), then assert them against the fixture; a quantity
+    in ``skip`` is printed and not asserted"""
     bad = []
     for q, v in got.items():
-        if q in skip:
-            continue
         err, tl = error(c, q, v), tol(c, q)
-        print(f"{label} {c.name} {q}: unit = {c.unit[q]:.3g}, tolerance = {tl:.3g}, error = {err:.3g}")
-        if not err <= tl:
+        print(f"{label} {c.name} {q}: unit = {c.unit[q]:.3g}, tolerance = {tl:.3g}, error = {err:.3g}" + (" (not asserted)" if q in skip else ""))
+        if q not in skip and not err <= tl:
             bad.append((q, err, tl))
     assert not bad, (label, c.name, bad)
