@@ -139,6 +139,9 @@ _SIGNATURES = {
     # oversample, objective, out, workspace, workspace_bytes, stream
     "exo_bls_power_f64": (ctypes.c_int, [_c_dp, _c_dp, _c_dp, _i64, _i64, _i64, _c_dp, _i64, _i64, _i64, _c_dp, _i32,
                                          ctypes.c_double, _i32, _i32, _c_dp, _c_dp, _i64, _c_dp]),
+    # ... objective, templates (device, flat), template_offsets (host, n_duration + 1), out, workspace, workspace_bytes, stream
+    "exo_tls_power_f64": (ctypes.c_int, [_c_dp, _c_dp, _c_dp, _i64, _i64, _i64, _c_dp, _i64, _i64, _i64, _c_dp, _i32,
+                                         ctypes.c_double, _i32, _i32, _c_dp, _c_dp, _c_dp, _c_dp, _i64, _c_dp]),
     # t, y, yerr, n_yerr, n, n_series, frequencies, n_frequency, power, workspace, workspace_bytes, stream
     "exo_lomb_scargle_power_f64": (ctypes.c_int, [_c_dp, _c_dp, _c_dp, _i64, _i64, _i64, _c_dp, _i64, _c_dp, _c_dp, _i64, _c_dp]),
     "exo_radial_velocity_fwd_f64": (ctypes.c_int, [_c_dp, _i64, _c_dp, _i64, _i32, _c_dp, _c_dp]),

@@ -1,7 +1,8 @@
-// exo_estimators.hip -- period search (exoplanet_amd/estimators.py): the box-least-squares periodogram and the exact
-// floating-mean Lomb-Scargle periodogram of a batch of series on one time axis.  Pre-fit utilities beside the per-step
-// path: a translation unit of its own, so that none of the likelihood's kernels changes.  The arithmetic of one period
-// lives in exo_estimators_core.hpp (tested on the host); definitions, resources and timings: DESIGN.md section 9.
+// exo_estimators.hip -- period search (exoplanet_amd/estimators.py): the box-least-squares periodogram, its limb-darkened
+// twin (transit least squares: a template in place of the box) and the exact floating-mean Lomb-Scargle periodogram of a
+// batch of series on one time axis.  Pre-fit utilities beside the per-step path: a translation unit of its own, so that
+// none of the likelihood's kernels changes.  The arithmetic of one period lives in exo_estimators_core.hpp (tested on the
+// host); definitions, resources and timings: DESIGN.md sections 9 and 18.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -28,6 +29,10 @@ constexpr int kLsThreads = 256;
 
 struct Durations {
   int32_t m[kMaxDur];  // boxes of m[k] bins, computed on the host
+};
+
+struct Templates {
+  int32_t off[kMaxDur + 1];  // template k of the template search: entries off[k] .. off[k] + m[k] - 1 of the flat table
 };
 
 // workspace, in doubles: [0] t_min, [1] t_max, [2 + 2 b] Y_b, [3 + 2 b] W_b, then tt[n], w[n_w][n], wy[n_series][n], then the slabs
@@ -119,15 +124,13 @@ __global__ __launch_bounds__(kPrepThreads) void est_prepare_kernel(const double*
 // The order in which the lanes' adds arrive is not fixed, so a bin's sum may differ in its last bits from run to run.
 __device__ __forceinline__ void add_f64(double* p, double v) { unsafeAtomicAdd(p, v); }
 
-// One period of one series: histogram of (w y, w) over the bins of the folded time, the wrap-around copy, inclusive prefix
-// sums in place, the search over (duration, start) and the outputs.  hy, hw: n_bins + 1 entries each, in LDS or in a slab of
+// The histogram pass of one period of one series, shared by the box search and the template search: zero, histogram of
+// (w y, w) over the bins of the folded time, the wrap-around copy.  hy, hw: n_bins + 1 entries each, in LDS or in a slab of
 // the workspace that this workgroup alone uses (kGlobal: the fences that make its atomics visible to its own plain loads).
 template <bool kGlobal>
-__device__ __forceinline__ void bls_period(double* hy, double* hw, int64_t n_bins, const double* __restrict__ tt,
-                                           const double* __restrict__ w, const double* __restrict__ wy, int64_t n, double p,
-                                           double delta, int oversample, const Durations& dur, int n_dur, double Y, double W,
-                                           double t_min, int objective, double* out, int64_t out_stride, double* red_d,
-                                           int64_t* red_i) {
+__device__ __forceinline__ void bls_histogram(double* hy, double* hw, int64_t n_bins, const double* __restrict__ tt,
+                                              const double* __restrict__ w, const double* __restrict__ wy, int64_t n, double p,
+                                              double delta, int oversample) {
   const int tid = threadIdx.x, nt = blockDim.x;
   for (int64_t i = tid; i <= n_bins; i += nt) {
     hy[i] = 0.0;
@@ -149,6 +152,36 @@ __device__ __forceinline__ void bls_period(double* hy, double* hw, int64_t n_bin
     hw[n_bins - oversample + i] = hw[i];
   }
   __syncthreads();
+}
+
+// the arg-max of the workgroup from every lane's own (first maximiser in (k, s) order): shuffles, then LDS; valid in thread 0
+__device__ __forceinline__ BlsBest block_best(BlsBest best, double* red_d, int64_t* red_i) {
+  const int tid = threadIdx.x, nt = blockDim.x;
+  for (int o = kWave / 2; o > 0; o >>= 1) {
+    const double obj = __shfl_down(best.obj, o, kWave);
+    const int64_t key = __shfl_down((long long)best.key, o, kWave);
+    bls_best_take(best, obj, key);
+  }
+  if (tid % kWave == 0) {
+    red_d[tid / kWave] = best.obj;
+    red_i[tid / kWave] = best.key;
+  }
+  __syncthreads();
+  if (tid == 0)
+    for (int i = 1; i < nt / kWave; ++i) bls_best_take(best, red_d[i], red_i[i]);
+  return best;
+}
+
+// One period of one series of the box search: the histogram pass, inclusive prefix sums in place, the search over (duration,
+// start) and the outputs.
+template <bool kGlobal>
+__device__ __forceinline__ void bls_period(double* hy, double* hw, int64_t n_bins, const double* __restrict__ tt,
+                                           const double* __restrict__ w, const double* __restrict__ wy, int64_t n, double p,
+                                           double delta, int oversample, const Durations& dur, int n_dur, double Y, double W,
+                                           double t_min, int objective, double* out, int64_t out_stride, double* red_d,
+                                           int64_t* red_i) {
+  const int tid = threadIdx.x, nt = blockDim.x;
+  bls_histogram<kGlobal>(hy, hw, n_bins, tt, w, wy, n, p, delta, oversample);
   // inclusive prefix sums: each lane its own stretch, the lanes' totals scanned by lane 0's wave, then the offsets added
   const int64_t per = (n_bins + nt) / nt, lo = 1 + (int64_t)tid * per, hi = lo + per < n_bins + 1 ? lo + per : n_bins + 1;
   double ay = 0.0, aw = 0.0;
@@ -181,21 +214,28 @@ __device__ __forceinline__ void bls_period(double* hy, double* hw, int64_t n_bin
   }
   __syncthreads();
   // every lane its share of the candidates, then the arg-max of the wave and of the workgroup (first maximiser in (k, s) order)
-  BlsBest best = bls_search(hy, hw, n_bins, dur.m, n_dur, Y, W, objective, tid, nt);
-  for (int o = kWave / 2; o > 0; o >>= 1) {
-    const double obj = __shfl_down(best.obj, o, kWave);
-    const int64_t key = __shfl_down((long long)best.key, o, kWave);
-    bls_best_take(best, obj, key);
-  }
-  if (tid % kWave == 0) {
-    red_d[tid / kWave] = best.obj;
-    red_i[tid / kWave] = best.key;
-  }
+  const BlsBest best = block_best(bls_search(hy, hw, n_bins, dur.m, n_dur, Y, W, objective, tid, nt), red_d, red_i);
+  if (tid == 0) bls_outputs(hy, hw, n_bins, dur.m, Y, W, objective, best, p, delta, t_min, out, out_stride);
   __syncthreads();
-  if (tid == 0) {
-    for (int i = 1; i < nt / kWave; ++i) bls_best_take(best, red_d[i], red_i[i]);
-    bls_outputs(hy, hw, n_bins, dur.m, Y, W, objective, best, p, delta, t_min, out, out_stride);
-  }
+}
+
+// One period of one series of the template search: the histogram pass, then the correlation of the
+// histogram itself with every template -- lanes over the starts s, strided by the workgroup, so that neighbouring lanes read
+// neighbouring bins; k outer, j inner.  g: the flat table in global memory, read under an index that is uniform across the wave.
+template <bool kGlobal>
+__device__ __forceinline__ void tls_period(double* hy, double* hw, int64_t n_bins, const double* __restrict__ tt,
+                                           const double* __restrict__ w, const double* __restrict__ wy, int64_t n, double p,
+                                           double delta, int oversample, const Durations& dur, const Templates& tpl, int n_dur,
+                                           const double* __restrict__ g, double Y, double W, double t_min, int objective,
+                                           double* out, int64_t out_stride, double* red_d, int64_t* red_i) {
+  const int tid = threadIdx.x, nt = blockDim.x;
+  bls_histogram<kGlobal>(hy, hw, n_bins, tt, w, wy, n, p, delta, oversample);
+  const BlsBest best =
+      block_best(tls_search((const double*)hy, (const double*)hw, n_bins, dur.m, tpl.off, n_dur, g, Y, W, objective, tid, nt),
+                 red_d, red_i);
+  if (tid == 0)
+    tls_outputs((const double*)hy, (const double*)hw, n_bins, dur.m, tpl.off, g, Y, W, objective, best, p, delta, t_min, out,
+                out_stride);
   __syncthreads();
 }
 
@@ -242,6 +282,53 @@ __global__ __launch_bounds__(kSlabThreads) void bls_slab_kernel(const double* __
     }
     bls_period<true>(slab, slab + n_bins + 1, n_bins, ws + L.tt(), ws + L.w(b), ws + L.wy(b), L.n, p, delta, oversample, dur,
                      n_dur, ws[2 + 2 * b], ws[3 + 2 * b], ws[0], objective, o, L.n_series * n_period, red_d, red_i);
+  }
+}
+
+// the template search's pair: the geometry, the switch on n_bins and the fences of the box search's kernels
+__global__ __launch_bounds__(kBlsThreads) void tls_lds_kernel(const double* __restrict__ periods, int64_t n_period, Layout L,
+                                                              double delta, int oversample, Durations dur, Templates tpl,
+                                                              int n_dur, const double* __restrict__ g, int objective,
+                                                              int64_t lds_bins, const double* __restrict__ ws,
+                                                              double* __restrict__ out) {
+  extern __shared__ double hist[];
+  __shared__ double red_d[kBlsThreads / kWave];
+  __shared__ int64_t red_i[kBlsThreads / kWave];
+  const int64_t ip = blockIdx.x, b = blockIdx.y;
+  const double p = periods[ip];
+  const int64_t n_bins = bls_n_bins(p, delta, oversample);
+  if (n_bins > kLdsBins) return;  // the slab kernel's
+  if (n_bins > lds_bins) {        // (more bins than the caller's max_bins announced: nothing is written past the histogram)
+    if (threadIdx.x == 0)
+      for (int i = 0; i < 7; ++i) out[(i * L.n_series + b) * n_period + ip] = NAN;
+    return;
+  }
+  tls_period<false>(hist, hist + n_bins + 1, n_bins, ws + L.tt(), ws + L.w(b), ws + L.wy(b), L.n, p, delta, oversample, dur, tpl,
+                    n_dur, g, ws[2 + 2 * b], ws[3 + 2 * b], ws[0], objective, out + b * n_period + ip, L.n_series * n_period,
+                    red_d, red_i);
+}
+
+__global__ __launch_bounds__(kSlabThreads) void tls_slab_kernel(const double* __restrict__ periods, int64_t n_period, Layout L,
+                                                                double delta, int oversample, Durations dur, Templates tpl,
+                                                                int n_dur, const double* __restrict__ g, int objective,
+                                                                int64_t max_bins, double* __restrict__ ws,
+                                                                double* __restrict__ out) {
+  __shared__ double red_d[kSlabThreads / kWave];
+  __shared__ int64_t red_i[kSlabThreads / kWave];
+  double* slab = ws + L.slabs() + (int64_t)blockIdx.x * 2 * (max_bins + 1);
+  for (int64_t item = blockIdx.x; item < n_period * L.n_series; item += gridDim.x) {
+    const int64_t ip = item % n_period, b = item / n_period;
+    const double p = periods[ip];
+    const int64_t n_bins = bls_n_bins(p, delta, oversample);
+    if (n_bins <= kLdsBins) continue;
+    double* o = out + b * n_period + ip;
+    if (n_bins > max_bins) {  // (the host sized the slabs from these very periods: not reached)
+      if (threadIdx.x == 0)
+        for (int i = 0; i < 7; ++i) o[i * L.n_series * n_period] = NAN;
+      continue;
+    }
+    tls_period<true>(slab, slab + n_bins + 1, n_bins, ws + L.tt(), ws + L.w(b), ws + L.wy(b), L.n, p, delta, oversample, dur, tpl,
+                     n_dur, g, ws[2 + 2 * b], ws[3 + 2 * b], ws[0], objective, o, L.n_series * n_period, red_d, red_i);
   }
 }
 
@@ -355,6 +442,45 @@ int exo_bls_power_f64(const double* t, const double* y, const double* yerr, int6
   if (max_bins > kLdsBins)
     hipLaunchKernelGGL(bls_slab_kernel, dim3((unsigned)n_slabs(n_series, n_period, max_bins)), dim3(kSlabThreads), 0, s, periods,
                        n_period, L, delta, (int)oversample, dur, (int)n_duration, (int)objective, max_bins, ws, out);
+  return launch_status();
+}
+
+int exo_tls_power_f64(const double* t, const double* y, const double* yerr, int64_t n_yerr, int64_t n, int64_t n_series,
+                      const double* periods, int64_t n_period, int64_t min_bins, int64_t max_bins, const int32_t* duration_bins,
+                      int32_t n_duration, double delta, int32_t oversample, int32_t objective, const double* templates,
+                      const int32_t* template_offsets, double* out, void* workspace, int64_t workspace_bytes, void* stream) {
+  if (n_period == 0) return EXO_OK;
+  if (!series_ok(n, n_series, n_yerr) || n_period < 0 || n_period > INT32_MAX || !t || !y || (n_yerr > 0 && !yerr) ||
+      !periods || !duration_bins || n_duration < 1 || n_duration > kMaxDur || !(delta > 0.0) || oversample < 1 ||
+      (objective != EXO_BLS_LIKELIHOOD && objective != EXO_BLS_SNR) || min_bins < 1 || max_bins < min_bins || !templates ||
+      !template_offsets || !out || !workspace)
+    return EXO_ERR_INVALID_ARGUMENT;
+  Durations dur{};
+  Templates tpl{};
+  if (template_offsets[0] < 0) return EXO_ERR_INVALID_ARGUMENT;
+  tpl.off[0] = template_offsets[0];
+  for (int k = 0; k < n_duration; ++k) {
+    // (in int64: an offset near INT32_MAX must not wrap into a match)
+    if (duration_bins[k] < 1 || (int64_t)template_offsets[k] + duration_bins[k] != template_offsets[k + 1] ||
+        template_offsets[k + 1] > EXO_TLS_MAX_TEMPLATE)
+      return EXO_ERR_INVALID_ARGUMENT;
+    dur.m[k] = duration_bins[k];
+    tpl.off[k + 1] = template_offsets[k + 1];
+  }
+  if (workspace_bytes < exo_bls_workspace_bytes(n, n_series, n_period, max_bins)) return EXO_ERR_WORKSPACE;
+  const Layout L = layout(n, n_series, n_yerr);
+  double* ws = (double*)workspace;
+  hipStream_t s = (hipStream_t)stream;
+  prepare(t, y, n_yerr > 0 ? yerr : nullptr, n_yerr, L, 0, ws, s);
+  if (min_bins <= kLdsBins) {
+    const int64_t bins = max_bins < kLdsBins ? max_bins : kLdsBins;
+    hipLaunchKernelGGL(tls_lds_kernel, dim3((unsigned)n_period, (unsigned)n_series), dim3(kBlsThreads),
+                       (size_t)(16 * (bins + 1)), s, periods, n_period, L, delta, (int)oversample, dur, tpl, (int)n_duration,
+                       templates, (int)objective, bins, (const double*)ws, out);
+  }
+  if (max_bins > kLdsBins)
+    hipLaunchKernelGGL(tls_slab_kernel, dim3((unsigned)n_slabs(n_series, n_period, max_bins)), dim3(kSlabThreads), 0, s, periods,
+                       n_period, L, delta, (int)oversample, dur, tpl, (int)n_duration, templates, (int)objective, max_bins, ws, out);
   return launch_status();
 }
 

@@ -1,7 +1,8 @@
 // exo_estimators_core.hpp -- the per-period arithmetic of the period-search estimators (exoplanet_amd/estimators.py):
-// the box-least-squares bin index and objective, and the closed-form floating-mean Lomb-Scargle power from its
-// weighted sums.  Definitions and derivations: DESIGN.md section 9.  Compiles for the device (exo_estimators.hip) and,
-// with EXO_HOST_BUILD, for the host (tests/estimators_harness.cpp checks it against the numpy restatement without a GPU).
+// the box-least-squares bin index and objective, the template search on the same bins (transit least squares), and the
+// closed-form floating-mean Lomb-Scargle power from its weighted sums.  Definitions and derivations: DESIGN.md sections 9
+// and 18.  Compiles for the device (exo_estimators.hip) and, with EXO_HOST_BUILD, for the host (tests/estimators_harness.cpp
+// and tests/tls_harness.cpp check it against the numpy restatements without a GPU).
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -116,6 +117,82 @@ EXO_EST_HD void bls_outputs(Ptr cy, Ptr cw, int64_t n_bins, const int32_t* m, do
   out[2 * stride] = b.depth_err;
   out[3 * stride] = b.depth_snr;
   out[4 * stride] = b.log_likelihood;
+  out[5 * stride] = (double)mk * delta;
+  out[6 * stride] = fmod((double)s * delta + 0.5 * (double)mk * delta + t_min, p);
+}
+
+// ---- transit least squares: a template in place of the box -----------------------------------------------
+
+struct TlsWindow {
+  double A, B, C, w_in;  // sum g hw, sum g^2 hw, sum g hy, sum hw over the window
+  double D, depth, depth_err, depth_snr, log_likelihood;
+  bool ok;  // w_in > 0, W - w_in > 0 and D > 0
+};
+
+// one window of the histogram hy, hw (NOT prefix sums): bins s + 1 .. s + mk against the template g[0 .. mk - 1], ascending j.
+// The model c - depth g inside, c outside, both fitted: D = B - A^2 / W, depth = (A Y / W - C) / D.  Every product that could
+// be contracted into a fused multiply-add is written as one, so that the search and the recomputation at the maximiser, and
+// the host and the device build, do the same operations.
+template <class Ptr, class GPtr>
+EXO_EST_HD TlsWindow tls_window(Ptr hy, Ptr hw, GPtr g, int64_t s, int64_t mk, double Y, double W) {
+  TlsWindow r;
+  double A = 0.0, B = 0.0, C = 0.0, w_in = 0.0;
+#ifndef EXO_HOST_BUILD
+#pragma unroll 4  // (four bins' loads in flight before the first fma waits for them; each sum keeps its ascending order)
+#endif
+  for (int64_t j = 0; j < mk; ++j) {
+    const double gj = g[j], wj = hw[s + 1 + j], yj = hy[s + 1 + j];
+    A = fma(gj, wj, A);
+    B = fma(gj * gj, wj, B);
+    C = fma(gj, yj, C);
+    w_in += wj;
+  }
+  r.A = A, r.B = B, r.C = C, r.w_in = w_in;
+  r.D = fma(-A, A / W, B);
+  r.ok = w_in > 0.0 && W - w_in > 0.0 && r.D > 0.0;
+  const double root = sqrt(r.D);
+  r.depth = fma(A, Y / W, -C) / r.D;
+  r.depth_err = 1.0 / root;
+  r.depth_snr = r.depth * root;
+  r.log_likelihood = 0.5 * r.depth * r.depth * r.D;
+  return r;
+}
+
+EXO_EST_HD double tls_objective(const TlsWindow& w, int objective) { return objective ? w.depth_snr : w.log_likelihood; }
+
+// the search of one period over the histogram hy, hw[0 .. n_bins] for the lanes `lane`, lane + n_lane, ... of every duration;
+// template k is g[off[k] .. off[k] + m[k] - 1].  Keys and ties as in bls_search.
+template <class Ptr, class GPtr>
+EXO_EST_HD BlsBest tls_search(Ptr hy, Ptr hw, int64_t n_bins, const int32_t* m, const int32_t* off, int n_dur, GPtr g, double Y,
+                              double W, int objective, int64_t lane, int64_t n_lane) {
+  BlsBest best = bls_best_init();
+  for (int k = 0; k < n_dur; ++k) {
+    const int64_t mk = m[k];
+    if (mk < 1) continue;
+    for (int64_t s = lane; s + mk <= n_bins; s += n_lane) {
+      const TlsWindow w = tls_window(hy, hw, g + off[k], s, mk, Y, W);
+      if (w.ok) bls_best_take(best, tls_objective(w, objective), (int64_t)k * (n_bins + 1) + s);
+    }
+  }
+  return best;
+}
+
+// the seven outputs at the maximiser, laid out as bls_outputs'; its window is summed again in the order of the search
+template <class Ptr, class GPtr>
+EXO_EST_HD void tls_outputs(Ptr hy, Ptr hw, int64_t n_bins, const int32_t* m, const int32_t* off, GPtr g, double Y, double W,
+                            int objective, BlsBest best, double p, double delta, double t_min, double* out, int64_t stride) {
+  if (best.key == INT64_MAX) {
+    out[0] = -INFINITY;
+    for (int i = 1; i < 7; ++i) out[i * stride] = NAN;
+    return;
+  }
+  const int64_t k = best.key / (n_bins + 1), s = best.key % (n_bins + 1), mk = m[k];
+  const TlsWindow w = tls_window(hy, hw, g + off[k], s, mk, Y, W);
+  out[0] = tls_objective(w, objective);
+  out[1 * stride] = w.depth;
+  out[2 * stride] = w.depth_err;
+  out[3 * stride] = w.depth_snr;
+  out[4 * stride] = w.log_likelihood;
   out[5 * stride] = (double)mk * delta;
   out[6 * stride] = fmod((double)s * delta + 0.5 * (double)mk * delta + t_min, p);
 }

@@ -1,12 +1,15 @@
 """Period search and the other pre-fit estimators of the reference's ``exoplanet.estimators``: where ``period0`` and ``t00``
-come from.  The two periodograms are HIP kernels (csrc/exo_estimators.hip) and are computed exactly on an unthinned grid, for
+come from.  The periodograms are HIP kernels (csrc/exo_estimators.hip) and are computed exactly on an unthinned grid, for
 many series on one time axis at once; the glue around them keeps the reference's names, arguments, defaults and dictionary
-keys.  Definitions: DESIGN.md section 9.
+keys.  Definitions: DESIGN.md section 9, and section 18 for transit least squares -- the box search's twin with a
+limb-darkened template in place of the box, whose ``depth`` is the mid-transit depth and therefore a starting ``r`` (not in
+the reference).
 
-Low level (device tensors in and out, float64): :func:`bls_power`, :func:`lomb_scargle_power`, and the grids
-:func:`bls_autoperiod`, :func:`lomb_scargle_autofrequency` (host arithmetic).
+Low level (device tensors in and out, float64): :func:`bls_power`, :func:`tls_power` (its templates:
+:func:`transit_template`), :func:`lomb_scargle_power`, and the grids :func:`bls_autoperiod`,
+:func:`lomb_scargle_autofrequency` (host arithmetic).
 
-High level (numpy arrays or tensors in, numpy out, ``peaks`` hold Python floats): :func:`bls_estimator`,
+High level (numpy arrays or tensors in, numpy out, ``peaks`` hold Python floats): :func:`bls_estimator`, :func:`tls_estimator`,
 :func:`lomb_scargle_estimator`, :func:`autocorr_estimator`, :func:`find_peaks`, :func:`estimate_semi_amplitude`,
 :func:`estimate_minimum_mass`.  Plain numbers throughout: days, m/s and solar masses in, m/s and Jupiter masses out.
 
@@ -15,9 +18,9 @@ sizes and the choice of kernel need them there -- and their device copies are ca
 enqueues kernels only and can be captured into a graph after one eager call.  Given as device tensors they are copied to the
 host once per call, which waits for the stream; that is the only synchronisation in this module's low-level functions.
 
-Run-to-run differences: the box search sums each phase bin with fp64 atomic adds, whose order is not fixed; ``power`` and the
-other outputs may differ in their last bits between two runs on the same input (and a near-tie between two boxes may then
-resolve differently).  The Lomb-Scargle sums have a fixed order and are bitwise reproducible.
+Run-to-run differences: the box search and the template search sum each phase bin with fp64 atomic adds, whose order is not
+fixed; ``power`` and the other outputs may differ in their last bits between two runs on the same input (and a near-tie
+between two boxes may then resolve differently).  The Lomb-Scargle sums have a fixed order and are bitwise reproducible.
 """
 import collections
 import ctypes
@@ -28,11 +31,12 @@ import torch
 from . import _lib
 
 __all__ = [
-    "bls_power", "lomb_scargle_power", "bls_autoperiod", "lomb_scargle_autofrequency", "find_peaks", "bls_estimator",
-    "lomb_scargle_estimator", "autocorr_function", "autocorr_estimator", "estimate_semi_amplitude", "estimate_minimum_mass",
+    "bls_power", "tls_power", "transit_template", "lomb_scargle_power", "bls_autoperiod", "lomb_scargle_autofrequency",
+    "find_peaks", "bls_estimator", "tls_estimator", "lomb_scargle_estimator", "autocorr_function", "autocorr_estimator", "estimate_semi_amplitude", "estimate_minimum_mass",
 ]
 
 MAX_DURATIONS = 16      # EXO_BLS_MAX_DURATIONS
+MAX_TEMPLATE = 8192     # EXO_TLS_MAX_TEMPLATE: bins of all templates of a call together
 _OBJECTIVES = {None: 0, "likelihood": 0, "snr": 1}
 BLS_FIELDS = ("power", "depth", "depth_err", "depth_snr", "log_likelihood", "duration", "transit_time")
 
@@ -162,6 +166,110 @@ def bls_power(t, y, yerr=None, *, periods, durations, oversample=10, objective="
     return res
 
 
+_template_cache = collections.OrderedDict()
+
+
+def transit_template(m, ror=0.1, b=0.0, u=(0.4804, 0.1867)):
+    """The shape of a quadratically limb-darkened transit for :func:`tls_power`: the flux deficit of a straight-line transit of
+    impact parameter ``b`` and radius ratio ``ror`` from first to fourth contact, sampled at the ``m`` bin centres
+    ``x_j = (2 j + 1) / m - 1`` and divided by the deficit at mid-transit, so that the fitted ``depth`` is the mid-transit depth:
+    ``z = sqrt(b^2 + ((1 + ror)^2 - b^2) x^2)``, ``g = lc(z, ror; u) / lc(b, ror; u)``.  A numpy array (m,).  The flux comes from
+    the package's own solution-vector kernel (``ops.quad_solution_vector``), so a ROCm device is needed; results are remembered
+    per argument set, and a repeated call touches no device."""
+    if int(m) != m or m < 1:
+        raise ValueError(f"m must be an integer >= 1, got {m}")
+    ror, b = float(ror), float(b)
+    if not ror > 0:
+        raise ValueError(f"ror must be positive, got {ror}")
+    if not 0 <= b < 1:
+        raise ValueError(f"b must lie in [0, 1), got {b}")
+    u = tuple(float(v) for v in np.atleast_1d(np.asarray(u, dtype=np.float64)))
+    if len(u) != 2:
+        raise ValueError(f"u must hold the two quadratic limb-darkening coefficients, got {u}")
+    key = (int(m), ror, b, u)
+    hit = _template_cache.get(key)
+    if hit is not None:
+        _template_cache.move_to_end(key)
+        return hit.copy()
+    from . import ops
+
+    dev = _device_of()
+    x = (2.0 * np.arange(int(m)) + 1.0) / int(m) - 1.0
+    z = np.sqrt(b * b + ((1.0 + ror) ** 2 - b * b) * x * x)
+    zd = torch.as_tensor(np.append(z, b), dtype=torch.float64, device=dev)
+    s = ops.quad_solution_vector(zd, torch.full_like(zd, ror)).cpu().numpy()
+    c = np.array([1.0 - u[0] - 1.5 * u[1], u[0] + 2.0 * u[1], -0.25 * u[1]])
+    lc = s @ (c / (np.pi * (c[0] + c[1] / 1.5))) - 1.0
+    g = lc[:-1] / lc[-1]
+    _template_cache[key] = g.copy()
+    while len(_template_cache) > 64:
+        _template_cache.popitem(last=False)
+    return g
+
+
+def _template_table(templates, m, ror, b, u):
+    """-> the flat host table of the K templates and its K + 1 offsets (int32)"""
+    if templates is None:
+        templates = [transit_template(int(mk), ror, b, u) for mk in m]
+    elif isinstance(templates, (torch.Tensor, np.ndarray)) and templates.ndim != 1:
+        raise ValueError(f"templates must be a list of {len(m)} one-dimensional arrays, got an array of shape {tuple(templates.shape)}")
+    elif isinstance(templates, (torch.Tensor, np.ndarray)):
+        templates = [templates]
+    if len(templates) != len(m):
+        raise ValueError(f"templates must hold one array per duration ({len(m)}), got {len(templates)}")
+    rows = [np.atleast_1d(_np(g)) for g in templates]
+    for k, (g, mk) in enumerate(zip(rows, m)):
+        if g.ndim != 1 or g.size != mk:
+            raise ValueError(f"template {k} must have shape ({int(mk)},), the duration in bins, got {tuple(g.shape)}")
+        if not np.all(np.isfinite(g)):
+            raise ValueError(f"template {k} is not finite: {g[~np.isfinite(g)][:3]}")
+    offsets = np.concatenate([[0], np.cumsum([g.size for g in rows])])
+    if offsets[-1] > MAX_TEMPLATE:
+        raise ValueError(f"the templates hold {int(offsets[-1])} bins in all, more than the {MAX_TEMPLATE} a call takes")
+    return np.ascontiguousarray(np.concatenate(rows)), offsets.astype(np.int32)
+
+
+def tls_power(t, y, yerr=None, *, periods, durations, templates=None, ror=0.1, b=0.0, u=(0.4804, 0.1867), oversample=10,
+              objective="likelihood"):
+    """Transit-least-squares periodogram on the bins of :func:`bls_power`: every box is replaced by a template ``g_k`` of
+    ``m_k = round(d_k / delta)`` bins, and the level and the depth of the model ``c - depth * g_k`` inside the window, ``c``
+    outside, are fitted jointly by weighted least squares.
+
+    Arguments and results as :func:`bls_power`, with ``templates``: a list of K arrays of lengths ``m_k`` (``bls_plan`` gives
+    them), finite; None: :func:`transit_template` of ``ror``, ``b`` and ``u`` for every duration.  ``depth`` is the factor of the
+    template (the mid-transit depth for a template that is 1 there), ``depth_err = 1 / sqrt(D)``, ``log_likelihood`` exactly half
+    the drop in chi-squared against a constant.  With all-ones templates the depth, its error and its signal to noise are
+    :func:`bls_power`'s.  Host templates are cached on the device by content, as the grids are."""
+    if objective not in _OBJECTIVES:
+        raise ValueError(f"unknown objective {objective!r}: 'likelihood' or 'snr'")
+    t, y, yerr, batched = _device_series(t, y, yerr)
+    p_host, p_dev = _grid(periods, "periods", t.device)
+    d_host = np.atleast_1d(_np(durations))
+    if d_host.ndim != 1:
+        raise ValueError("durations must be one-dimensional")
+    delta, m, n_bins = bls_plan(p_host, d_host, oversample)
+    table, offsets = _template_table(templates, m, ror, b, u)
+    _, g_dev = _grid(table, "templates", t.device)
+    B, N, P = y.shape[0], y.shape[1], p_host.size
+    out = torch.empty((7, B, P), dtype=torch.float64, device=t.device)
+    if P:
+        lib = _lib.load()
+        lo, hi = int(n_bins.min()), int(n_bins.max())
+        nbytes = lib.exo_bls_workspace_bytes(N, B, P, hi)
+        if nbytes < 0:
+            raise ValueError("tls_power: invalid sizes")
+        ws = _workspace(nbytes, t.device)
+        _lib.check(lib.exo_tls_power_f64(t.data_ptr(), y.data_ptr(), 0 if yerr is None else yerr.data_ptr(),
+                                         0 if yerr is None else yerr.shape[0], N, B, p_dev.data_ptr(), P, lo, hi,
+                                         m.ctypes.data_as(ctypes.c_void_p), m.size, delta, int(oversample), _OBJECTIVES[objective],
+                                         g_dev.data_ptr(), offsets.ctypes.data_as(ctypes.c_void_p), out.data_ptr(), ws.data_ptr(),
+                                         ws.numel() * 8, _stream(t)), "exo_tls_power_f64")
+    res = BLSResult(period=p_dev)
+    for i, k in enumerate(BLS_FIELDS):
+        res[k] = out[i] if batched else out[i, 0]
+    return res
+
+
 def lomb_scargle_power(t, y, yerr=None, *, frequencies):
     """Floating-mean Lomb-Scargle periodogram, exact sums, "psd" normalisation: ``(chi2_0 - chi2(f)) / 2`` with ``chi2(f)`` the
     weighted least-squares misfit of ``a sin(2 pi f t) + b cos(2 pi f t) + c``.  ``y`` (N,) or (B, N) -> (F,) or (B, F)."""
@@ -264,6 +372,20 @@ def find_peaks(freq, power, max_peaks=0):
     return peaks[0]
 
 
+def _estimator_periods(xc, durations, min_period, max_period, minimum_n_transit, frequency_factor):
+    """the period grid of the transit estimators; ``frequency_factor=None``: doubled until there are no more periods than cadences"""
+    grid = lambda ff: bls_autoperiod(xc, durations, minimum_period=min_period, maximum_period=max_period,  # noqa: E731
+                                     minimum_n_transit=minimum_n_transit, frequency_factor=ff)
+    if frequency_factor is not None:
+        return grid(frequency_factor)
+    frequency_factor = 1.0
+    periods = grid(frequency_factor)
+    while len(periods) > len(xc):
+        frequency_factor *= 2
+        periods = grid(frequency_factor)
+    return periods
+
+
 def bls_estimator(x, y, yerr=None, duration=0.2, min_period=None, max_period=None, objective=None, method=None, oversample=10,
                   frequency_factor=None, minimum_n_transit=3):
     """Estimate the period of a transit signal by box least squares.  Returns ``bls`` (the periodogram: numpy arrays under the
@@ -275,16 +397,7 @@ def bls_estimator(x, y, yerr=None, duration=0.2, min_period=None, max_period=Non
     xh = _np(x)
     x_ref = 0.5 * (xh.min() + xh.max())
     durations = np.atleast_1d(np.asarray(duration, dtype=np.float64))
-    grid = lambda ff: bls_autoperiod(xh - x_ref, durations, minimum_period=min_period, maximum_period=max_period,
-                                     minimum_n_transit=minimum_n_transit, frequency_factor=ff)
-    if frequency_factor is None:
-        frequency_factor = 1.0
-        periods = grid(frequency_factor)
-        while len(periods) > len(xh):
-            frequency_factor *= 2
-            periods = grid(frequency_factor)
-    else:
-        periods = grid(frequency_factor)
+    periods = _estimator_periods(xh - x_ref, durations, min_period, max_period, minimum_n_transit, frequency_factor)
     yd = _to(y, dev)
     res = bls_power(_to(xh - x_ref, dev), yd - torch.median(yd), _to(yerr, dev), periods=periods, durations=durations,
                     oversample=oversample, objective="likelihood" if objective is None else objective)
@@ -296,6 +409,54 @@ def bls_estimator(x, y, yerr=None, duration=0.2, min_period=None, max_period=Non
     if peaks:
         ind = peaks[0]["index"]
         results["peak_info"] = dict((k, float(v[ind])) for k, v in pg.items() if k != "objective")
+    return results
+
+
+def tls_estimator(x, y, yerr=None, duration=0.2, min_period=None, max_period=None, objective=None, oversample=10,
+                  frequency_factor=None, minimum_n_transit=3, ror=0.1, b=0.0, u=(0.4804, 0.1867)):
+    """Estimate the period, the mid-transit depth and from it the radius ratio of a transit signal by transit least squares:
+    :func:`bls_estimator`'s twin on :func:`tls_power` with the :func:`transit_template` of ``ror``, ``b`` and ``u`` (the same grid
+    and thinning rule, the median subtracted).  Returns ``tls`` (the periodogram: numpy arrays under the keys of
+    :class:`BLSResult`, and ``sr`` and ``sde_spectrum``), ``peaks`` and ``peak_info``.
+
+    ``sr = min chi2 / chi2(p)`` with ``chi2(p) = chi2_0 - 2 log_likelihood(p)``, ``chi2_0 = sum w (y - ybar)^2``, over the periods
+    of finite power (NaN elsewhere); ``sde_spectrum = (sr - mean) / std``.  ``peak_info`` holds the periodogram's values at the
+    peak, ``sde = (1 - mean) / std``, and ``ror`` from ``LimbDarkLightCurve(*u).get_ror_from_approx_transit_depth(depth, b)``: a
+    starting value for ``r`` (NaN for a brightening)."""
+    from .light_curves.limb_dark import LimbDarkLightCurve
+
+    dev = _device_of(x, y)
+    xh = _np(x)
+    x_ref = 0.5 * (xh.min() + xh.max())
+    durations = np.atleast_1d(np.asarray(duration, dtype=np.float64))
+    periods = _estimator_periods(xh - x_ref, durations, min_period, max_period, minimum_n_transit, frequency_factor)
+    objective = "likelihood" if objective is None else objective
+    yd, ed = _to(y, dev), _to(yerr, dev)
+    yd = yd - torch.median(yd)
+    res = tls_power(_to(xh - x_ref, dev), yd, ed, periods=periods, durations=durations, ror=ror, b=b, u=u, oversample=oversample,
+                    objective=objective)
+    # the signal residue and its detection efficiency, over the periods with a fit
+    w = torch.ones_like(yd) if ed is None else 1.0 / ed.expand_as(yd) ** 2
+    chi2_0 = (w * (yd - (w * yd).sum() / w.sum()) ** 2).sum()
+    chi2 = chi2_0 - 2.0 * res["log_likelihood"]
+    ok = torch.isfinite(res["power"])
+    nan = torch.full_like(chi2, float("nan"))
+    sr = torch.where(ok, chi2[ok].min() / chi2, nan) if bool(ok.any()) else nan
+    mean, std = sr[ok].mean(), sr[ok].std()
+    pg = BLSResult((k, _np(v)) for k, v in res.items())
+    pg["transit_time"] = pg["transit_time"] + x_ref
+    pg["sr"], pg["sde_spectrum"] = _np(sr), _np((sr - mean) / std)
+    pg["objective"] = objective
+    peaks = find_peaks(1.0 / pg["period"], pg["power"], max_peaks=1)
+    results = dict(tls=pg, peaks=peaks, peak_info=None)
+    if peaks:
+        ind = peaks[0]["index"] - 1           # (find_peaks counts from one: this is the grid's highest sample itself)
+        info = dict((k, float(pg[k][ind])) for k in ("period",) + BLS_FIELDS)
+        info["sde"] = float((1.0 - mean) / std)
+        star = LimbDarkLightCurve(torch.tensor(u[0], dtype=torch.float64), torch.tensor(u[1], dtype=torch.float64))
+        info["ror"] = float(star.get_ror_from_approx_transit_depth(torch.tensor(info["depth"], dtype=torch.float64),
+                                                                   torch.tensor(float(b), dtype=torch.float64)))
+        results["peak_info"] = info
     return results
 
 

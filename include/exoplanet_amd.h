@@ -984,6 +984,22 @@ int exo_lomb_scargle_power_f64(const double* t, const double* y, const double* y
                                const double* frequencies, int64_t n_frequency, double* power, void* workspace,
                                int64_t workspace_bytes, void* stream);
 
+/* Transit least squares on the same bins (definition: DESIGN.md section 18): the box of duration k is replaced by a template
+ * g_k[0 .. duration_bins[k] - 1], and the level c and the depth of the model "c - depth g_k inside the window, c outside" are
+ * fitted jointly by weighted least squares; log_likelihood is half the drop in chi-squared against a constant, exactly.
+ * The arguments of exo_bls_power_f64, the same out[7][n_series][n_period] and the same workspace
+ * (exo_bls_workspace_bytes), plus templates: ONE flat table on the device, finite values (the caller's promise), and
+ * template_offsets: HOST array of n_duration + 1 entries, template k at templates[template_offsets[k] ..
+ * template_offsets[k + 1] - 1].  EXO_ERR_INVALID_ARGUMENT, before any launch: what exo_bls_power_f64 rejects, a null table or
+ * null offsets, template_offsets[0] < 0, template_offsets[k + 1] - template_offsets[k] != duration_bins[k], a table that
+ * ends beyond EXO_TLS_MAX_TEMPLATE entries (64 KiB).  With every template entry 1 the depth, its error and its signal to
+ * noise are the box search's.  (Added without a new ABI number: no caller breaks.) */
+#define EXO_TLS_MAX_TEMPLATE 8192
+int exo_tls_power_f64(const double* t, const double* y, const double* yerr, int64_t n_yerr, int64_t n, int64_t n_series,
+                      const double* periods, int64_t n_period, int64_t min_bins, int64_t max_bins, const int32_t* duration_bins,
+                      int32_t n_duration, double delta, int32_t oversample, int32_t objective, const double* templates,
+                      const int32_t* template_offsets, double* out, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---------------------------------------------------------------------------
  * Priors and constrained parameters (exoplanet_amd/distributions.py; definitions and measurements: DESIGN.md section 10).
  * One unconstrained array z[n_chain][n_free] -- the flat array the samplers integrate -- becomes the constrained, named

@@ -1,0 +1,290 @@
+"""GPU: estimators.tls_power, transit_template and tls_estimator -- the template-search kernels (tls_lds_kernel, tls_slab_kernel)
+against the brute-force numpy restatement of DESIGN.md section 18 (tests/tls_oracle.py).
+
+Tolerances are not constants (DESIGN.md 9.5's rule): every case computes, on its own input, the largest relative difference
+between the oracle run in float64 and in np.longdouble at the same maximiser, and allows 16 times that with a floor of 1e-13,
+relative to each period's own value.  `power` is compared on every period; the other fields too where the kernel's maximiser is
+the oracle's, and where a near-tie picked another window they are checked for consistency through tls_at.  Periods the oracle
+flags as fragile (a cadence within 1e-9 of a bin edge) may be left out, at most 2 % of a case's; the inputs here have none.
+tls_oracle.check prints the figures before it asserts; DESIGN.md section 18 records them as measured on an MI355X."""
+import functools
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import estimators_oracle as O  # noqa: E402
+import tls_oracle as TO  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+DURATIONS, OVERSAMPLE = (0.1, 0.2, 0.4), 10
+TRUE_DEPTH = 0.0120687                          # lc(b = 0.3, ror = 0.1; u): the injected mid-transit depth
+
+
+def T(a, dev):
+    return None if a is None else torch.as_tensor(np.asarray(a, dtype=np.float64), dtype=torch.float64, device=dev)
+
+
+def host(res, row=None):
+    out = {k: v.cpu().numpy() for k, v in res.items()}
+    return out if row is None else {k: (v[row] if v.ndim == 2 else v) for k, v in out.items()}
+
+
+def templates_for(durations, oversample, ror=TO.TRUE["ror"], b=TO.TRUE["b"]):
+    return [TO.transit_template(int(m), ror, b) for m in O.bls_plan(durations, oversample)[1]]
+
+
+@functools.lru_cache(maxsize=None)
+def main_case(objective, with_yerr, offset=0.0, ones=False):
+    """the main input and its oracle pair, computed once and shared; nothing in it is modified afterwards"""
+    t, y = TO.main_input(offset=offset)
+    yerr = 2e-3 * (0.5 + np.random.RandomState(5).uniform(size=t.size)) if with_yerr else None
+    periods = TO.main_periods()
+    tpl = [np.ones(int(m)) for m in O.bls_plan(DURATIONS, OVERSAMPLE)[1]] if ones else templates_for(DURATIONS, OVERSAMPLE)
+    return t, y, yerr, periods, tpl, TO.unit_and_reference(t, y, yerr, periods, DURATIONS, tpl, OVERSAMPLE, objective)
+
+
+@pytest.mark.parametrize("objective", ["likelihood", "snr"])
+@pytest.mark.parametrize("with_yerr", [False, True])
+def test_tls_power_against_the_oracle(dev, objective, with_yerr):
+    from exoplanet_amd.estimators import tls_power
+
+    t, y, yerr, periods, tpl, ref = main_case(objective, with_yerr)
+    res = tls_power(T(t, dev), T(y, dev), T(yerr, dev), periods=periods, durations=DURATIONS, templates=tpl, oversample=OVERSAMPLE,
+                    objective=objective)
+    got = host(res)
+    assert got["power"].shape == (203,) and np.array_equal(got["period"], periods) and set(got) == set(O.FIELDS) | {"period"}
+    TO.check(f"main input, {objective}, yerr {with_yerr}", got, t, y, yerr, periods, DURATIONS, tpl, OVERSAMPLE, objective, reference=ref)
+    assert abs(periods[np.argmax(got["power"])] - 2.345) < 2e-4
+    # templates=None builds the same templates through the package's own solution-vector kernel
+    if objective == "likelihood" and not with_yerr:
+        auto = host(tls_power(T(t, dev), T(y, dev), periods=periods, durations=DURATIONS, ror=TO.TRUE["ror"], b=TO.TRUE["b"]))
+        TO.check("main input, templates=None", auto, t, y, None, periods, DURATIONS, tpl, OVERSAMPLE, objective, reference=ref)
+
+
+def test_tls_power_with_y_near_one(dev):
+    """the same series around 1 instead of 0: A Y / W - C cancels three digits, which the rule's unit measures and absorbs"""
+    from exoplanet_amd.estimators import tls_power
+
+    t, y, _, periods, tpl, ref = main_case("likelihood", False, offset=1.0)
+    got = host(tls_power(T(t, dev), T(y, dev), periods=periods, durations=DURATIONS, templates=tpl))
+    TO.check("main input, y near 1", got, t, y, None, periods, DURATIONS, tpl, OVERSAMPLE, "likelihood", reference=ref)
+
+
+def test_tls_batch_with_per_series_yerr(dev):
+    """three series with their own error bars in one call; row b is the single call to the rule's tolerance (the order of the
+    atomic adds differs) and both are the oracle's"""
+    from exoplanet_amd.estimators import tls_power
+
+    t, y = TO.main_input()
+    rs = np.random.RandomState(2)
+    Y = y[None] + 1e-3 * rs.randn(3, t.size)
+    E = 2e-3 * (0.5 + rs.uniform(size=(3, t.size)))
+    periods = np.concatenate([TO.main_periods()[:200:5], [2.345, 2.3449, 4.69]])
+    tpl = templates_for(DURATIONS, OVERSAMPLE)
+    kw = dict(periods=periods, durations=DURATIONS, templates=tpl)
+    batch = tls_power(T(t, dev), T(Y, dev), T(E, dev), **kw)
+    assert batch["power"].shape == (3, len(periods)) and batch["period"].shape == (len(periods),)
+    for b in range(3):
+        tol, _ = TO.check(f"series {b} of a batch", host(batch, b), t, Y[b], E[b], periods, DURATIONS, tpl, OVERSAMPLE, "likelihood")
+        one = host(tls_power(T(t, dev), T(Y[b], dev), T(E[b], dev), **kw))
+        diff = O.rel_diff(host(batch, b)["power"], one["power"])
+        print(f"[series {b}] batched against the single call: {diff:.2e}")
+        assert diff <= tol
+    # a shared (N,) yerr
+    shared = tls_power(T(t, dev), T(Y, dev), T(E[0], dev), **kw)
+    TO.check("shared yerr, series 2", host(shared, 2), t, Y[2], E[0], periods, DURATIONS, tpl, OVERSAMPLE, "likelihood")
+
+
+def test_tls_across_the_switch_of_paths(dev):
+    """3810 .. 3860 bins: the largest histogram LDS holds is 3835 bins, so both kernels run in one call, neighbours on either
+    side; and one period of 20 010 bins deep in the slab path"""
+    from exoplanet_amd.estimators import bls_plan, tls_power
+
+    rs = np.random.RandomState(722)
+    t = np.sort(rs.uniform(0, 120, 3000))
+    y = 2e-3 * rs.randn(3000)
+    y[np.abs((t - 7.0 + 19.1) % 38.2 - 19.1) < 0.08] -= 0.01
+    durations = (0.1, 0.16)
+    periods = np.concatenate([np.linspace(38.0, 38.5, 12), [200.0]])
+    n_bins = bls_plan(periods, durations, 10)[2]
+    assert n_bins[:12].min() == 3810 and n_bins[:12].max() == 3860 and (n_bins[:12] <= 3835).sum() >= 3 and n_bins[12] >= 20000
+    tpl = templates_for(durations, 10)
+    got = host(tls_power(T(t, dev), T(y, dev), periods=periods, durations=durations, templates=tpl))
+    TO.check("switch of paths and 20 010 bins", got, t, y, None, periods, durations, tpl, 10, "likelihood")
+    # each side alone (one kernel per call) gives what the mixed call gave, to the same tolerance
+    for part in (n_bins <= 3835, n_bins > 3835):
+        alone = host(tls_power(T(t, dev), T(y, dev), periods=periods[part], durations=durations, templates=tpl))
+        TO.check("one side of the switch", alone, t, y, None, periods[part], durations, tpl, 10, "likelihood")
+
+
+def small_input():
+    rs = np.random.RandomState(3)
+    t = np.concatenate([np.sort(rs.uniform(0, 4, 150)), np.sort(rs.uniform(9, 13, 150))])
+    y = 2e-3 * rs.randn(300)
+    y[np.abs((t - 0.8 + 0.85) % 1.7 - 0.85) < 0.08] -= 0.02
+    return t, y
+
+
+def test_tls_smallest_shapes(dev):
+    from exoplanet_amd.estimators import bls_plan, tls_power
+
+    t, y = small_input()
+    periods = np.array([0.9, 1.7, 3.4, 6.0, 12.5])
+    # N = 300 with a gap, oversample 5, m = 5 and 8: at 12.5 d most windows hold no cadence
+    durations = (0.1, 0.16)
+    assert list(bls_plan(periods, durations, 5)[1]) == [5, 8]
+    tpl = templates_for(durations, 5)
+    for objective in ("likelihood", "snr"):
+        got = host(tls_power(T(t, dev), T(y, dev), periods=periods, durations=durations, templates=tpl, oversample=5, objective=objective))
+        TO.check(f"N = 300 with a gap, {objective}", got, t, y, None, periods, durations, tpl, 5, objective)
+    # m_k = 1: a template of one bin
+    for g in ([[1.0]], [[0.8]]):
+        got = host(tls_power(T(t, dev), T(y, dev), periods=periods, durations=[0.1], templates=g, oversample=1))
+        TO.check(f"m = 1, g = {g[0][0]}", got, t, y, None, periods, [0.1], g, 1, "likelihood")
+    # K = 16, the most a call takes
+    d16 = np.linspace(0.1, 0.4, 16)
+    assert list(bls_plan(periods, d16, 10)[1]) == list(range(10, 41, 2))
+    tpl = templates_for(d16, 10)
+    got = host(tls_power(T(t, dev), T(y, dev), periods=periods, durations=d16, templates=tpl))
+    tol, _ = TO.check("K = 16", got, t, y, None, periods, d16, tpl, 10, "likelihood")
+    # B = 1 keeps its batch axis and is the (N,) call
+    one = tls_power(T(t, dev), T(y[None], dev), periods=periods, durations=d16, templates=tpl)
+    assert one["power"].shape == (1, 5) and one["period"].shape == (5,)
+    assert O.rel_diff(host(one, 0)["power"], got["power"]) <= tol
+    TO.check("B = 1", host(one, 0), t, y, None, periods, d16, tpl, 10, "likelihood")
+    # one cadence: no window leaves weight outside itself
+    got = host(tls_power(T([3.0], dev), T([1.0], dev), periods=[1.0, 2.5], durations=[0.1], templates=[np.ones(10)]))
+    assert np.all(got["power"] == -np.inf) and all(np.all(np.isnan(got[k])) for k in O.FIELDS[1:])
+    # argument errors that need a device to get that far
+    d = T(t, dev)
+    with pytest.raises(ValueError, match=r"\(7,\)"):
+        tls_power(d, T(y, dev), periods=periods, durations=[0.1], templates=[np.ones(7)])
+    with pytest.raises(ValueError, match="got 2"):
+        tls_power(d, T(y, dev), periods=periods, durations=[0.1], templates=[np.ones(10), np.ones(10)])
+    with pytest.raises(ValueError, match="shape"):
+        tls_power(d, T(y[:-1], dev), periods=periods, durations=[0.1])
+
+
+def test_all_ones_templates_are_the_box_search(dev):
+    """g = 1 with the "snr" objective: period, power, depth, depth_err, depth_snr, duration and transit_time are
+    bls_power(objective="snr")'s -- seven of the eight keys; log_likelihood is exact here (depth_snr^2 / 2) and astropy's
+    approximation there, smaller by w_out / W.  The tolerance is the rule's, from the units of both oracles."""
+    from exoplanet_amd.estimators import bls_power, tls_power
+
+    t, y, _, periods, ones, (want, keep, unit_tls) = main_case("snr", False, ones=True)
+    box_want = O.bls_power(t, y, None, periods, DURATIONS, OVERSAMPLE, "snr")
+    box_exact = O.bls_power(t, y, None, periods, DURATIONS, OVERSAMPLE, "snr", dtype=np.longdouble)
+    same = (box_want["duration"] == want["duration"]) & (np.abs(box_want["transit_time"] - want["transit_time"]) < 1e-9)
+    unit = max([unit_tls] + [O.rel_diff(box_want[k][same], box_exact[k][same]) for k in ("power", "depth", "depth_err", "depth_snr")])
+    tol = max(TO.FACTOR * unit, TO.FLOOR)
+    tls = host(tls_power(T(t, dev), T(y, dev), periods=periods, durations=DURATIONS, templates=ones, objective="snr"))
+    box = host(bls_power(T(t, dev), T(y, dev), periods=periods, durations=DURATIONS, objective="snr"))
+    err = max(O.rel_diff(tls[k], box[k]) for k in ("power", "depth", "depth_err", "depth_snr"))
+    print(f"[g = 1, snr] the two oracles pick the same window on {int(same.sum())} of {len(periods)} periods; unit {unit:.2e}, "
+          f"tolerance {tol:.2e}, tls_power against bls_power {err:.2e}")
+    assert same.all() and np.array_equal(tls["period"], box["period"])
+    assert np.array_equal(tls["duration"], box["duration"]) and np.array_equal(tls["transit_time"], box["transit_time"])
+    assert err <= tol
+    assert O.rel_diff(tls["log_likelihood"], 0.5 * box["depth_snr"] ** 2) <= tol and np.all(tls["log_likelihood"] < box["log_likelihood"])
+
+
+def test_the_template_recovers_the_mid_transit_depth(dev):
+    """the science: at the true period the limb-darkened template gives a higher power than the box and the mid-transit depth;
+    the box's mean deficit is low.  The bounds are the issue's; the oracle gives ratio 1.12, +0.5 % and -21 %."""
+    from exoplanet_amd.estimators import tls_power
+
+    t, y, _, _, tpl, _ = main_case("likelihood", False)
+    ones = [np.ones(len(g)) for g in tpl]
+    kw = dict(periods=[2.345], durations=DURATIONS)
+    shaped, flat = host(tls_power(T(t, dev), T(y, dev), templates=tpl, **kw)), host(tls_power(T(t, dev), T(y, dev), templates=ones, **kw))
+    want = TO.tls_power(t, y, None, [2.345], DURATIONS, tpl, OVERSAMPLE)
+    want1 = TO.tls_power(t, y, None, [2.345], DURATIONS, ones, OVERSAMPLE)
+    print(f"[science] true depth {TRUE_DEPTH}; template: power {shaped['power'][0]:.3f}, depth {shaped['depth'][0]:.6f} "
+          f"({shaped['depth'][0] / TRUE_DEPTH - 1:+.2%}); all ones: power {flat['power'][0]:.3f}, depth {flat['depth'][0]:.6f} "
+          f"({flat['depth'][0] / TRUE_DEPTH - 1:+.2%}); ratio {shaped['power'][0] / flat['power'][0]:.3f}; oracle ratio "
+          f"{want['power'][0] / want1['power'][0]:.3f}, {want['depth'][0] / TRUE_DEPTH - 1:+.2%}, {want1['depth'][0] / TRUE_DEPTH - 1:+.2%}")
+    assert TO.true_depth() == pytest.approx(TRUE_DEPTH, rel=1e-6)
+    assert shaped["power"][0] > flat["power"][0]
+    assert abs(shaped["depth"][0] / TRUE_DEPTH - 1) < 0.02
+    assert flat["depth"][0] < 0.85 * TRUE_DEPTH
+    assert shaped["duration"][0] == pytest.approx(0.2) and abs(shaped["transit_time"][0] - (1.0 - t.min()) % 2.345 - t.min()) < 0.02
+
+
+@pytest.mark.parametrize("m", [1, 10, 40])
+@pytest.mark.parametrize("b", [0.0, 0.3, 0.9])
+def test_transit_template_against_the_numpy_port(dev, m, b):
+    """The kernel's solution vector is held to 5e-15 absolute of its fixture (tests/test_gpu_golden.py) and the numpy port is
+    the fixture's other side, so each deficit, a sum of three such entries times |c| <= 0.6 minus 1, carries at most ~1e-14; the
+    template N / D with N, D the deficits at z and at b then differs by at most (1 + g) 1e-14 / D, g <= 1.2."""
+    from exoplanet_amd.estimators import transit_template
+
+    got = transit_template(m, ror=0.1, b=b)
+    want = TO.transit_template(m, 0.1, b)
+    tol = 2.2e-14 / float(TO.lc_deficit(b, 0.1)[0])
+    err = float(np.max(np.abs(got - want)))
+    print(f"[transit_template m = {m}, b = {b}] error {err:.2e}, tolerance {tol:.2e}; g from {got.min():.4f} to {got.max():.4f}")
+    assert isinstance(got, np.ndarray) and got.shape == (m,) and err <= tol
+    assert np.all(got > 0) and np.allclose(got, got[::-1], rtol=0, atol=tol)   # (symmetric about mid-transit)
+    if m % 2:
+        assert got[m // 2] == pytest.approx(1.0, abs=tol)                 # the bin centre at mid-transit
+    again = transit_template(m, ror=0.1, b=b)
+    assert np.array_equal(again, got) and again is not got                # remembered, and the caller's copy is its own
+
+
+def test_tls_captured_in_a_graph(dev):
+    """host templates and grids are cached on the device by content: a repeated call enqueues kernels only"""
+    from exoplanet_amd.estimators import tls_power
+
+    t, y = TO.main_input(n=2000)
+    periods = np.concatenate([TO.main_periods()[:200:4], [2.345, 45.0]])      # (45 d: 4510 bins, the slab path as well)
+    tpl = templates_for(DURATIONS, OVERSAMPLE)
+    td, yd = T(t, dev), T(y, dev)
+    kw = dict(periods=periods, durations=DURATIONS, ror=TO.TRUE["ror"], b=TO.TRUE["b"])     # templates=None: built, then remembered
+    eager = tls_power(td, yd, **kw)
+    torch.cuda.synchronize()
+    side = torch.cuda.Stream(device=dev)
+    side.wait_stream(torch.cuda.current_stream(dev))
+    with torch.cuda.stream(side):                                      # (torch wants a warm-up on the capturing stream)
+        tls_power(td, yd, **kw)
+    torch.cuda.current_stream(dev).wait_stream(side)
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        res = tls_power(td, yd, **kw)
+    for _ in range(3):
+        graph.replay()
+    torch.cuda.synchronize()
+    tol, _ = TO.check("graph replay", host(res), t, y, None, periods, DURATIONS, tpl, OVERSAMPLE, "likelihood")
+    diff = O.rel_diff(res["power"].cpu().numpy(), eager["power"].cpu().numpy())
+    print(f"[graph replay] against the eager call: {diff:.2e}")
+    assert diff <= tol
+    yd.copy_(T(y[::-1].copy(), dev))                                    # new data in the captured input, same graph
+    graph.replay()
+    torch.cuda.synchronize()
+    TO.check("graph replay, new data", host(res), t, y[::-1], None, periods, DURATIONS, tpl, OVERSAMPLE, "likelihood")
+
+
+def test_tls_estimator(dev):
+    from exoplanet_amd.estimators import tls_estimator
+
+    t, y = TO.main_input()
+    found = tls_estimator(t, y, duration=0.2, b=TO.TRUE["b"])
+    pg, info = found["tls"], found["peak_info"]
+    print(f"[tls_estimator] {len(pg['period'])} periods, peak at {found['peaks'][0]['period']:.5f}, sde {info['sde']:.1f}, depth "
+          f"{info['depth']:.6f}, ror {info['ror']:.4f}")
+    assert len(pg["period"]) <= len(t) and set(pg) == set(O.FIELDS) | {"period", "sr", "sde_spectrum", "objective"}
+    assert abs(found["peaks"][0]["period"] - 2.345) < 1e-3
+    assert info["sde"] > 0 and abs(info["ror"] / 0.1 - 1) < 0.03
+    assert set(info) == set(O.FIELDS) | {"period", "sde", "ror"} and all(type(v) is float for v in info.values())
+    assert abs((info["transit_time"] - 1.0 + 0.5 * 2.345) % 2.345 - 0.5 * 2.345) < 0.02
+    finite = np.isfinite(pg["power"])
+    assert np.nanmax(pg["sr"]) == 1.0 and np.all(pg["sr"][finite] > 0) and info["sde"] == pytest.approx(np.nanmax(pg["sde_spectrum"]))
+    # device tensors in, error bars, the full grid, the other objective
+    full = tls_estimator(T(t, dev), T(y, dev), yerr=2e-3, frequency_factor=1.0, objective="snr", b=TO.TRUE["b"])
+    assert len(full["tls"]["period"]) > len(t) and abs(full["peaks"][0]["period"] - 2.345) < 1e-3
+    assert abs(full["peak_info"]["ror"] / 0.1 - 1) < 0.03
