@@ -144,6 +144,12 @@ _SIGNATURES = {
                                          ctypes.c_double, _i32, _i32, _c_dp, _c_dp, _c_dp, _c_dp, _i64, _c_dp]),
     # t, y, yerr, n_yerr, n, n_series, frequencies, n_frequency, power, workspace, workspace_bytes, stream
     "exo_lomb_scargle_power_f64": (ctypes.c_int, [_c_dp, _c_dp, _c_dp, _i64, _i64, _i64, _c_dp, _i64, _c_dp, _c_dp, _i64, _c_dp]),
+    # t, n, half_window, break_tolerance, edge_cutoff, lo, hi, edge, widest, stream
+    "exo_location_windows_f64": (ctypes.c_int, [_c_dp, _i64, ctypes.c_double, ctypes.c_double, ctypes.c_double, _c_dp, _c_dp,
+                                                _c_dp, _c_dp, _c_dp]),
+    # y, exclude, n_exclude, n, n_series, lo, hi, edge, max_window, method, cval, n_iter, trend, scale, stream
+    "exo_running_location_f64": (ctypes.c_int, [_c_dp, _c_dp, _i64, _i64, _i64, _c_dp, _c_dp, _c_dp, _i32, _i32, ctypes.c_double,
+                                                _i32, _c_dp, _c_dp, _c_dp]),
     "exo_radial_velocity_fwd_f64": (ctypes.c_int, [_c_dp, _i64, _c_dp, _i64, _i32, _c_dp, _c_dp]),
     "exo_radial_velocity_vjp_f64": (ctypes.c_int, [_c_dp, _i64, _c_dp, _i64, _i32, _c_dp, _c_dp, _c_dp]),
     # t, tau, inst, rv, var, n_cad, n_var, params, n_draw, n_planet, trend, n_trend, offset, jit2, n_inst, loglike, gparams,

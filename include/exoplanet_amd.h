@@ -53,7 +53,8 @@ extern "C" {
  *     exo_white_noise_terms_f64, exo_white_noise_workspace_bytes; a slightly larger exo_transit_flux_workspace_bytes.
  * 19: the radial-velocity likelihood -- exo_rv_loglike_vjp_f64, EXO_RV_MAX_TREND, EXO_RV_MAX_INST.
  * 20: the solve -- exo_celerite_solve_work_doubles, exo_celerite_solve_f64.
- * 21: the astrometric likelihood -- exo_astrometry_loglike_vjp_f64. */
+ * 21: the astrometric likelihood -- exo_astrometry_loglike_vjp_f64.  (Entry points added since, no new number because no
+ *     caller breaks: exo_tls_power_f64; exo_location_windows_f64, exo_running_location_f64, EXO_LOCATION_*.) */
 #define EXO_ABI_VERSION 21
 int32_t exo_abi_version(void);
 
@@ -999,6 +1000,42 @@ int exo_tls_power_f64(const double* t, const double* y, const double* yerr, int6
                       const double* periods, int64_t n_period, int64_t min_bins, int64_t max_bins, const int32_t* duration_bins,
                       int32_t n_duration, double delta, int32_t oversample, int32_t objective, const double* templates,
                       const int32_t* template_offsets, double* out, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------
+ * Detrending before the search (exoplanet_amd/estimators.py: location_plan, running_location, flatten, sde; definition:
+ * DESIGN.md section 19): the running median, median absolute deviation and Tukey biweight location of n_series series
+ * y[n_series][n] over time windows on one axis t[n], finite and non-decreasing (the caller's promise).  Kernels only, on
+ * the caller's stream; no atomics: results are bitwise reproducible, and a row of a batch is bitwise the single call.
+ *
+ * exo_location_windows_f64 -- the windows.  Cadence i opens a new segment when t[i] - t[i-1] > break_tolerance (> 0;
+ * INFINITY: one segment).  lo[i], hi[i]: the first and the last cadence j of i's segment with t[j] >= t[i] - half_window and
+ * t[j] <= t[i] + half_window, each bound ONE fp64 operation; edge[i] = 1 where t[i] is closer than edge_cutoff to its segment's
+ * first or last time (t[i] - t_first < edge_cutoff or t_last - t[i] < edge_cutoff), else 0; *widest = max(hi - lo + 1), one
+ * device int32.  EXO_ERR_INVALID_ARGUMENT, before any launch: a null pointer, n < 1, half_window negative or NaN,
+ * break_tolerance not > 0, edge_cutoff negative or NaN.
+ *
+ * exo_running_location_f64 -- the filter.  exclude: n_exclude = 0 (none), 1 (one row for every series) or n_series rows of n
+ * bytes, non-zero: the cadence is left out of every window (it still gets a value).  lo, hi: from the call above; edge:
+ * from it, or NULL (no cadence is cut).  max_window: at least the widest window, the `widest` of the call above read back by
+ * the caller; the workgroup's LDS is sized by it, 8 (256 + 2 max_window - 2) bytes, which bounds it by
+ * EXO_LOCATION_MAX_WINDOW = 8192 cadences (a 1 d window at 20 s cadence is 4320; 133 104 of the 163 840 bytes of a CU).  A cadence
+ * whose window is wider than max_window gets NaN, never a wrong value (and so may cadences of its 256-cadence tile: their
+ * shared span is cut to the size promised); no index leaves [0, n) or the staged span whatever lo and hi hold.
+ * trend[n_series][n]: method EXO_LOCATION_MEDIAN: the median of the window's participating values (the mean of the two
+ * middle ones for an even count); EXO_LOCATION_BIWEIGHT: exactly n_iter steps of the biweight location with tuning constant
+ * cval from the median, scaled by the MAD (the median where the MAD is 0).  scale[n_series][n], or NULL: the MAD, unscaled.
+ * No participating value, or edge[i]: NaN in both.  EXO_ERR_INVALID_ARGUMENT, before any launch: a null y, lo, hi or trend,
+ * n < 1, n_series < 1, cval <= 0 (or NaN), n_iter < 0, an unknown method, max_window outside [1, EXO_LOCATION_MAX_WINDOW],
+ * n_exclude other than 0, 1 or n_series, or rows promised and a null exclude.  (Added without a new ABI number: no caller
+ * breaks.) */
+#define EXO_LOCATION_MEDIAN 0
+#define EXO_LOCATION_BIWEIGHT 1
+#define EXO_LOCATION_MAX_WINDOW 8192
+int exo_location_windows_f64(const double* t, int64_t n, double half_window, double break_tolerance, double edge_cutoff,
+                             int32_t* lo, int32_t* hi, uint8_t* edge, int32_t* widest, void* stream);
+int exo_running_location_f64(const double* y, const uint8_t* exclude, int64_t n_exclude, int64_t n, int64_t n_series,
+                             const int32_t* lo, const int32_t* hi, const uint8_t* edge, int32_t max_window, int32_t method,
+                             double cval, int32_t n_iter, double* trend, double* scale, void* stream);
 
 /* ---------------------------------------------------------------------------
  * Priors and constrained parameters (exoplanet_amd/distributions.py; definitions and measurements: DESIGN.md section 10).
