@@ -150,6 +150,14 @@ _SIGNATURES = {
     # y, exclude, n_exclude, n, n_series, lo, hi, edge, max_window, method, cval, n_iter, trend, scale, stream
     "exo_running_location_f64": (ctypes.c_int, [_c_dp, _c_dp, _i64, _i64, _i64, _c_dp, _c_dp, _c_dp, _i32, _i32, ctypes.c_double,
                                                 _i32, _c_dp, _c_dp, _c_dp]),
+    # t, n, epochs, n_transit, period, t0, window, linear_time, lo, hi, widest, stream
+    "exo_timing_windows_f64": (ctypes.c_int, [_c_dp, _i64, _c_dp, _i64, ctypes.c_double, ctypes.c_double, ctypes.c_double, _c_dp,
+                                              _c_dp, _c_dp, _c_dp, _c_dp]),
+    # t, y, ivar, n_ivar, n, n_series, linear_time, lo, hi, n_transit, max_window, duration, max_shift, n_shift, window, tmpl,
+    # n_template, depth, n_depth, min_in_transit, out, iout, curve, stream
+    "exo_transit_timing_f64": (ctypes.c_int, [_c_dp, _c_dp, _c_dp, _i64, _i64, _i64, _c_dp, _c_dp, _c_dp, _i64, _i32,
+                                              ctypes.c_double, ctypes.c_double, _i32, ctypes.c_double, _c_dp, _i32, _c_dp, _i64,
+                                              _i32, _c_dp, _c_dp, _c_dp, _c_dp]),
     "exo_radial_velocity_fwd_f64": (ctypes.c_int, [_c_dp, _i64, _c_dp, _i64, _i32, _c_dp, _c_dp]),
     "exo_radial_velocity_vjp_f64": (ctypes.c_int, [_c_dp, _i64, _c_dp, _i64, _i32, _c_dp, _c_dp, _c_dp]),
     # t, tau, inst, rv, var, n_cad, n_var, params, n_draw, n_planet, trend, n_trend, offset, jit2, n_inst, loglike, gparams,

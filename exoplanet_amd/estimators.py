@@ -7,12 +7,17 @@ the reference).  Before the search comes the detrending (csrc/exo_detrend.hip, D
 median, MAD or biweight location, divided out of the series, since real photometry is not flat (not in the reference either;
 wotan's biweight and lightkurve's ``flatten`` are the CPU counterparts).
 
+After the search come the transits one by one (csrc/exo_timing.hip): the same template slid over a
+grid of shifts of every single transit's mid-time, which gives the times a ``TTVOrbit`` starts from and the per-transit depths
+behind the odd/even test (not in the reference).
+
 Low level (device tensors in and out, float64): :func:`bls_power`, :func:`tls_power` (its templates:
-:func:`transit_template`), :func:`lomb_scargle_power`, :func:`running_location` (its windows: :func:`location_plan`), and the
+:func:`transit_template`), :func:`lomb_scargle_power`, :func:`running_location` (its windows: :func:`location_plan`),
+:func:`transit_times` (its windows: :func:`timing_plan`), and the
 grids :func:`bls_autoperiod`, :func:`lomb_scargle_autofrequency` (host arithmetic).
 
 High level (numpy arrays or tensors in, numpy out, ``peaks`` hold Python floats): :func:`flatten`, :func:`bls_estimator`,
-:func:`tls_estimator`, :func:`lomb_scargle_estimator`, :func:`autocorr_estimator`, :func:`find_peaks`, :func:`sde`,
+:func:`tls_estimator`, :func:`ttv_estimator`, :func:`lomb_scargle_estimator`, :func:`autocorr_estimator`, :func:`find_peaks`, :func:`sde`,
 :func:`estimate_semi_amplitude`, :func:`estimate_minimum_mass`.  Plain numbers throughout: days, m/s and solar masses in, m/s and
 Jupiter masses out.
 
@@ -21,13 +26,14 @@ sizes and the choice of kernel need them there -- and their device copies are ca
 enqueues kernels only and can be captured into a graph after one eager call.  Given as device tensors they are copied to the
 host once per call, which waits for the stream; that is the only synchronisation in the periodograms.  The detrending has one
 of its own: :func:`location_plan` reads the widest window (the kernel's LDS is sized by it) and whether ``t`` is sorted back to
-the host.  :func:`running_location` given that ``plan`` enqueues kernels only and can be captured.
+the host.  :func:`running_location` given that ``plan`` enqueues kernels only and can be captured.  :func:`timing_plan` and
+:func:`transit_times` divide the per-transit fit the same way.
 
 Run-to-run differences: the box search and the template search sum each phase bin with fp64 atomic adds, whose order is not
 fixed; ``power`` and the other outputs may differ in their last bits between two runs on the same input (and a near-tie
 between two boxes may then resolve differently).  The Lomb-Scargle sums have a fixed order and are bitwise reproducible, and so
-are the running filters (no atomics: selection does no arithmetic, the biweight sums run in the window's order), a row of a
-batch being bitwise what the single call gives.
+are the running filters (no atomics: selection does no arithmetic, the biweight sums run in the window's order) and the
+per-transit fit (sums in the window's order, a fixed-shape reduction), a row of a batch being bitwise what the single call gives.
 """
 import collections
 import ctypes
@@ -40,6 +46,7 @@ from . import _lib
 __all__ = [
     "bls_power", "tls_power", "transit_template", "lomb_scargle_power", "bls_autoperiod", "lomb_scargle_autofrequency",
     "LocationPlan", "location_plan", "running_location", "flatten", "sde",
+    "TimingPlan", "timing_plan", "transit_times", "ttv_estimator",
     "find_peaks", "bls_estimator", "tls_estimator", "lomb_scargle_estimator", "autocorr_function", "autocorr_estimator", "estimate_semi_amplitude", "estimate_minimum_mass",
 ]
 
@@ -444,6 +451,258 @@ def sde(power, window=151):
     r = resid[ok]
     res = torch.where(ok, resid / torch.sqrt(((r - r.mean()) ** 2).mean()), torch.full_like(p, float("nan")))
     return res if as_tensor else _np(res)
+
+
+# ---- the transits one by one: times and depths -----------------------------------------------------------------------------------
+
+MAX_TIMING_WINDOW = 4096     # EXO_TIMING_MAX_WINDOW: cadences in one transit's window
+MAX_TIMING_TEMPLATE = 1024   # EXO_TIMING_MAX_TEMPLATE: bins of the template
+MAX_TIMING_SHIFTS = 4097     # EXO_TIMING_MAX_SHIFTS: trial shifts
+TIMING_FIELDS = ("transit_time", "shift", "time_err", "depth", "depth_err", "log_likelihood", "depth_snr")
+TIMING_COUNTS = ("n_window", "n_in", "valid", "at_edge")
+
+
+class TimingPlan:
+    """The transits of a linear ephemeris on one time axis, from :func:`timing_plan`: ``transit_ind`` (host int64, (K,): the
+    epoch numbers ``n_k``) and its device copy ``epochs``, the device tensors ``linear_time`` (``T_k = t0 + period n_k``), ``lo`` and
+    ``hi`` (int32: transit k's window is the cadences ``lo[k] .. hi[k]``, both included) and ``shifts`` (M,), the widest window
+    ``max_window`` in cadences, a Python int, and the numbers it was made with."""
+
+    __slots__ = ("period", "t0", "duration", "max_shift", "n_shift", "window", "transit_ind", "epochs", "linear_time", "lo", "hi",
+                 "shifts", "max_window", "n", "device")
+
+    def __init__(self, **kw):
+        for k in self.__slots__:
+            setattr(self, k, kw[k])
+
+    def __repr__(self):
+        return (f"TimingPlan(transits={len(self.transit_ind)}, n_shift={self.n_shift}, max_window={self.max_window}, n={self.n}, "
+                f"device={self.device})")
+
+
+def _timing_numbers(period, t0, duration, max_shift, n_shift, window):
+    for name, v in (("period", period), ("t0", t0), ("duration", duration)):
+        if v is None:
+            raise ValueError(f"the per-transit fit needs {name} (or a plan)")
+    period, t0, duration = float(period), float(t0), float(duration)
+    if not period > 0:
+        raise ValueError(f"period must be positive, got {period}")
+    if not np.isfinite(t0):
+        raise ValueError(f"t0 must be finite, got {t0}")
+    if not duration > 0:
+        raise ValueError(f"duration must be positive, got {duration}")
+    max_shift = duration / 2 if max_shift is None else float(max_shift)
+    if not max_shift >= 0:
+        raise ValueError(f"max_shift must be at least 0, got {max_shift}")
+    window = 3 * duration + 2 * max_shift if window is None else float(window)
+    if not window >= duration + 2 * max_shift:
+        raise ValueError(f"window must hold the template at every shift: at least duration + 2 max_shift = {duration + 2 * max_shift}, "
+                         f"got {window}")
+    if int(n_shift) != n_shift or n_shift < 3 or n_shift % 2 == 0:
+        raise ValueError(f"n_shift must be an odd integer >= 3, got {n_shift}")
+    if n_shift > MAX_TIMING_SHIFTS:
+        raise ValueError(f"n_shift = {n_shift}: more than the {MAX_TIMING_SHIFTS} shifts a call takes (EXO_TIMING_MAX_SHIFTS)")
+    return period, t0, duration, max_shift, int(n_shift), window
+
+
+def timing_plan(t, period, t0, duration, max_shift=None, n_shift=201, window=None, check_sorted=True):
+    """The transits of the linear ephemeris ``t0 + period n`` on the device time axis ``t`` (N,), finite and non-decreasing, and
+    their windows for :func:`transit_times`: every integer ``n`` with ``t0 + period n`` inside ``[t[0] - window / 2, t[-1] +
+    window / 2]``, and for each the cadences with ``|t_i - T_k| <= window / 2``.  ``duration``: first to fourth contact, as in
+    :func:`transit_template`.  The ``n_shift`` (odd) trial shifts of a mid-time run from ``-max_shift`` to ``max_shift`` (default
+    ``duration / 2``); ``window`` defaults to ``3 duration + 2 max_shift``, one duration of baseline beyond the furthest position of
+    the template on each side.  Returns a :class:`TimingPlan`; no epoch in range gives one without transits.
+
+    This is the one synchronisation of the per-transit fit: ``t[0]`` and ``t[-1]``, the widest window (the kernel's LDS is sized
+    by it) and, with ``check_sorted``, whether ``t`` is sorted and finite are read back.  ValueError: an unsorted ``t``, or a
+    window of more than ``MAX_TIMING_WINDOW`` cadences."""
+    if not isinstance(t, torch.Tensor):
+        raise ValueError("t must be a torch.Tensor on a ROCm device")
+    if not t.is_cuda:
+        raise ValueError(f"t lives on {t.device}: the estimators run HIP kernels on a ROCm device; there is no CPU fallback")
+    if t.ndim != 1 or t.numel() < 1:
+        raise ValueError(f"t must have shape (N,), got {tuple(t.shape)}")
+    period, t0, duration, max_shift, n_shift, window = _timing_numbers(period, t0, duration, max_shift, n_shift, window)
+    t = t.to(torch.float64).contiguous()
+    n = t.numel()
+    first, last = (float(v) for v in torch.stack([t[0], t[-1]]).cpu())
+    if not (np.isfinite(first) and np.isfinite(last)):
+        raise ValueError("t must be finite and non-decreasing (sort the series first)")
+    a, b = first - window / 2, last + window / 2
+    cand = np.arange(int(np.floor((a - t0) / period)) - 1, int(np.ceil((b - t0) / period)) + 2, dtype=np.int64)
+    T_k = t0 + period * cand.astype(np.float64)
+    transit_ind = cand[(T_k >= a) & (T_k <= b)]
+    K = transit_ind.size
+    h = 2.0 * max_shift / (n_shift - 1)
+    _, shifts = _grid(-max_shift + np.arange(n_shift, dtype=np.float64) * h, "shifts", t.device)
+    epochs = torch.as_tensor(transit_ind, device=t.device)
+    linear_time = torch.empty(K, dtype=torch.float64, device=t.device)
+    lo = torch.empty(K, dtype=torch.int32, device=t.device)
+    hi = torch.empty(K, dtype=torch.int32, device=t.device)
+    info = torch.zeros(2, dtype=torch.int32, device=t.device)
+    if K:
+        lib = _lib.load()
+        _lib.check(lib.exo_timing_windows_f64(t.data_ptr(), n, epochs.data_ptr(), K, period, t0, window, linear_time.data_ptr(),
+                                              lo.data_ptr(), hi.data_ptr(), info.data_ptr(), _stream(t)), "exo_timing_windows_f64")
+    if check_sorted:
+        info[1] = (~(t[1:] >= t[:-1])).sum() + (~torch.isfinite(t)).sum()
+    widest, unsorted = (int(v) for v in info.cpu())
+    if unsorted:
+        raise ValueError("t must be finite and non-decreasing (sort the series first)")
+    if widest > MAX_TIMING_WINDOW:
+        raise ValueError(f"the widest window holds {widest} cadences, more than the {MAX_TIMING_WINDOW} a window may hold "
+                         "(EXO_TIMING_MAX_WINDOW): shorten window or bin the series")
+    return TimingPlan(period=period, t0=t0, duration=duration, max_shift=max_shift, n_shift=n_shift, window=window,
+                      transit_ind=transit_ind, epochs=epochs, linear_time=linear_time, lo=lo, hi=hi, shifts=shifts,
+                      max_window=max(widest, 1), n=n, device=t.device)
+
+
+def transit_times(t, y, yerr=None, *, period=None, t0=None, duration=None, max_shift=None, n_shift=201, window=None, template=None,
+                  ror=0.1, b=0.0, u=(0.4804, 0.1867), n_template=256, depth=None, min_in_transit=3, exclude=None, return_curve=False,
+                  plan=None):
+    """The mid-time and the depth of every single transit of ``y`` (N,) or (B, N) at times ``t`` (N,), finite and non-decreasing,
+    around the linear ephemeris ``t0 + period n`` (definition: DESIGN.md section 20).  Device tensors in and out.
+
+    In the window of transit k (see :func:`timing_plan` for ``duration``, ``max_shift``, ``n_shift`` and ``window``) the template
+    -- ``template``, a finite array of at most ``MAX_TIMING_TEMPLATE`` samples at the bin centres of :func:`transit_template`, or
+    None: ``transit_template(n_template, ror, b, u)`` -- is made continuous by linear interpolation and placed at every trial
+    shift; the level and the depth of ``c - depth g`` are fitted by weighted least squares (weights ``1 / yerr^2``; ``yerr``: None, a
+    scalar, (N,) or (B, N); ``exclude``: bool, (N,) or (B, N), cadences of weight 0, another planet's transits for instance), and
+    ``log_likelihood`` is half the drop in chi-squared against a constant.  ``depth`` (a number or (B,)) holds the depth at that
+    value instead; ``depth_err`` is then NaN.  A shift needs ``min_in_transit`` weighted cadences inside the template and one
+    outside.  The highest shift is refined by the parabola through it and its neighbours, whose curvature is ``time_err``
+    (a change of chi-squared by 1); a maximum at an end of the grid, beside a shift without a fit, or without curvature has
+    ``at_edge`` set, ``shift`` the grid's and ``time_err`` NaN.
+
+    Returns a :class:`BLSResult` of (K,) or (B, K) device tensors: ``transit_time`` (``linear_time + shift``), ``shift``, ``time_err``,
+    ``depth``, ``depth_err``, ``log_likelihood``, ``depth_snr``, ``n_window`` and ``n_in`` (int32: the cadences of the window, and the
+    weighted ones inside the template at the maximum), ``valid`` and ``at_edge`` (bool); ``transit_ind`` (K,), the epoch numbers
+    ``n_k``, and ``linear_time`` (K,); with ``return_curve`` also ``curve`` (..., K, M), the log likelihood of every shift (``-inf``
+    without a fit), and ``shifts`` (M,).  A transit without any fit is not ``valid`` and holds NaN (``n_in`` 0).
+
+    With ``plan`` (a :class:`TimingPlan` of the same ``t``; ``period`` ... ``window`` are then not read) the call enqueues kernels
+    only and may be captured into a graph, once the template is known (a host template is cached on the device by content).
+    Bitwise reproducible; a row of a batch is bitwise the single call."""
+    t, y, yerr, batched = _device_series(t, y, yerr)
+    B, N = y.shape
+    if int(min_in_transit) != min_in_transit or min_in_transit < 1:
+        raise ValueError(f"min_in_transit must be an integer >= 1, got {min_in_transit}")
+    if exclude is not None:
+        if not isinstance(exclude, torch.Tensor):
+            raise ValueError("exclude must be a torch.Tensor on a ROCm device")
+        if not exclude.is_cuda:
+            raise ValueError(f"exclude lives on {exclude.device}: there is no CPU fallback")
+        if exclude.dtype != torch.bool or tuple(exclude.shape) not in ((N,), (1, N), (B, N)):
+            raise ValueError(f"exclude must be bool of shape (N,) or that of y, got {exclude.dtype} {tuple(exclude.shape)}")
+        exclude = exclude.to(t.device).reshape(-1, N)
+    if depth is not None:
+        if isinstance(depth, torch.Tensor) and depth.ndim > 0:
+            if not depth.is_cuda:
+                raise ValueError(f"depth lives on {depth.device}: there is no CPU fallback")
+            if tuple(depth.shape) not in ((1,), (B,)):
+                raise ValueError(f"depth must be a number or have shape (B,) with B = {B}, got {tuple(depth.shape)}")
+            depth = depth.to(device=t.device, dtype=torch.float64).contiguous()
+        else:
+            depth = torch.full((1,), float(depth), dtype=torch.float64, device=t.device)
+    if template is None:
+        if int(n_template) != n_template or not 1 <= n_template <= MAX_TIMING_TEMPLATE:
+            raise ValueError(f"n_template must be an integer in [1, {MAX_TIMING_TEMPLATE}], got {n_template}")
+        template = transit_template(int(n_template), ror, b, u)
+    g_host, g_dev = _grid(template, "template", t.device)
+    if not 1 <= g_host.size <= MAX_TIMING_TEMPLATE:
+        raise ValueError(f"the template holds {g_host.size} bins: a call takes 1 to {MAX_TIMING_TEMPLATE} (EXO_TIMING_MAX_TEMPLATE)")
+    if not np.all(np.isfinite(g_host)):
+        raise ValueError(f"the template is not finite: {g_host[~np.isfinite(g_host)][:3]}")
+    if plan is None:
+        plan = timing_plan(t, period, t0, duration, max_shift=max_shift, n_shift=n_shift, window=window)
+    elif plan.n != N or plan.device != t.device:
+        raise ValueError(f"plan was made for {plan.n} cadences on {plan.device}, t has {N} on {t.device}")
+    K, M = len(plan.transit_ind), plan.n_shift
+    ivar = None
+    if yerr is not None:
+        ivar = 1.0 / yerr ** 2
+    if exclude is not None:
+        keep = (~exclude).to(torch.float64)
+        ivar = keep if ivar is None else torch.where(exclude, torch.zeros_like(ivar), ivar)
+    if ivar is not None:
+        ivar = ivar.contiguous()
+    out = torch.empty((7, B, K), dtype=torch.float64, device=t.device)
+    iout = torch.empty((4, B, K), dtype=torch.int32, device=t.device)
+    curve = torch.empty((B, K, M), dtype=torch.float64, device=t.device) if return_curve else None
+    if K:
+        lib = _lib.load()
+        _lib.check(lib.exo_transit_timing_f64(t.data_ptr(), y.data_ptr(), 0 if ivar is None else ivar.data_ptr(),
+                                              0 if ivar is None else ivar.shape[0], N, B, plan.linear_time.data_ptr(),
+                                              plan.lo.data_ptr(), plan.hi.data_ptr(), K, plan.max_window, plan.duration, plan.max_shift,
+                                              M, plan.window, g_dev.data_ptr(), g_host.size, 0 if depth is None else depth.data_ptr(),
+                                              0 if depth is None else depth.numel(), int(min_in_transit), out.data_ptr(),
+                                              iout.data_ptr(), 0 if curve is None else curve.data_ptr(), _stream(t)),
+                   "exo_transit_timing_f64")
+    res = BLSResult(transit_ind=plan.epochs, linear_time=plan.linear_time)
+    for i, k in enumerate(TIMING_FIELDS):
+        res[k] = out[i] if batched else out[i, 0]
+    for i, k in enumerate(TIMING_COUNTS):
+        v = iout[i] if i < 2 else iout[i] != 0
+        res[k] = v if batched else v[0]
+    if return_curve:
+        res["curve"] = curve if batched else curve[0]
+        res["shifts"] = plan.shifts
+    return res
+
+
+def ttv_estimator(x, y, yerr=None, period=None, t0=None, duration=None, **kwargs):
+    """Measure the time and the depth of every transit of one light curve around the linear ephemeris of a period search, and
+    from them the two questions asked of a peak: do the times follow a line, and are odd and even transits equally deep?
+    ``x`` sorted, (N,); ``y`` (N,); numpy arrays or tensors in, numpy arrays and Python floats out.  ``period``, ``t0`` and
+    ``duration`` as :func:`bls_estimator` / :func:`tls_estimator` report them; ``kwargs``: those of :func:`transit_times`
+    (``max_shift``, ``n_shift``, ``window``, ``ror``, ``b``, ``u``, ``template``, ``depth``, ``min_in_transit``, ``exclude`` ...).
+
+    Returns ``timing`` (the arrays of :func:`transit_times`) and, over the transits that are valid and not at an edge of the
+    grid: ``transit_times`` and ``transit_time_err``; ``transit_inds``, zero-based and counted from the first of them; ``period``
+    and ``t0`` of the line through the times weighted by ``1 / time_err^2`` (``t0``: the line at index 0; fewer than two
+    transits: the input's); ``ttvs``, observed minus that line; ``ttv_chi2 = sum (ttv / err)^2`` and ``ttv_dof``, the count less 2;
+    ``depth_odd`` and ``depth_even``, the inverse-variance means of the depths over odd and even epoch numbers, and
+    ``odd_even_sigma``, their difference over its error (NaN with a held depth or without transits of both kinds).
+
+    The hand-over to a model with free transit times::
+
+        res = ttv_estimator(x, y, yerr, period=peak["period"], t0=peak["transit_time"], duration=peak["duration"])
+        orbit = TTVOrbit(transit_times=[res["transit_times"]], transit_inds=[res["transit_inds"]], b=..., duration=...)
+    """
+    dev = _device_of(x, y)
+    if kwargs.get("exclude") is not None:
+        kwargs["exclude"] = torch.as_tensor(kwargs["exclude"], dtype=torch.bool, device=dev)
+    if isinstance(kwargs.get("depth"), np.ndarray):
+        kwargs["depth"] = _to(kwargs["depth"], dev)
+    yd = _to(y, dev)
+    if yd.ndim != 1:
+        raise ValueError(f"ttv_estimator takes one series, y of shape (N,), got {tuple(yd.shape)}")
+    ed = _to(yerr, dev)
+    res = transit_times(_to(x, dev), yd, ed if ed is None or ed.ndim else float(ed), period=period, t0=t0, duration=duration,
+                        **kwargs)
+    timing = BLSResult((k, v.cpu().numpy()) for k, v in res.items())
+    use = timing["valid"] & ~timing["at_edge"]
+    n_k = timing["transit_ind"][use]
+    times, err = timing["transit_time"][use], timing["time_err"][use]
+    inds = (n_k - n_k[0]) if n_k.size else n_k
+    period_fit, t0_fit = float(period), float(times[0]) if n_k.size else float(t0)
+    if n_k.size >= 2:
+        wt = 1.0 / err ** 2
+        ibar = (wt * inds).sum() / wt.sum()
+        tbar = (wt * times).sum() / wt.sum()
+        period_fit = float((wt * (inds - ibar) * (times - tbar)).sum() / (wt * (inds - ibar) ** 2).sum())
+        t0_fit = float(tbar - period_fit * ibar)
+    ttvs = times - (t0_fit + period_fit * inds)
+    results = dict(timing=timing, transit_inds=inds.astype(np.int64), transit_times=times, transit_time_err=err, period=period_fit,
+                   t0=t0_fit, ttvs=ttvs, ttv_chi2=float(((ttvs / err) ** 2).sum()), ttv_dof=int(n_k.size) - 2)
+    means = {}
+    for name, odd in (("odd", 1), ("even", 0)):
+        sel = timing["valid"] & (timing["transit_ind"] % 2 == odd) & np.isfinite(timing["depth_err"])
+        wd = 1.0 / timing["depth_err"][sel] ** 2
+        means[name] = ((wd * timing["depth"][sel]).sum() / wd.sum(), 1.0 / wd.sum()) if sel.any() else (float("nan"), float("nan"))
+        results[f"depth_{name}"] = float(means[name][0])
+    results["odd_even_sigma"] = float((means["odd"][0] - means["even"][0]) / np.sqrt(means["odd"][1] + means["even"][1]))
+    return results
 
 
 def _span(t):

@@ -54,7 +54,8 @@ extern "C" {
  * 19: the radial-velocity likelihood -- exo_rv_loglike_vjp_f64, EXO_RV_MAX_TREND, EXO_RV_MAX_INST.
  * 20: the solve -- exo_celerite_solve_work_doubles, exo_celerite_solve_f64.
  * 21: the astrometric likelihood -- exo_astrometry_loglike_vjp_f64.  (Entry points added since, no new number because no
- *     caller breaks: exo_tls_power_f64; exo_location_windows_f64, exo_running_location_f64, EXO_LOCATION_*.) */
+ *     caller breaks: exo_tls_power_f64; exo_location_windows_f64, exo_running_location_f64, EXO_LOCATION_*;
+ *     exo_timing_windows_f64, exo_transit_timing_f64, EXO_TIMING_*.) */
 #define EXO_ABI_VERSION 21
 int32_t exo_abi_version(void);
 
@@ -1036,6 +1037,51 @@ int exo_location_windows_f64(const double* t, int64_t n, double half_window, dou
 int exo_running_location_f64(const double* y, const uint8_t* exclude, int64_t n_exclude, int64_t n, int64_t n_series,
                              const int32_t* lo, const int32_t* hi, const uint8_t* edge, int32_t max_window, int32_t method,
                              double cval, int32_t n_iter, double* trend, double* scale, void* stream);
+
+/* ---------------------------------------------------------------------------
+ * Per-transit times and depths (exoplanet_amd/estimators.py: timing_plan, transit_times, ttv_estimator; definition:
+ * DESIGN.md section 20, restated in numpy by tests/timing_oracle.py): around every transit of a linear ephemeris a template
+ * is slid over a grid of trial shifts of the mid-time; at every shift the level and the depth of "c - depth g" are fitted to
+ * the cadences of the transit's window by weighted least squares, and the maximum of the log-likelihood gain over a
+ * constant is refined by the parabola through its three samples.  Kernels only, on the caller's stream; no atomics, no
+ * workspace: every output is bitwise reproducible, and a row of a batch is bitwise the single call.
+ *
+ * exo_timing_windows_f64 -- the windows, one thread per epoch.  epochs[n_transit]: device int64, the transit numbers n_k.
+ * linear_time[k] <- T_k = t0 + period n_k (one multiplication, one addition).  lo[k], hi[k] <- the first and the last cadence i
+ * of t[n] (finite, non-decreasing: the caller's promise) with -window / 2 <= t_i - T_k <= window / 2, the difference ONE
+ * fp64 operation; a window without a cadence has hi = lo - 1.  *widest <- max(hi - lo + 1), one device int32.
+ * EXO_ERR_INVALID_ARGUMENT, before any launch: a null pointer, n < 1, n_transit < 1, period or window not positive (or NaN),
+ * t0 not finite.
+ *
+ * exo_transit_timing_f64 -- the fit, one workgroup per (transit, series) of y[n_series][n].  ivar: the weights 1 / yerr^2,
+ * n_ivar = 0 (NULL: unit weights), 1 (one row for every series) or n_series rows of n; a weight of 0 takes the cadence out.
+ * linear_time, lo, hi: from the call above; max_window: at least its `widest`, read back by the caller -- the workgroup's
+ * LDS is sized by it, 8 (3 max_window + n_template + n_shift) + 5120 bytes, which gives the three caps below (144 392 of the
+ * 163 840 bytes of a CU with all three reached).  A window wider than max_window gives an invalid transit, never a wrong
+ * value, and no index leaves [0, n) whatever lo and hi hold.  duration: first to fourth contact; the trial shifts are
+ * delta_j = -max_shift + j (2 max_shift / (n_shift - 1)), j = 0 .. n_shift - 1, n_shift odd; window: the one the windows
+ * were made with (it is only checked here).  tmpl[n_template]: the template's samples at the bin centres
+ * (2 q + 1) / n_template - 1, finite; between them it is linear, beyond the outermost linear to 0 at -1 and +1.
+ * depth: n_depth = 0 (NULL: the depth is fitted), 1 or n_series values it is held at.  min_in_transit >= 1.
+ * out[7][n_series][n_transit]: transit_time, shift, time_err, depth, depth_err, log_likelihood, depth_snr;
+ * iout[4][n_series][n_transit] (int32): n_window (hi - lo + 1, whatever the weights), n_in (at the maximum), valid, at_edge;
+ * curve[n_series][n_transit][n_shift] or NULL: the log-likelihood gain of every shift, -inf where (k, j) is not
+ * admissible.  An invalid transit: NaN in out, n_in = 0, at_edge = 0.
+ * EXO_ERR_INVALID_ARGUMENT, before any launch: a null t, y, linear_time, lo, hi, tmpl, out or iout; n < 1, n_series < 1 (or
+ * > 65535), n_transit < 1; n_shift even, < 3 or > EXO_TIMING_MAX_SHIFTS; duration, window not positive (or NaN); max_shift
+ * negative (or NaN); window < duration + 2 max_shift; max_window outside [1, EXO_TIMING_MAX_WINDOW]; n_template outside
+ * [1, EXO_TIMING_MAX_TEMPLATE]; min_in_transit < 1; n_ivar other than 0, 1 or n_series, n_depth likewise, or rows promised
+ * and a null pointer.  (Added without a new ABI number: no caller breaks.) */
+#define EXO_TIMING_MAX_WINDOW 4096
+#define EXO_TIMING_MAX_TEMPLATE 1024
+#define EXO_TIMING_MAX_SHIFTS 4097
+int exo_timing_windows_f64(const double* t, int64_t n, const int64_t* epochs, int64_t n_transit, double period, double t0,
+                           double window, double* linear_time, int32_t* lo, int32_t* hi, int32_t* widest, void* stream);
+int exo_transit_timing_f64(const double* t, const double* y, const double* ivar, int64_t n_ivar, int64_t n, int64_t n_series,
+                           const double* linear_time, const int32_t* lo, const int32_t* hi, int64_t n_transit,
+                           int32_t max_window, double duration, double max_shift, int32_t n_shift, double window,
+                           const double* tmpl, int32_t n_template, const double* depth, int64_t n_depth,
+                           int32_t min_in_transit, double* out, int32_t* iout, double* curve, void* stream);
 
 /* ---------------------------------------------------------------------------
  * Priors and constrained parameters (exoplanet_amd/distributions.py; definitions and measurements: DESIGN.md section 10).
