@@ -14,13 +14,14 @@
 
 #include "../../include/exoplanet_amd.h"
 #include "exo_detrend_core.hpp"
+#include "exo_estimators_launch.hpp"
 
 namespace {
 
 using namespace detrend;
 
 constexpr int kTile = 256;         // cadences (threads) per workgroup of the filter
-constexpr int kPlanThreads = 1024; // the two single-workgroup kernels of the plan
+constexpr int kPlanThreads = 1024; // the segments kernel: one workgroup
 constexpr int kWinThreads = 256;
 constexpr int kMaxWindow = EXO_LOCATION_MAX_WINDOW;
 // the staged span of the widest call: 133 104 bytes of the 160 KiB a workgroup may have
@@ -81,24 +82,6 @@ __global__ __launch_bounds__(kWinThreads) void location_windows_kernel(const dou
   hi[i] = (int32_t)window_hi(t, i, e, above);
 }
 
-// the widest window (one workgroup; a fixed order, no atomics)
-__global__ __launch_bounds__(kPlanThreads) void location_widest_kernel(const int32_t* __restrict__ lo, const int32_t* __restrict__ hi,
-                                                                        int64_t n, int32_t* __restrict__ widest) {
-  __shared__ int32_t part[kPlanThreads];
-  int32_t w = 0;
-  for (int64_t i = threadIdx.x; i < n; i += kPlanThreads) {
-    const int32_t wi = hi[i] - lo[i] + 1;
-    w = wi > w ? wi : w;
-  }
-  part[threadIdx.x] = w;
-  __syncthreads();
-  for (int o = kPlanThreads / 2; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) part[threadIdx.x] = part[threadIdx.x + o] > part[threadIdx.x] ? part[threadIdx.x + o] : part[threadIdx.x];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) *widest = part[0];
-}
-
 // The filter.  grid: (tiles of kTile cadences, series); dynamic LDS: `capacity` doubles.  Every index is checked against
 // [0, n) and against the staged span before it is used: a cadence whose window is wider than max_window, does not hold
 // the cadence's tile-mates' order (lo, hi not from the plan) or does not fit the span gets NaN.
@@ -134,8 +117,6 @@ __global__ __launch_bounds__(kTile) void running_location_kernel(const double* _
   if (scale) scale[b * n + i] = sc;
 }
 
-inline int launch_status() { return hipGetLastError() == hipSuccess ? EXO_OK : EXO_ERR_LAUNCH; }
-
 }  // namespace
 
 extern "C" {
@@ -149,7 +130,7 @@ int exo_location_windows_f64(const double* t, int64_t n, double half_window, dou
   hipLaunchKernelGGL(location_segments_kernel, dim3(1), dim3(kPlanThreads), 0, s, t, n, break_tolerance, lo, hi);
   hipLaunchKernelGGL(location_windows_kernel, dim3((unsigned)((n + kWinThreads - 1) / kWinThreads)), dim3(kWinThreads), 0, s, t, n,
                      half_window, edge_cutoff, lo, hi, edge);
-  hipLaunchKernelGGL(location_widest_kernel, dim3(1), dim3(kPlanThreads), 0, s, (const int32_t*)lo, (const int32_t*)hi, n, widest);
+  hipLaunchKernelGGL(widest_window_kernel<kWidestThreads>, dim3(1), dim3(kWidestThreads), 0, s, (const int32_t*)lo, (const int32_t*)hi, n, widest);
   return launch_status();
 }
 
@@ -162,10 +143,7 @@ int exo_running_location_f64(const double* y, const uint8_t* exclude, int64_t n_
     return EXO_ERR_INVALID_ARGUMENT;
   const int32_t capacity = kTile + 2 * max_window - 2;
   const size_t lds = (size_t)capacity * 8;
-  // (above the 64 KiB a launch may ask for by default; a property of the function, not a stream operation)
-  if (lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(running_location_kernel),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return EXO_ERR_LAUNCH;
+  if (!allow_dynamic_lds(running_location_kernel, lds)) return EXO_ERR_LAUNCH;
   hipLaunchKernelGGL(running_location_kernel, dim3((unsigned)((n + kTile - 1) / kTile), (unsigned)n_series), dim3(kTile), lds,
                      (hipStream_t)stream, y, n_exclude > 0 ? exclude : nullptr, n_exclude > 1 ? n : (int64_t)0, n, lo, hi, edge,
                      max_window, capacity, method, cval, n_iter, trend, scale);

@@ -10,6 +10,7 @@
 #include "../../include/exoplanet_amd.h"
 #include "exo_draw_block.hpp"
 #include "exo_estimators_core.hpp"
+#include "exo_estimators_launch.hpp"
 
 namespace {
 
@@ -172,101 +173,131 @@ __device__ __forceinline__ BlsBest block_best(BlsBest best, double* red_d, int64
   return best;
 }
 
-// One period of one series of the box search: the histogram pass, inclusive prefix sums in place, the search over (duration,
-// start) and the outputs.
-template <bool kGlobal>
-__device__ __forceinline__ void bls_period(double* hy, double* hw, int64_t n_bins, const double* __restrict__ tt,
-                                           const double* __restrict__ w, const double* __restrict__ wy, int64_t n, double p,
-                                           double delta, int oversample, const Durations& dur, int n_dur, double Y, double W,
-                                           double t_min, int objective, double* out, int64_t out_stride, double* red_d,
-                                           int64_t* red_i) {
-  const int tid = threadIdx.x, nt = blockDim.x;
-  bls_histogram<kGlobal>(hy, hw, n_bins, tt, w, wy, n, p, delta, oversample);
-  // inclusive prefix sums: each lane its own stretch, the lanes' totals scanned by lane 0's wave, then the offsets added
-  const int64_t per = (n_bins + nt) / nt, lo = 1 + (int64_t)tid * per, hi = lo + per < n_bins + 1 ? lo + per : n_bins + 1;
-  double ay = 0.0, aw = 0.0;
-  for (int64_t i = lo; i < hi; ++i) {
-    ay += hy[i];
-    aw += hw[i];
-    hy[i] = ay;
-    hw[i] = aw;
-  }
-  double* tot_y = red_d;
-  double* tot_w = red_d + nt;
-  tot_y[tid] = ay;
-  tot_w[tid] = aw;
-  __syncthreads();
-  if (tid == 0) {
-    double cy = 0.0, cw = 0.0;
-    for (int i = 0; i < nt; ++i) {
-      const double y0 = tot_y[i], w0 = tot_w[i];
-      tot_y[i] = cy;
-      tot_w[i] = cw;
-      cy += y0;
-      cw += w0;
+// The two searches: what differs after the shared histogram pass.  Each is passed by value as a kernel argument and says how
+// many doubles of `red_d` a workgroup of `threads` needs, what a lane's best candidate is, and what thread 0 writes at the
+// workgroup's maximiser.  The template search's table is NOT in its struct: as a `const double* __restrict__` kernel
+// parameter of its own (`table`; the box search is handed a null pointer and ignores it) its reads, under an index that is
+// uniform across the wave, stay scalar loads on the slab path too, where the histogram shares the global address space with it.
+
+// The box search: inclusive prefix sums in place, then the search over (duration, start).
+struct BoxSearch {
+  Durations dur;
+  int n_dur;
+  static constexpr int red_doubles(int threads) { return 2 * threads; }  // the lanes' totals of both prefix sums
+
+  __device__ __forceinline__ BlsBest lane_best(double* hy, double* hw, int64_t n_bins, const double*, double Y, double W,
+                                               int objective, double* red_d) const {
+    const int tid = threadIdx.x, nt = blockDim.x;
+    // inclusive prefix sums: each lane its own stretch, the lanes' totals scanned by lane 0's wave, then the offsets added
+    const int64_t per = (n_bins + nt) / nt, lo = 1 + (int64_t)tid * per, hi = lo + per < n_bins + 1 ? lo + per : n_bins + 1;
+    double ay = 0.0, aw = 0.0;
+    for (int64_t i = lo; i < hi; ++i) {
+      ay += hy[i];
+      aw += hw[i];
+      hy[i] = ay;
+      hw[i] = aw;
     }
+    double* tot_y = red_d;
+    double* tot_w = red_d + nt;
+    tot_y[tid] = ay;
+    tot_w[tid] = aw;
+    __syncthreads();
+    if (tid == 0) {
+      double cy = 0.0, cw = 0.0;
+      for (int i = 0; i < nt; ++i) {
+        const double y0 = tot_y[i], w0 = tot_w[i];
+        tot_y[i] = cy;
+        tot_w[i] = cw;
+        cy += y0;
+        cw += w0;
+      }
+    }
+    __syncthreads();
+    const double oy = tot_y[tid], ow = tot_w[tid];
+    for (int64_t i = lo; i < hi; ++i) {
+      hy[i] += oy;
+      hw[i] += ow;
+    }
+    __syncthreads();
+    return bls_search(hy, hw, n_bins, dur.m, n_dur, Y, W, objective, tid, nt);
   }
-  __syncthreads();
-  const double oy = tot_y[tid], ow = tot_w[tid];
-  for (int64_t i = lo; i < hi; ++i) {
-    hy[i] += oy;
-    hw[i] += ow;
+
+  __device__ __forceinline__ void outputs(double* hy, double* hw, int64_t n_bins, const double*, double Y, double W, int objective,
+                                          BlsBest best, double p, double delta, double t_min, double* out, int64_t out_stride) const {
+    bls_outputs(hy, hw, n_bins, dur.m, Y, W, objective, best, p, delta, t_min, out, out_stride);
   }
-  __syncthreads();
-  // every lane its share of the candidates, then the arg-max of the wave and of the workgroup (first maximiser in (k, s) order)
-  const BlsBest best = block_best(bls_search(hy, hw, n_bins, dur.m, n_dur, Y, W, objective, tid, nt), red_d, red_i);
-  if (tid == 0) bls_outputs(hy, hw, n_bins, dur.m, Y, W, objective, best, p, delta, t_min, out, out_stride);
+};
+
+// The template search: the correlation of the histogram itself with every template -- lanes over the
+// starts s, strided by the workgroup, so that neighbouring lanes read neighbouring bins; k outer, j inner.  g: the flat table
+// in global memory, read under an index that is uniform across the wave.
+struct TemplateSearch {
+  Durations dur;
+  Templates tpl;
+  int n_dur;
+  static constexpr int red_doubles(int threads) { return threads / kWave; }  // block_best's alone
+
+  __device__ __forceinline__ BlsBest lane_best(const double* hy, const double* hw, int64_t n_bins, const double* __restrict__ g,
+                                               double Y, double W, int objective, double*) const {
+    return tls_search(hy, hw, n_bins, dur.m, tpl.off, n_dur, g, Y, W, objective, threadIdx.x, blockDim.x);
+  }
+
+  __device__ __forceinline__ void outputs(const double* hy, const double* hw, int64_t n_bins, const double* __restrict__ g, double Y,
+                                          double W, int objective, BlsBest best, double p, double delta, double t_min, double* out,
+                                          int64_t out_stride) const {
+    tls_outputs(hy, hw, n_bins, dur.m, tpl.off, g, Y, W, objective, best, p, delta, t_min, out, out_stride);
+  }
+};
+
+// One period of one series: the histogram pass, every lane its share of the candidates, the arg-max of the wave and of the
+// workgroup (first maximiser in (k, s) order), and the outputs.
+template <class Search, bool kGlobal>
+__device__ __forceinline__ void period(const Search& search, const double* __restrict__ table, double* hy, double* hw,
+                                       int64_t n_bins, const double* __restrict__ tt, const double* __restrict__ w,
+                                       const double* __restrict__ wy, int64_t n, double p, double delta, int oversample, double Y,
+                                       double W, double t_min, int objective, double* out, int64_t out_stride, double* red_d,
+                                       int64_t* red_i) {
+  bls_histogram<kGlobal>(hy, hw, n_bins, tt, w, wy, n, p, delta, oversample);
+  const BlsBest best = block_best(search.lane_best(hy, hw, n_bins, table, Y, W, objective, red_d), red_d, red_i);
+  if (threadIdx.x == 0) search.outputs(hy, hw, n_bins, table, Y, W, objective, best, p, delta, t_min, out, out_stride);
   __syncthreads();
 }
 
-// One period of one series of the template search: the histogram pass, then the correlation of the
-// histogram itself with every template -- lanes over the starts s, strided by the workgroup, so that neighbouring lanes read
-// neighbouring bins; k outer, j inner.  g: the flat table in global memory, read under an index that is uniform across the wave.
-template <bool kGlobal>
-__device__ __forceinline__ void tls_period(double* hy, double* hw, int64_t n_bins, const double* __restrict__ tt,
-                                           const double* __restrict__ w, const double* __restrict__ wy, int64_t n, double p,
-                                           double delta, int oversample, const Durations& dur, const Templates& tpl, int n_dur,
-                                           const double* __restrict__ g, double Y, double W, double t_min, int objective,
-                                           double* out, int64_t out_stride, double* red_d, int64_t* red_i) {
-  const int tid = threadIdx.x, nt = blockDim.x;
-  bls_histogram<kGlobal>(hy, hw, n_bins, tt, w, wy, n, p, delta, oversample);
-  const BlsBest best =
-      block_best(tls_search((const double*)hy, (const double*)hw, n_bins, dur.m, tpl.off, n_dur, g, Y, W, objective, tid, nt),
-                 red_d, red_i);
-  if (tid == 0)
-    tls_outputs((const double*)hy, (const double*)hw, n_bins, dur.m, tpl.off, g, Y, W, objective, best, p, delta, t_min, out,
-                out_stride);
-  __syncthreads();
+// a period whose histogram has no room: NaN in its seven planes
+__device__ __forceinline__ void fill_nan(double* o, int64_t plane) {
+  if (threadIdx.x == 0)
+    for (int i = 0; i < 7; ++i) o[i * plane] = NAN;
 }
 
 // periods whose histogram fits the LDS: workgroup (period, series)
-__global__ __launch_bounds__(kBlsThreads) void bls_lds_kernel(const double* __restrict__ periods, int64_t n_period, Layout L,
-                                                              double delta, int oversample, Durations dur, int n_dur,
-                                                              int objective, int64_t lds_bins,
-                                                              const double* __restrict__ ws, double* __restrict__ out) {
+template <class Search>
+__global__ __launch_bounds__(kBlsThreads) void search_lds_kernel(const double* __restrict__ periods, int64_t n_period, Layout L,
+                                                                 double delta, int oversample, Search search,
+                                                                 const double* __restrict__ table, int objective, int64_t lds_bins,
+                                                                 const double* __restrict__ ws, double* __restrict__ out) {
   extern __shared__ double hist[];
-  __shared__ double red_d[2 * kBlsThreads];
+  __shared__ double red_d[Search::red_doubles(kBlsThreads)];
   __shared__ int64_t red_i[kBlsThreads / kWave];
   const int64_t ip = blockIdx.x, b = blockIdx.y;
   const double p = periods[ip];
   const int64_t n_bins = bls_n_bins(p, delta, oversample);
   if (n_bins > kLdsBins) return;  // the slab kernel's
-  if (n_bins > lds_bins) {        // (more bins than the caller's max_bins announced: nothing is written past the histogram)
-    if (threadIdx.x == 0)
-      for (int i = 0; i < 7; ++i) out[(i * L.n_series + b) * n_period + ip] = NAN;
+  double* o = out + b * n_period + ip;
+  if (n_bins > lds_bins) {  // (more bins than the caller's max_bins announced: nothing is written past the histogram)
+    fill_nan(o, L.n_series * n_period);
     return;
   }
-  bls_period<false>(hist, hist + n_bins + 1, n_bins, ws + L.tt(), ws + L.w(b), ws + L.wy(b), L.n, p, delta, oversample, dur,
-                    n_dur, ws[2 + 2 * b], ws[3 + 2 * b], ws[0], objective, out + b * n_period + ip, L.n_series * n_period, red_d,
-                    red_i);
+  period<Search, false>(search, table, hist, hist + n_bins + 1, n_bins, ws + L.tt(), ws + L.w(b), ws + L.wy(b), L.n, p, delta, oversample,
+                        ws[2 + 2 * b], ws[3 + 2 * b], ws[0], objective, o, L.n_series * n_period, red_d, red_i);
 }
 
 // the others: the histogram in a slab of the workspace, one slab per workgroup, the workgroups walking the (period, series) pairs
-__global__ __launch_bounds__(kSlabThreads) void bls_slab_kernel(const double* __restrict__ periods, int64_t n_period, Layout L,
-                                                                double delta, int oversample, Durations dur, int n_dur,
-                                                                int objective, int64_t max_bins, double* __restrict__ ws,
-                                                                double* __restrict__ out) {
-  __shared__ double red_d[2 * kSlabThreads];
+template <class Search>
+__global__ __launch_bounds__(kSlabThreads) void search_slab_kernel(const double* __restrict__ periods, int64_t n_period, Layout L,
+                                                                   double delta, int oversample, Search search,
+                                                                   const double* __restrict__ table, int objective, int64_t max_bins,
+                                                                   double* __restrict__ ws, double* __restrict__ out) {
+  __shared__ double red_d[Search::red_doubles(kSlabThreads)];
   __shared__ int64_t red_i[kSlabThreads / kWave];
   double* slab = ws + L.slabs() + (int64_t)blockIdx.x * 2 * (max_bins + 1);
   for (int64_t item = blockIdx.x; item < n_period * L.n_series; item += gridDim.x) {
@@ -276,59 +307,11 @@ __global__ __launch_bounds__(kSlabThreads) void bls_slab_kernel(const double* __
     if (n_bins <= kLdsBins) continue;
     double* o = out + b * n_period + ip;
     if (n_bins > max_bins) {  // (the host sized the slabs from these very periods: not reached)
-      if (threadIdx.x == 0)
-        for (int i = 0; i < 7; ++i) o[i * L.n_series * n_period] = NAN;
+      fill_nan(o, L.n_series * n_period);
       continue;
     }
-    bls_period<true>(slab, slab + n_bins + 1, n_bins, ws + L.tt(), ws + L.w(b), ws + L.wy(b), L.n, p, delta, oversample, dur,
-                     n_dur, ws[2 + 2 * b], ws[3 + 2 * b], ws[0], objective, o, L.n_series * n_period, red_d, red_i);
-  }
-}
-
-// the template search's pair: the geometry, the switch on n_bins and the fences of the box search's kernels
-__global__ __launch_bounds__(kBlsThreads) void tls_lds_kernel(const double* __restrict__ periods, int64_t n_period, Layout L,
-                                                              double delta, int oversample, Durations dur, Templates tpl,
-                                                              int n_dur, const double* __restrict__ g, int objective,
-                                                              int64_t lds_bins, const double* __restrict__ ws,
-                                                              double* __restrict__ out) {
-  extern __shared__ double hist[];
-  __shared__ double red_d[kBlsThreads / kWave];
-  __shared__ int64_t red_i[kBlsThreads / kWave];
-  const int64_t ip = blockIdx.x, b = blockIdx.y;
-  const double p = periods[ip];
-  const int64_t n_bins = bls_n_bins(p, delta, oversample);
-  if (n_bins > kLdsBins) return;  // the slab kernel's
-  if (n_bins > lds_bins) {        // (more bins than the caller's max_bins announced: nothing is written past the histogram)
-    if (threadIdx.x == 0)
-      for (int i = 0; i < 7; ++i) out[(i * L.n_series + b) * n_period + ip] = NAN;
-    return;
-  }
-  tls_period<false>(hist, hist + n_bins + 1, n_bins, ws + L.tt(), ws + L.w(b), ws + L.wy(b), L.n, p, delta, oversample, dur, tpl,
-                    n_dur, g, ws[2 + 2 * b], ws[3 + 2 * b], ws[0], objective, out + b * n_period + ip, L.n_series * n_period,
-                    red_d, red_i);
-}
-
-__global__ __launch_bounds__(kSlabThreads) void tls_slab_kernel(const double* __restrict__ periods, int64_t n_period, Layout L,
-                                                                double delta, int oversample, Durations dur, Templates tpl,
-                                                                int n_dur, const double* __restrict__ g, int objective,
-                                                                int64_t max_bins, double* __restrict__ ws,
-                                                                double* __restrict__ out) {
-  __shared__ double red_d[kSlabThreads / kWave];
-  __shared__ int64_t red_i[kSlabThreads / kWave];
-  double* slab = ws + L.slabs() + (int64_t)blockIdx.x * 2 * (max_bins + 1);
-  for (int64_t item = blockIdx.x; item < n_period * L.n_series; item += gridDim.x) {
-    const int64_t ip = item % n_period, b = item / n_period;
-    const double p = periods[ip];
-    const int64_t n_bins = bls_n_bins(p, delta, oversample);
-    if (n_bins <= kLdsBins) continue;
-    double* o = out + b * n_period + ip;
-    if (n_bins > max_bins) {  // (the host sized the slabs from these very periods: not reached)
-      if (threadIdx.x == 0)
-        for (int i = 0; i < 7; ++i) o[i * L.n_series * n_period] = NAN;
-      continue;
-    }
-    tls_period<true>(slab, slab + n_bins + 1, n_bins, ws + L.tt(), ws + L.w(b), ws + L.wy(b), L.n, p, delta, oversample, dur, tpl,
-                     n_dur, g, ws[2 + 2 * b], ws[3 + 2 * b], ws[0], objective, o, L.n_series * n_period, red_d, red_i);
+    period<Search, true>(search, table, slab, slab + n_bins + 1, n_bins, ws + L.tt(), ws + L.w(b), ws + L.wy(b), L.n, p, delta, oversample,
+                         ws[2 + 2 * b], ws[3 + 2 * b], ws[0], objective, o, L.n_series * n_period, red_d, red_i);
   }
 }
 
@@ -377,8 +360,6 @@ __global__ __launch_bounds__(kLsThreads) void lomb_scargle_kernel(const double* 
   }
 }
 
-inline int launch_status() { return hipGetLastError() == hipSuccess ? EXO_OK : EXO_ERR_LAUNCH; }
-
 inline bool series_ok(int64_t n, int64_t n_series, int64_t n_yerr) {
   return n >= 1 && n <= INT32_MAX && n_series >= 1 && n_series <= 65535 && (n_yerr == 0 || n_yerr == 1 || n_yerr == n_series);
 }
@@ -402,6 +383,57 @@ inline void prepare(const double* t, const double* y, const double* yerr, int64_
                      stride, ws);
 }
 
+// the arguments that exo_bls_power_f64 and exo_tls_power_f64 share
+struct SearchCall {
+  const double *t, *y, *yerr;
+  int64_t n_yerr, n, n_series;
+  const double* periods;
+  int64_t n_period, min_bins, max_bins;
+  const int32_t* duration_bins;
+  int32_t n_duration;
+  double delta;
+  int32_t oversample, objective;
+  double* out;
+  void* workspace;
+  int64_t workspace_bytes;
+  void* stream;
+};
+
+inline bool search_args_ok(const SearchCall& c) {
+  return series_ok(c.n, c.n_series, c.n_yerr) && c.n_period >= 0 && c.n_period <= INT32_MAX && c.t && c.y &&
+         (c.n_yerr <= 0 || c.yerr) && c.periods && c.duration_bins && c.n_duration >= 1 && c.n_duration <= kMaxDur &&
+         c.delta > 0.0 && c.oversample >= 1 && (c.objective == EXO_BLS_LIKELIHOOD || c.objective == EXO_BLS_SNR) &&
+         c.min_bins >= 1 && c.max_bins >= c.min_bins && c.out && c.workspace;
+}
+
+// the durations into `search`, the workspace, the columns, and the search's kernel pair over the periods (table: the template
+// search's, else null)
+template <class Search>
+inline int launch_search(Search search, const double* table, const SearchCall& c) {
+  search.dur = Durations{};
+  search.n_dur = (int)c.n_duration;
+  for (int k = 0; k < c.n_duration; ++k) {
+    if (c.duration_bins[k] < 1) return EXO_ERR_INVALID_ARGUMENT;
+    search.dur.m[k] = c.duration_bins[k];
+  }
+  if (c.workspace_bytes < exo_bls_workspace_bytes(c.n, c.n_series, c.n_period, c.max_bins)) return EXO_ERR_WORKSPACE;
+  const Layout L = layout(c.n, c.n_series, c.n_yerr);
+  double* ws = (double*)c.workspace;
+  hipStream_t s = (hipStream_t)c.stream;
+  prepare(c.t, c.y, c.n_yerr > 0 ? c.yerr : nullptr, c.n_yerr, L, 0, ws, s);
+  // which kernel a period takes depends on its bin count alone (bls_n_bins, the same division on both sides)
+  if (c.min_bins <= kLdsBins) {
+    const int64_t bins = c.max_bins < kLdsBins ? c.max_bins : kLdsBins;
+    hipLaunchKernelGGL(search_lds_kernel<Search>, dim3((unsigned)c.n_period, (unsigned)c.n_series), dim3(kBlsThreads),
+                       (size_t)(16 * (bins + 1)), s, c.periods, c.n_period, L, c.delta, (int)c.oversample, search, table,
+                       (int)c.objective, bins, (const double*)ws, c.out);
+  }
+  if (c.max_bins > kLdsBins)
+    hipLaunchKernelGGL(search_slab_kernel<Search>, dim3((unsigned)n_slabs(c.n_series, c.n_period, c.max_bins)), dim3(kSlabThreads), 0,
+                       s, c.periods, c.n_period, L, c.delta, (int)c.oversample, search, table, (int)c.objective, c.max_bins, ws, c.out);
+  return launch_status();
+}
+
 }  // namespace
 
 extern "C" {
@@ -417,71 +449,30 @@ int exo_bls_power_f64(const double* t, const double* y, const double* yerr, int6
                       const double* periods, int64_t n_period, int64_t min_bins, int64_t max_bins, const int32_t* duration_bins,
                       int32_t n_duration, double delta, int32_t oversample, int32_t objective, double* out, void* workspace,
                       int64_t workspace_bytes, void* stream) {
+  const SearchCall c{t, y, yerr, n_yerr, n, n_series, periods, n_period, min_bins, max_bins, duration_bins, n_duration, delta,
+                     oversample, objective, out, workspace, workspace_bytes, stream};
   if (n_period == 0) return EXO_OK;
-  if (!series_ok(n, n_series, n_yerr) || n_period < 0 || n_period > INT32_MAX || !t || !y || (n_yerr > 0 && !yerr) ||
-      !periods || !duration_bins || n_duration < 1 || n_duration > kMaxDur || !(delta > 0.0) || oversample < 1 ||
-      (objective != EXO_BLS_LIKELIHOOD && objective != EXO_BLS_SNR) || min_bins < 1 || max_bins < min_bins || !out || !workspace)
-    return EXO_ERR_INVALID_ARGUMENT;
-  Durations dur{};
-  for (int k = 0; k < n_duration; ++k) {
-    if (duration_bins[k] < 1) return EXO_ERR_INVALID_ARGUMENT;
-    dur.m[k] = duration_bins[k];
-  }
-  if (workspace_bytes < exo_bls_workspace_bytes(n, n_series, n_period, max_bins)) return EXO_ERR_WORKSPACE;
-  const Layout L = layout(n, n_series, n_yerr);
-  double* ws = (double*)workspace;
-  hipStream_t s = (hipStream_t)stream;
-  prepare(t, y, n_yerr > 0 ? yerr : nullptr, n_yerr, L, 0, ws, s);
-  // which kernel a period takes depends on its bin count alone (bls_n_bins, the same division on both sides)
-  if (min_bins <= kLdsBins) {
-    const int64_t bins = max_bins < kLdsBins ? max_bins : kLdsBins;
-    hipLaunchKernelGGL(bls_lds_kernel, dim3((unsigned)n_period, (unsigned)n_series), dim3(kBlsThreads),
-                       (size_t)(16 * (bins + 1)), s, periods, n_period, L, delta, (int)oversample, dur, (int)n_duration,
-                       (int)objective, bins, (const double*)ws, out);
-  }
-  if (max_bins > kLdsBins)
-    hipLaunchKernelGGL(bls_slab_kernel, dim3((unsigned)n_slabs(n_series, n_period, max_bins)), dim3(kSlabThreads), 0, s, periods,
-                       n_period, L, delta, (int)oversample, dur, (int)n_duration, (int)objective, max_bins, ws, out);
-  return launch_status();
+  if (!search_args_ok(c)) return EXO_ERR_INVALID_ARGUMENT;
+  return launch_search(BoxSearch{}, nullptr, c);
 }
 
 int exo_tls_power_f64(const double* t, const double* y, const double* yerr, int64_t n_yerr, int64_t n, int64_t n_series,
                       const double* periods, int64_t n_period, int64_t min_bins, int64_t max_bins, const int32_t* duration_bins,
                       int32_t n_duration, double delta, int32_t oversample, int32_t objective, const double* templates,
                       const int32_t* template_offsets, double* out, void* workspace, int64_t workspace_bytes, void* stream) {
+  const SearchCall c{t, y, yerr, n_yerr, n, n_series, periods, n_period, min_bins, max_bins, duration_bins, n_duration, delta,
+                     oversample, objective, out, workspace, workspace_bytes, stream};
   if (n_period == 0) return EXO_OK;
-  if (!series_ok(n, n_series, n_yerr) || n_period < 0 || n_period > INT32_MAX || !t || !y || (n_yerr > 0 && !yerr) ||
-      !periods || !duration_bins || n_duration < 1 || n_duration > kMaxDur || !(delta > 0.0) || oversample < 1 ||
-      (objective != EXO_BLS_LIKELIHOOD && objective != EXO_BLS_SNR) || min_bins < 1 || max_bins < min_bins || !templates ||
-      !template_offsets || !out || !workspace)
-    return EXO_ERR_INVALID_ARGUMENT;
-  Durations dur{};
-  Templates tpl{};
-  if (template_offsets[0] < 0) return EXO_ERR_INVALID_ARGUMENT;
-  tpl.off[0] = template_offsets[0];
+  if (!search_args_ok(c) || !templates || !template_offsets || template_offsets[0] < 0) return EXO_ERR_INVALID_ARGUMENT;
+  TemplateSearch search{};
+  search.tpl.off[0] = template_offsets[0];
   for (int k = 0; k < n_duration; ++k) {
-    // (in int64: an offset near INT32_MAX must not wrap into a match)
-    if (duration_bins[k] < 1 || (int64_t)template_offsets[k] + duration_bins[k] != template_offsets[k + 1] ||
-        template_offsets[k + 1] > EXO_TLS_MAX_TEMPLATE)
+    // template k holds duration_bins[k] entries (in int64: an offset near INT32_MAX must not wrap into a match)
+    if ((int64_t)template_offsets[k] + duration_bins[k] != template_offsets[k + 1] || template_offsets[k + 1] > EXO_TLS_MAX_TEMPLATE)
       return EXO_ERR_INVALID_ARGUMENT;
-    dur.m[k] = duration_bins[k];
-    tpl.off[k + 1] = template_offsets[k + 1];
+    search.tpl.off[k + 1] = template_offsets[k + 1];
   }
-  if (workspace_bytes < exo_bls_workspace_bytes(n, n_series, n_period, max_bins)) return EXO_ERR_WORKSPACE;
-  const Layout L = layout(n, n_series, n_yerr);
-  double* ws = (double*)workspace;
-  hipStream_t s = (hipStream_t)stream;
-  prepare(t, y, n_yerr > 0 ? yerr : nullptr, n_yerr, L, 0, ws, s);
-  if (min_bins <= kLdsBins) {
-    const int64_t bins = max_bins < kLdsBins ? max_bins : kLdsBins;
-    hipLaunchKernelGGL(tls_lds_kernel, dim3((unsigned)n_period, (unsigned)n_series), dim3(kBlsThreads),
-                       (size_t)(16 * (bins + 1)), s, periods, n_period, L, delta, (int)oversample, dur, tpl, (int)n_duration,
-                       templates, (int)objective, bins, (const double*)ws, out);
-  }
-  if (max_bins > kLdsBins)
-    hipLaunchKernelGGL(tls_slab_kernel, dim3((unsigned)n_slabs(n_series, n_period, max_bins)), dim3(kSlabThreads), 0, s, periods,
-                       n_period, L, delta, (int)oversample, dur, tpl, (int)n_duration, templates, (int)objective, max_bins, ws, out);
-  return launch_status();
+  return launch_search(search, templates, c);
 }
 
 int exo_lomb_scargle_power_f64(const double* t, const double* y, const double* yerr, int64_t n_yerr, int64_t n, int64_t n_series,

@@ -100,25 +100,34 @@ EXO_EST_HD BlsBest bls_search(Ptr cy, Ptr cw, int64_t n_bins, const int32_t* m, 
   return best;
 }
 
-// the seven outputs at the maximiser (out[i * stride]: power, depth, depth_err, depth_snr, log_likelihood, duration,
-// transit_time); no admissible box: power = -inf, the rest NaN
-template <class Ptr>
-EXO_EST_HD void bls_outputs(Ptr cy, Ptr cw, int64_t n_bins, const int32_t* m, double Y, double W, int objective, BlsBest best,
-                            double p, double delta, double t_min, double* out, int64_t stride) {
-  if (best.key == INT64_MAX) {
+// The seven outputs of one period, for both searches (out[i * stride]: power, depth, depth_err, depth_snr, log_likelihood,
+// duration, transit_time): the fit at the maximiser, the objective's value there, and the maximiser itself -- mk bins wide
+// from bin s.  Not `found` (no admissible box or window): power = -inf, the rest NaN, and nothing else is read.
+EXO_EST_HD void search_outputs(bool found, double depth, double depth_err, double depth_snr, double log_likelihood, double power,
+                               int64_t mk, int64_t s, double p, double delta, double t_min, double* out, int64_t stride) {
+  if (!found) {
     out[0] = -INFINITY;
     for (int i = 1; i < 7; ++i) out[i * stride] = NAN;
     return;
   }
-  const int64_t k = best.key / (n_bins + 1), s = best.key % (n_bins + 1), mk = m[k];
-  const BlsBox b = bls_box(cy[s + mk] - cy[s], cw[s + mk] - cw[s], Y, W);
-  out[0] = bls_objective(b, objective);
-  out[1 * stride] = b.depth;
-  out[2 * stride] = b.depth_err;
-  out[3 * stride] = b.depth_snr;
-  out[4 * stride] = b.log_likelihood;
+  out[0] = power;
+  out[1 * stride] = depth;
+  out[2 * stride] = depth_err;
+  out[3 * stride] = depth_snr;
+  out[4 * stride] = log_likelihood;
   out[5 * stride] = (double)mk * delta;
   out[6 * stride] = fmod((double)s * delta + 0.5 * (double)mk * delta + t_min, p);
+}
+
+// the box search's outputs: its box at the maximiser is taken from the prefix sums again
+template <class Ptr>
+EXO_EST_HD void bls_outputs(Ptr cy, Ptr cw, int64_t n_bins, const int32_t* m, double Y, double W, int objective, BlsBest best,
+                            double p, double delta, double t_min, double* out, int64_t stride) {
+  const bool found = best.key != INT64_MAX;
+  const int64_t k = best.key / (n_bins + 1), s = best.key % (n_bins + 1), mk = found ? m[k] : 0;
+  const BlsBox b = found ? bls_box(cy[s + mk] - cy[s], cw[s + mk] - cw[s], Y, W) : BlsBox{};
+  search_outputs(found, b.depth, b.depth_err, b.depth_snr, b.log_likelihood, bls_objective(b, objective), mk, s, p, delta, t_min,
+                 out, stride);
 }
 
 // ---- transit least squares: a template in place of the box -----------------------------------------------
@@ -181,20 +190,11 @@ EXO_EST_HD BlsBest tls_search(Ptr hy, Ptr hw, int64_t n_bins, const int32_t* m, 
 template <class Ptr, class GPtr>
 EXO_EST_HD void tls_outputs(Ptr hy, Ptr hw, int64_t n_bins, const int32_t* m, const int32_t* off, GPtr g, double Y, double W,
                             int objective, BlsBest best, double p, double delta, double t_min, double* out, int64_t stride) {
-  if (best.key == INT64_MAX) {
-    out[0] = -INFINITY;
-    for (int i = 1; i < 7; ++i) out[i * stride] = NAN;
-    return;
-  }
-  const int64_t k = best.key / (n_bins + 1), s = best.key % (n_bins + 1), mk = m[k];
-  const TlsWindow w = tls_window(hy, hw, g + off[k], s, mk, Y, W);
-  out[0] = tls_objective(w, objective);
-  out[1 * stride] = w.depth;
-  out[2 * stride] = w.depth_err;
-  out[3 * stride] = w.depth_snr;
-  out[4 * stride] = w.log_likelihood;
-  out[5 * stride] = (double)mk * delta;
-  out[6 * stride] = fmod((double)s * delta + 0.5 * (double)mk * delta + t_min, p);
+  const bool found = best.key != INT64_MAX;
+  const int64_t k = best.key / (n_bins + 1), s = best.key % (n_bins + 1), mk = found ? m[k] : 0;
+  const TlsWindow w = found ? tls_window(hy, hw, g + off[k], s, mk, Y, W) : TlsWindow{};
+  search_outputs(found, w.depth, w.depth_err, w.depth_snr, w.log_likelihood, tls_objective(w, objective), mk, s, p, delta, t_min,
+                 out, stride);
 }
 
 // ---- Lomb-Scargle -----------------------------------------------------------------------------------------------------------

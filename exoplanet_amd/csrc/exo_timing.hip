@@ -15,6 +15,7 @@
 #include <stdint.h>
 
 #include "../../include/exoplanet_amd.h"
+#include "exo_estimators_launch.hpp"
 #include "exo_timing_core.hpp"
 
 namespace {
@@ -23,7 +24,6 @@ using namespace timing;
 
 constexpr int kThreads = EXO_TIMING_THREADS;
 constexpr int kWinThreads = 256;
-constexpr int kWidestThreads = 1024;
 
 __global__ __launch_bounds__(kWinThreads) void timing_windows_kernel(const double* __restrict__ t, int64_t n,
                                                                       const int64_t* __restrict__ epochs, int64_t n_transit,
@@ -35,24 +35,6 @@ __global__ __launch_bounds__(kWinThreads) void timing_windows_kernel(const doubl
   const double T = t0 + period * (double)epochs[k];
   linear_time[k] = T;
   transit_window(t, n, T, half_window, lo + k, hi + k);
-}
-
-// the widest window (one workgroup; a fixed order, no atomics)
-__global__ __launch_bounds__(kWidestThreads) void timing_widest_kernel(const int32_t* __restrict__ lo, const int32_t* __restrict__ hi,
-                                                                        int64_t n_transit, int32_t* __restrict__ widest) {
-  __shared__ int32_t part[kWidestThreads];
-  int32_t w = 0;
-  for (int64_t k = threadIdx.x; k < n_transit; k += kWidestThreads) {
-    const int32_t wk = hi[k] - lo[k] + 1;
-    w = wk > w ? wk : w;
-  }
-  part[threadIdx.x] = w;
-  __syncthreads();
-  for (int o = kWidestThreads / 2; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) part[threadIdx.x] = part[threadIdx.x + o] > part[threadIdx.x] ? part[threadIdx.x + o] : part[threadIdx.x];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) *widest = part[0];
 }
 
 // The fit.  grid: (transits, series); dynamic LDS: lds_bytes(max_window, m, n_shift).  lo and hi are clamped to [0, n) and the
@@ -185,8 +167,6 @@ __global__ __launch_bounds__(kThreads) void transit_timing_kernel(
   iout[3 * plane + slot] = at_edge;
 }
 
-inline int launch_status() { return hipGetLastError() == hipSuccess ? EXO_OK : EXO_ERR_LAUNCH; }
-
 }  // namespace
 
 extern "C" {
@@ -199,7 +179,7 @@ int exo_timing_windows_f64(const double* t, int64_t n, const int64_t* epochs, in
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(timing_windows_kernel, dim3((unsigned)((n_transit + kWinThreads - 1) / kWinThreads)), dim3(kWinThreads), 0, s, t,
                      n, epochs, n_transit, period, t0, 0.5 * window, linear_time, lo, hi);
-  hipLaunchKernelGGL(timing_widest_kernel, dim3(1), dim3(kWidestThreads), 0, s, (const int32_t*)lo, (const int32_t*)hi, n_transit,
+  hipLaunchKernelGGL(widest_window_kernel<kWidestThreads>, dim3(1), dim3(kWidestThreads), 0, s, (const int32_t*)lo, (const int32_t*)hi, n_transit,
                      widest);
   return launch_status();
 }
@@ -217,10 +197,7 @@ int exo_transit_timing_f64(const double* t, const double* y, const double* ivar,
       (n_depth != 0 && n_depth != 1 && n_depth != n_series) || (n_depth > 0 && !depth))
     return EXO_ERR_INVALID_ARGUMENT;
   const size_t lds = (size_t)lds_bytes(max_window, n_template, n_shift);
-  // (above the 64 KiB a launch may ask for by default; a property of the function, not a stream operation)
-  if (lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(transit_timing_kernel),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return EXO_ERR_LAUNCH;
+  if (!allow_dynamic_lds(transit_timing_kernel, lds)) return EXO_ERR_LAUNCH;
   hipLaunchKernelGGL(transit_timing_kernel, dim3((unsigned)n_transit, (unsigned)n_series), dim3(kThreads), lds, (hipStream_t)stream,
                      t, y, n_ivar > 0 ? ivar : nullptr, n_ivar > 1 ? n : (int64_t)0, n, linear_time, lo, hi, n_transit, max_window,
                      0.5 * duration, max_shift, n_shift, tmpl, n_template, n_depth > 0 ? depth : nullptr,

@@ -64,15 +64,41 @@ class BLSResult(dict):
 
 # ---- arguments ---------------------------------------------------------------------------------------------------------------
 
-def _device_series(t, y, yerr):
-    """-> t (N,), y (B, N), yerr None / (1, N) / (B, N), all contiguous float64 on t's device, and whether y was batched"""
-    for name, x in (("t", t), ("y", y)):
-        if not isinstance(x, torch.Tensor):
-            raise ValueError(f"{name} must be a torch.Tensor on a ROCm device")
-        if not x.is_cuda:
-            raise ValueError(f"{name} lives on {x.device}: the estimators run HIP kernels on a ROCm device; there is no CPU fallback")
+def _np(x):
+    return x.detach().cpu().numpy().astype(np.float64) if isinstance(x, torch.Tensor) else np.asarray(x, dtype=np.float64)
+
+
+def _device_of(*xs):
+    for x in xs:
+        if isinstance(x, torch.Tensor) and x.is_cuda:
+            return x.device
+    if not torch.cuda.is_available():
+        raise ValueError("the estimators run on a ROCm device and none is available; there is no CPU fallback")
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+def _to(x, device):
+    return None if x is None else torch.as_tensor(x, dtype=torch.float64, device=device)
+
+
+def _on_device(name, x):
+    if not isinstance(x, torch.Tensor):
+        raise ValueError(f"{name} must be a torch.Tensor on a ROCm device")
+    if not x.is_cuda:
+        raise ValueError(f"{name} lives on {x.device}: the estimators run HIP kernels on a ROCm device; there is no CPU fallback")
+
+
+def _time_axis(t):
+    """the rule of a time axis: a device tensor of shape (N,), N >= 1"""
+    _on_device("t", t)
     if t.ndim != 1 or t.numel() < 1:
         raise ValueError(f"t must have shape (N,), got {tuple(t.shape)}")
+
+
+def _device_series(t, y, yerr):
+    """-> t (N,), y (B, N), yerr None / (1, N) / (B, N), all contiguous float64 on t's device, and whether y was batched"""
+    _time_axis(t)
+    _on_device("y", y)
     n = t.numel()
     if y.ndim not in (1, 2) or y.shape[-1] != n:
         raise ValueError(f"y must have shape (N,) or (B, N) with N = {n}, got {tuple(y.shape)}")
@@ -125,6 +151,43 @@ def _workspace(nbytes, device):
     return torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=device)
 
 
+def _exclude_rows(exclude, B, N, device):
+    """-> ``exclude`` (bool, (N,), (1, N) or (B, N), on a device) as contiguous rows (1, N) or (B, N).  Contiguous because
+    :func:`running_location` hands the kernel its address; :func:`transit_times` only does torch arithmetic with it, where the
+    call costs nothing."""
+    if not isinstance(exclude, torch.Tensor):
+        raise ValueError("exclude must be a torch.Tensor on a ROCm device")
+    if not exclude.is_cuda:
+        raise ValueError(f"exclude lives on {exclude.device}: there is no CPU fallback")
+    if exclude.dtype != torch.bool or tuple(exclude.shape) not in ((N,), (1, N), (B, N)):
+        raise ValueError(f"exclude must be bool of shape (N,) or that of y, got {exclude.dtype} {tuple(exclude.shape)}")
+    return exclude.to(device).reshape(-1, N).contiguous()
+
+
+def _plan_widest(info, t, check_sorted, cap, cap_name, argument):
+    """The read-back of a plan, its one device-to-host copy: ``info`` (int32, (2,)) holds the widest window, and with
+    ``check_sorted`` receives the count of places where ``t`` is unsorted or not finite.  -> the widest window"""
+    if check_sorted:
+        info[1] = (~(t[1:] >= t[:-1])).sum() + (~torch.isfinite(t)).sum()
+    widest, unsorted = (int(v) for v in info.cpu())
+    if unsorted:
+        raise ValueError("t must be finite and non-decreasing (sort the series first)")
+    if widest > cap:
+        raise ValueError(f"the widest window holds {widest} cadences, more than the {cap} a window may hold "
+                         f"({cap_name}): shorten {argument} or bin the series")
+    return widest
+
+
+def _check_plan(plan, t):
+    if plan.n != t.numel() or plan.device != t.device:
+        raise ValueError(f"plan was made for {plan.n} cadences on {plan.device}, t has {t.numel()} on {t.device}")
+
+
+def _fields(planes, names, batched):
+    """-> the output planes (F, B, ...) by name, without the series axis unless ``batched``"""
+    return {name: plane if batched else plane[0] for name, plane in zip(names, planes)}
+
+
 # ---- the periodograms ----------------------------------------------------------------------------------------------------------
 
 def bls_plan(periods, durations, oversample):
@@ -154,6 +217,12 @@ def bls_power(t, y, yerr=None, *, periods, durations, oversample=10, objective="
     maximum over durations and phases of the objective, the box's log likelihood (``"likelihood"``) or the depth's signal to
     noise (``"snr"``) -- and ``depth, depth_err, depth_snr, log_likelihood, duration, transit_time`` of that box, plus ``period``.
     A period with no admissible box (no weight inside or none outside every box) has ``power = -inf`` and NaN elsewhere."""
+    return _period_search("bls_power", t, y, yerr, periods, durations, oversample, objective)
+
+
+def _period_search(name, t, y, yerr, periods, durations, oversample, objective, extra=lambda m, device: ()):
+    """The body of :func:`bls_power` and :func:`tls_power`, whose entry point is ``exo_<name>_f64``.  ``extra(m, device)``
+    gives what that entry point takes between ``objective`` and ``out``: device tensors and numpy arrays, passed by address."""
     if objective not in _OBJECTIVES:
         raise ValueError(f"unknown objective {objective!r}: 'likelihood' or 'snr'")
     t, y, yerr, batched = _device_series(t, y, yerr)
@@ -162,6 +231,7 @@ def bls_power(t, y, yerr=None, *, periods, durations, oversample=10, objective="
     if d_host.ndim != 1:
         raise ValueError("durations must be one-dimensional")
     delta, m, n_bins = bls_plan(p_host, d_host, oversample)
+    more = extra(m, t.device)
     B, N, P = y.shape[0], y.shape[1], p_host.size
     out = torch.empty((7, B, P), dtype=torch.float64, device=t.device)
     if P:
@@ -169,16 +239,15 @@ def bls_power(t, y, yerr=None, *, periods, durations, oversample=10, objective="
         lo, hi = int(n_bins.min()), int(n_bins.max())
         nbytes = lib.exo_bls_workspace_bytes(N, B, P, hi)
         if nbytes < 0:
-            raise ValueError("bls_power: invalid sizes")
+            raise ValueError(f"{name}: invalid sizes")
         ws = _workspace(nbytes, t.device)
-        _lib.check(lib.exo_bls_power_f64(t.data_ptr(), y.data_ptr(), 0 if yerr is None else yerr.data_ptr(),
-                                         0 if yerr is None else yerr.shape[0], N, B, p_dev.data_ptr(), P, lo, hi,
-                                         m.ctypes.data_as(ctypes.c_void_p), m.size, delta, int(oversample), _OBJECTIVES[objective],
-                                         out.data_ptr(), ws.data_ptr(), ws.numel() * 8, _stream(t)), "exo_bls_power_f64")
-    res = BLSResult(period=p_dev)
-    for i, k in enumerate(BLS_FIELDS):
-        res[k] = out[i] if batched else out[i, 0]
-    return res
+        ptr = lambda x: x.data_ptr() if isinstance(x, torch.Tensor) else x.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
+        entry = f"exo_{name}_f64"
+        _lib.check(getattr(lib, entry)(t.data_ptr(), y.data_ptr(), 0 if yerr is None else yerr.data_ptr(),
+                                       0 if yerr is None else yerr.shape[0], N, B, p_dev.data_ptr(), P, lo, hi, ptr(m), m.size, delta,
+                                       int(oversample), _OBJECTIVES[objective], *(ptr(x) for x in more), out.data_ptr(),
+                                       ws.data_ptr(), ws.numel() * 8, _stream(t)), entry)
+    return BLSResult(period=p_dev, **_fields(out, BLS_FIELDS, batched))
 
 
 _template_cache = collections.OrderedDict()
@@ -255,34 +324,11 @@ def tls_power(t, y, yerr=None, *, periods, durations, templates=None, ror=0.1, b
     template (the mid-transit depth for a template that is 1 there), ``depth_err = 1 / sqrt(D)``, ``log_likelihood`` exactly half
     the drop in chi-squared against a constant.  With all-ones templates the depth, its error and its signal to noise are
     :func:`bls_power`'s.  Host templates are cached on the device by content, as the grids are."""
-    if objective not in _OBJECTIVES:
-        raise ValueError(f"unknown objective {objective!r}: 'likelihood' or 'snr'")
-    t, y, yerr, batched = _device_series(t, y, yerr)
-    p_host, p_dev = _grid(periods, "periods", t.device)
-    d_host = np.atleast_1d(_np(durations))
-    if d_host.ndim != 1:
-        raise ValueError("durations must be one-dimensional")
-    delta, m, n_bins = bls_plan(p_host, d_host, oversample)
-    table, offsets = _template_table(templates, m, ror, b, u)
-    _, g_dev = _grid(table, "templates", t.device)
-    B, N, P = y.shape[0], y.shape[1], p_host.size
-    out = torch.empty((7, B, P), dtype=torch.float64, device=t.device)
-    if P:
-        lib = _lib.load()
-        lo, hi = int(n_bins.min()), int(n_bins.max())
-        nbytes = lib.exo_bls_workspace_bytes(N, B, P, hi)
-        if nbytes < 0:
-            raise ValueError("tls_power: invalid sizes")
-        ws = _workspace(nbytes, t.device)
-        _lib.check(lib.exo_tls_power_f64(t.data_ptr(), y.data_ptr(), 0 if yerr is None else yerr.data_ptr(),
-                                         0 if yerr is None else yerr.shape[0], N, B, p_dev.data_ptr(), P, lo, hi,
-                                         m.ctypes.data_as(ctypes.c_void_p), m.size, delta, int(oversample), _OBJECTIVES[objective],
-                                         g_dev.data_ptr(), offsets.ctypes.data_as(ctypes.c_void_p), out.data_ptr(), ws.data_ptr(),
-                                         ws.numel() * 8, _stream(t)), "exo_tls_power_f64")
-    res = BLSResult(period=p_dev)
-    for i, k in enumerate(BLS_FIELDS):
-        res[k] = out[i] if batched else out[i, 0]
-    return res
+    def table(m, device):
+        flat, offsets = _template_table(templates, m, ror, b, u)
+        return _grid(flat, "templates", device)[1], offsets
+
+    return _period_search("tls_power", t, y, yerr, periods, durations, oversample, objective, extra=table)
 
 
 def lomb_scargle_power(t, y, yerr=None, *, frequencies):
@@ -331,12 +377,7 @@ def location_plan(t, window_length, break_tolerance=None, edge_cutoff=0.0, check
 
     This is the one synchronisation of the detrending functions: the widest window (and, with ``check_sorted``, whether
     ``t`` is sorted and finite) is read back.  ValueError: an unsorted ``t``, or a window wider than ``MAX_WINDOW`` cadences."""
-    if not isinstance(t, torch.Tensor):
-        raise ValueError("t must be a torch.Tensor on a ROCm device")
-    if not t.is_cuda:
-        raise ValueError(f"t lives on {t.device}: the estimators run HIP kernels on a ROCm device; there is no CPU fallback")
-    if t.ndim != 1 or t.numel() < 1:
-        raise ValueError(f"t must have shape (N,), got {tuple(t.shape)}")
+    _time_axis(t)
     window_length, edge_cutoff = float(window_length), float(edge_cutoff)
     if not window_length >= 0:
         raise ValueError(f"window_length must be at least 0, got {window_length}")
@@ -355,15 +396,7 @@ def location_plan(t, window_length, break_tolerance=None, edge_cutoff=0.0, check
                                             float("inf") if break_tolerance is None else float(break_tolerance), edge_cutoff,
                                             lo.data_ptr(), hi.data_ptr(), edge.data_ptr(), info.data_ptr(), _stream(t)),
                "exo_location_windows_f64")
-    if check_sorted:
-        info[1] = (~(t[1:] >= t[:-1])).sum() + (~torch.isfinite(t)).sum()
-    widest, unsorted = (int(v) for v in info.cpu())
-    if unsorted:
-        raise ValueError("t must be finite and non-decreasing (sort the series first)")
-    if widest > MAX_WINDOW:
-        raise ValueError(f"the widest window holds {widest} cadences, more than the {MAX_WINDOW} a window may hold "
-                         "(EXO_LOCATION_MAX_WINDOW): shorten window_length or bin the series")
-    return LocationPlan(lo, hi, edge, widest)
+    return LocationPlan(lo, hi, edge, _plan_widest(info, t, check_sorted, MAX_WINDOW, "EXO_LOCATION_MAX_WINDOW", "window_length"))
 
 
 def running_location(t, y, window_length=None, *, method="biweight", exclude=None, break_tolerance=None, edge_cutoff=0.0, cval=5.0,
@@ -391,19 +424,13 @@ def running_location(t, y, window_length=None, *, method="biweight", exclude=Non
     t, y, _, batched = _device_series(t, y, None)
     B, N = y.shape
     if exclude is not None:
-        if not isinstance(exclude, torch.Tensor):
-            raise ValueError("exclude must be a torch.Tensor on a ROCm device")
-        if not exclude.is_cuda:
-            raise ValueError(f"exclude lives on {exclude.device}: there is no CPU fallback")
-        if exclude.dtype != torch.bool or tuple(exclude.shape) not in ((N,), (1, N), (B, N)):
-            raise ValueError(f"exclude must be bool of shape (N,) or that of y, got {exclude.dtype} {tuple(exclude.shape)}")
-        exclude = exclude.to(t.device).reshape(-1, N).contiguous()
+        exclude = _exclude_rows(exclude, B, N, t.device)
     if plan is None:
         if window_length is None:
             raise ValueError("running_location needs window_length or plan")
         plan = location_plan(t, window_length, break_tolerance=break_tolerance, edge_cutoff=edge_cutoff)
-    elif plan.n != N or plan.device != t.device:
-        raise ValueError(f"plan was made for {plan.n} cadences on {plan.device}, t has {N} on {t.device}")
+    else:
+        _check_plan(plan, t)
     trend = torch.empty((B, N), dtype=torch.float64, device=t.device)
     scale = torch.empty((B, N), dtype=torch.float64, device=t.device) if return_scale else None
     lib = _lib.load()
@@ -516,12 +543,7 @@ def timing_plan(t, period, t0, duration, max_shift=None, n_shift=201, window=Non
     This is the one synchronisation of the per-transit fit: ``t[0]`` and ``t[-1]``, the widest window (the kernel's LDS is sized
     by it) and, with ``check_sorted``, whether ``t`` is sorted and finite are read back.  ValueError: an unsorted ``t``, or a
     window of more than ``MAX_TIMING_WINDOW`` cadences."""
-    if not isinstance(t, torch.Tensor):
-        raise ValueError("t must be a torch.Tensor on a ROCm device")
-    if not t.is_cuda:
-        raise ValueError(f"t lives on {t.device}: the estimators run HIP kernels on a ROCm device; there is no CPU fallback")
-    if t.ndim != 1 or t.numel() < 1:
-        raise ValueError(f"t must have shape (N,), got {tuple(t.shape)}")
+    _time_axis(t)
     period, t0, duration, max_shift, n_shift, window = _timing_numbers(period, t0, duration, max_shift, n_shift, window)
     t = t.to(torch.float64).contiguous()
     n = t.numel()
@@ -544,14 +566,7 @@ def timing_plan(t, period, t0, duration, max_shift=None, n_shift=201, window=Non
         lib = _lib.load()
         _lib.check(lib.exo_timing_windows_f64(t.data_ptr(), n, epochs.data_ptr(), K, period, t0, window, linear_time.data_ptr(),
                                               lo.data_ptr(), hi.data_ptr(), info.data_ptr(), _stream(t)), "exo_timing_windows_f64")
-    if check_sorted:
-        info[1] = (~(t[1:] >= t[:-1])).sum() + (~torch.isfinite(t)).sum()
-    widest, unsorted = (int(v) for v in info.cpu())
-    if unsorted:
-        raise ValueError("t must be finite and non-decreasing (sort the series first)")
-    if widest > MAX_TIMING_WINDOW:
-        raise ValueError(f"the widest window holds {widest} cadences, more than the {MAX_TIMING_WINDOW} a window may hold "
-                         "(EXO_TIMING_MAX_WINDOW): shorten window or bin the series")
+    widest = _plan_widest(info, t, check_sorted, MAX_TIMING_WINDOW, "EXO_TIMING_MAX_WINDOW", "window")
     return TimingPlan(period=period, t0=t0, duration=duration, max_shift=max_shift, n_shift=n_shift, window=window,
                       transit_ind=transit_ind, epochs=epochs, linear_time=linear_time, lo=lo, hi=hi, shifts=shifts,
                       max_window=max(widest, 1), n=n, device=t.device)
@@ -588,13 +603,7 @@ def transit_times(t, y, yerr=None, *, period=None, t0=None, duration=None, max_s
     if int(min_in_transit) != min_in_transit or min_in_transit < 1:
         raise ValueError(f"min_in_transit must be an integer >= 1, got {min_in_transit}")
     if exclude is not None:
-        if not isinstance(exclude, torch.Tensor):
-            raise ValueError("exclude must be a torch.Tensor on a ROCm device")
-        if not exclude.is_cuda:
-            raise ValueError(f"exclude lives on {exclude.device}: there is no CPU fallback")
-        if exclude.dtype != torch.bool or tuple(exclude.shape) not in ((N,), (1, N), (B, N)):
-            raise ValueError(f"exclude must be bool of shape (N,) or that of y, got {exclude.dtype} {tuple(exclude.shape)}")
-        exclude = exclude.to(t.device).reshape(-1, N)
+        exclude = _exclude_rows(exclude, B, N, t.device)
     if depth is not None:
         if isinstance(depth, torch.Tensor) and depth.ndim > 0:
             if not depth.is_cuda:
@@ -615,8 +624,8 @@ def transit_times(t, y, yerr=None, *, period=None, t0=None, duration=None, max_s
         raise ValueError(f"the template is not finite: {g_host[~np.isfinite(g_host)][:3]}")
     if plan is None:
         plan = timing_plan(t, period, t0, duration, max_shift=max_shift, n_shift=n_shift, window=window)
-    elif plan.n != N or plan.device != t.device:
-        raise ValueError(f"plan was made for {plan.n} cadences on {plan.device}, t has {N} on {t.device}")
+    else:
+        _check_plan(plan, t)
     K, M = len(plan.transit_ind), plan.n_shift
     ivar = None
     if yerr is not None:
@@ -638,15 +647,10 @@ def transit_times(t, y, yerr=None, *, period=None, t0=None, duration=None, max_s
                                               0 if depth is None else depth.numel(), int(min_in_transit), out.data_ptr(),
                                               iout.data_ptr(), 0 if curve is None else curve.data_ptr(), _stream(t)),
                    "exo_transit_timing_f64")
-    res = BLSResult(transit_ind=plan.epochs, linear_time=plan.linear_time)
-    for i, k in enumerate(TIMING_FIELDS):
-        res[k] = out[i] if batched else out[i, 0]
-    for i, k in enumerate(TIMING_COUNTS):
-        v = iout[i] if i < 2 else iout[i] != 0
-        res[k] = v if batched else v[0]
+    res = BLSResult(transit_ind=plan.epochs, linear_time=plan.linear_time, **_fields(out, TIMING_FIELDS, batched))
+    res.update(_fields((iout[0], iout[1], iout[2] != 0, iout[3] != 0), TIMING_COUNTS, batched))
     if return_curve:
-        res["curve"] = curve if batched else curve[0]
-        res["shifts"] = plan.shifts
+        res.update(_fields((curve,), ("curve",), batched), shifts=plan.shifts)
     return res
 
 
@@ -752,23 +756,6 @@ def lomb_scargle_autofrequency(t, samples_per_peak=5, nyquist_factor=5, minimum_
 
 # ---- the reference's estimators -------------------------------------------------------------------------------------------------
 
-def _np(x):
-    return x.detach().cpu().numpy().astype(np.float64) if isinstance(x, torch.Tensor) else np.asarray(x, dtype=np.float64)
-
-
-def _device_of(*xs):
-    for x in xs:
-        if isinstance(x, torch.Tensor) and x.is_cuda:
-            return x.device
-    if not torch.cuda.is_available():
-        raise ValueError("the estimators run on a ROCm device and none is available; there is no CPU fallback")
-    return torch.device("cuda", torch.cuda.current_device())
-
-
-def _to(x, device):
-    return None if x is None else torch.as_tensor(x, dtype=torch.float64, device=device)
-
-
 def find_peaks(freq, power, max_peaks=0):
     """Local maxima of a periodogram, highest first, each refined by the parabola through the three ``log(power)`` samples
     around it.  ``max_peaks = 0``: the highest peak as a dictionary ``index, log_power, period, period_uncert`` (ValueError if
@@ -805,6 +792,27 @@ def _estimator_periods(xc, durations, min_period, max_period, minimum_n_transit,
     return periods
 
 
+def _estimator_front(x, y, yerr, duration, min_period, max_period, minimum_n_transit, frequency_factor):
+    """What the two transit estimators do before the search.  -> ``x_ref``, the middle of the times; the times about it, the
+    series less its median and ``yerr`` as device tensors; and ``periods`` and ``durations``, the search's grid"""
+    dev = _device_of(x, y)
+    xh = _np(x)
+    x_ref = 0.5 * (xh.min() + xh.max())
+    durations = np.atleast_1d(np.asarray(duration, dtype=np.float64))
+    periods = _estimator_periods(xh - x_ref, durations, min_period, max_period, minimum_n_transit, frequency_factor)
+    yd = _to(y, dev)
+    return x_ref, _to(xh - x_ref, dev), yd - torch.median(yd), _to(yerr, dev), dict(periods=periods, durations=durations)
+
+
+def _estimator_back(res, x_ref, objective, **spectra):
+    """... and after it.  -> the periodogram as numpy arrays, its transit times on the input's axis again, with ``spectra`` and
+    ``objective`` added; and its peaks (at most one)"""
+    pg = BLSResult((k, _np(v)) for k, v in res.items())
+    pg["transit_time"] = pg["transit_time"] + x_ref
+    pg.update(spectra, objective=objective)
+    return pg, find_peaks(1.0 / pg["period"], pg["power"], max_peaks=1)
+
+
 def bls_estimator(x, y, yerr=None, duration=0.2, min_period=None, max_period=None, objective=None, method=None, oversample=10,
                   frequency_factor=None, minimum_n_transit=3):
     """Estimate the period of a transit signal by box least squares.  Returns ``bls`` (the periodogram: numpy arrays under the
@@ -812,18 +820,10 @@ def bls_estimator(x, y, yerr=None, duration=0.2, min_period=None, max_period=Non
 
     ``frequency_factor=None`` thins the grid as the reference does (doubled until there are no more periods than cadences), so
     that results compare; ``frequency_factor=1.0`` searches the full grid.  ``method`` is accepted and ignored."""
-    dev = _device_of(x, y)
-    xh = _np(x)
-    x_ref = 0.5 * (xh.min() + xh.max())
-    durations = np.atleast_1d(np.asarray(duration, dtype=np.float64))
-    periods = _estimator_periods(xh - x_ref, durations, min_period, max_period, minimum_n_transit, frequency_factor)
-    yd = _to(y, dev)
-    res = bls_power(_to(xh - x_ref, dev), yd - torch.median(yd), _to(yerr, dev), periods=periods, durations=durations,
-                    oversample=oversample, objective="likelihood" if objective is None else objective)
-    pg = BLSResult((k, _np(v)) for k, v in res.items())
-    pg["transit_time"] = pg["transit_time"] + x_ref
-    pg["objective"] = "likelihood" if objective is None else objective
-    peaks = find_peaks(1.0 / pg["period"], pg["power"], max_peaks=1)
+    objective = "likelihood" if objective is None else objective
+    x_ref, td, yd, ed, grid = _estimator_front(x, y, yerr, duration, min_period, max_period, minimum_n_transit, frequency_factor)
+    res = bls_power(td, yd, ed, oversample=oversample, objective=objective, **grid)
+    pg, peaks = _estimator_back(res, x_ref, objective)
     results = dict(bls=pg, peaks=peaks, peak_info=None)
     if peaks:
         ind = peaks[0]["index"]
@@ -844,16 +844,9 @@ def tls_estimator(x, y, yerr=None, duration=0.2, min_period=None, max_period=Non
     starting value for ``r`` (NaN for a brightening)."""
     from .light_curves.limb_dark import LimbDarkLightCurve
 
-    dev = _device_of(x, y)
-    xh = _np(x)
-    x_ref = 0.5 * (xh.min() + xh.max())
-    durations = np.atleast_1d(np.asarray(duration, dtype=np.float64))
-    periods = _estimator_periods(xh - x_ref, durations, min_period, max_period, minimum_n_transit, frequency_factor)
     objective = "likelihood" if objective is None else objective
-    yd, ed = _to(y, dev), _to(yerr, dev)
-    yd = yd - torch.median(yd)
-    res = tls_power(_to(xh - x_ref, dev), yd, ed, periods=periods, durations=durations, ror=ror, b=b, u=u, oversample=oversample,
-                    objective=objective)
+    x_ref, td, yd, ed, grid = _estimator_front(x, y, yerr, duration, min_period, max_period, minimum_n_transit, frequency_factor)
+    res = tls_power(td, yd, ed, ror=ror, b=b, u=u, oversample=oversample, objective=objective, **grid)
     # the signal residue and its detection efficiency, over the periods with a fit
     w = torch.ones_like(yd) if ed is None else 1.0 / ed.expand_as(yd) ** 2
     chi2_0 = (w * (yd - (w * yd).sum() / w.sum()) ** 2).sum()
@@ -862,11 +855,7 @@ def tls_estimator(x, y, yerr=None, duration=0.2, min_period=None, max_period=Non
     nan = torch.full_like(chi2, float("nan"))
     sr = torch.where(ok, chi2[ok].min() / chi2, nan) if bool(ok.any()) else nan
     mean, std = sr[ok].mean(), sr[ok].std()
-    pg = BLSResult((k, _np(v)) for k, v in res.items())
-    pg["transit_time"] = pg["transit_time"] + x_ref
-    pg["sr"], pg["sde_spectrum"] = _np(sr), _np((sr - mean) / std)
-    pg["objective"] = objective
-    peaks = find_peaks(1.0 / pg["period"], pg["power"], max_peaks=1)
+    pg, peaks = _estimator_back(res, x_ref, objective, sr=_np(sr), sde_spectrum=_np((sr - mean) / std))
     results = dict(tls=pg, peaks=peaks, peak_info=None)
     if peaks:
         ind = peaks[0]["index"] - 1           # (find_peaks counts from one: this is the grid's highest sample itself)

@@ -1,5 +1,5 @@
-"""GPU: estimators.tls_power, transit_template and tls_estimator -- the template-search kernels (tls_lds_kernel, tls_slab_kernel)
-against the brute-force numpy restatement of DESIGN.md section 18 (tests/tls_oracle.py).
+"""GPU: estimators.tls_power, transit_template and tls_estimator -- the template-search kernels (search_lds_kernel<TemplateSearch>,
+search_slab_kernel<TemplateSearch>) against the brute-force numpy restatement of DESIGN.md section 18 (tests/tls_oracle.py).
 
 Tolerances are not constants (DESIGN.md 9.5's rule): every case computes, on its own input, the largest relative difference
 between the oracle run in float64 and in np.longdouble at the same maximiser, and allows 16 times that with a floor of 1e-13,
@@ -191,6 +191,42 @@ def test_all_ones_templates_are_the_box_search(dev):
     assert np.array_equal(tls["duration"], box["duration"]) and np.array_equal(tls["transit_time"], box["transit_time"])
     assert err <= tol
     assert O.rel_diff(tls["log_likelihood"], 0.5 * box["depth_snr"] ** 2) <= tol and np.all(tls["log_likelihood"] < box["log_likelihood"])
+
+
+def slab_switch_input(seed=3):
+    """N = 600 cadences over 200 days and six periods of 3833 .. 3838 bins (duration 0.2, oversample 10): three on each side
+    of the 3835 bins that the LDS holds"""
+    rs = np.random.RandomState(seed)
+    t = np.sort(rs.uniform(0, 200, 600))
+    y = 2e-3 * rs.randn(600)
+    y[np.abs((t - 11.0 + 38.25) % 76.5 - 38.25) < 0.1] -= 0.01
+    return t, y, 0.02 * (np.arange(3823, 3829) - 0.5)
+
+
+def test_all_ones_templates_are_the_box_search_on_the_slab_path(dev):
+    """the property of test_all_ones_templates_are_the_box_search where that test does not reach: periods whose histogram lives
+    in a slab of the workspace (search_slab_kernel), next to neighbours that still fit the LDS, for both searches"""
+    from exoplanet_amd.estimators import bls_plan, bls_power, tls_power
+
+    t, y, periods = slab_switch_input()
+    durations, fields = (0.2,), ("power", "depth", "depth_err", "depth_snr")
+    _, m, n_bins = bls_plan(periods, durations, OVERSAMPLE)
+    assert list(n_bins) == [3833, 3834, 3835, 3836, 3837, 3838]
+    ones = [np.ones(int(m[0]))]
+    want, _, unit_tls = TO.unit_and_reference(t, y, None, periods, durations, ones, OVERSAMPLE, "snr")
+    box_want = O.bls_power(t, y, None, periods, durations, OVERSAMPLE, "snr")
+    box_exact = O.bls_power(t, y, None, periods, durations, OVERSAMPLE, "snr", dtype=np.longdouble)
+    same = (box_want["duration"] == want["duration"]) & (np.abs(box_want["transit_time"] - want["transit_time"]) < 1e-9)
+    unit = max([unit_tls] + [O.rel_diff(box_want[k][same], box_exact[k][same]) for k in fields])
+    tol = max(TO.FACTOR * unit, TO.FLOOR)
+    tls = host(tls_power(T(t, dev), T(y, dev), periods=periods, durations=durations, templates=ones, objective="snr"))
+    box = host(bls_power(T(t, dev), T(y, dev), periods=periods, durations=durations, objective="snr"))
+    err = max(O.rel_diff(tls[k], box[k]) for k in fields)
+    print(f"[g = 1, snr, 3833 .. 3838 bins] the two oracles pick the same window on {int(same.sum())} of {len(periods)} periods; "
+          f"unit {unit:.2e}, tolerance {tol:.2e}, tls_power against bls_power {err:.2e}")
+    assert same.all() and np.array_equal(tls["period"], box["period"])
+    assert np.array_equal(tls["duration"], box["duration"]) and np.array_equal(tls["transit_time"], box["transit_time"])
+    assert err <= tol
 
 
 def test_the_template_recovers_the_mid_transit_depth(dev):

@@ -1,16 +1,22 @@
-"""registers / scratch / occupancy of the kernels of one translation unit: python tools/kres.py exo_celerite.hip [filter] [-D...]"""
+"""registers / scratch / occupancy of the kernels of one translation unit, compiled with the flags the build gives that file
+(EXTRA_FLAGS of __graft_entry__.py): python tools/kres.py exo_celerite.hip [filter] [-D...]"""
+import os
 import re
 import subprocess
 import sys
+import tempfile
+
+R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, R)
+from __graft_entry__ import EXTRA_FLAGS, HIPCC  # noqa: E402
 
 src = sys.argv[1]
 pat = sys.argv[2] if len(sys.argv) > 2 and not sys.argv[2].startswith("-") else ""
 extra = [a for a in sys.argv[2:] if a.startswith("-")]
-import os
-R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I", R + "/include", "-mllvm",
-       "-disable-machine-licm", "-c", R + "/exoplanet_amd/csrc/" + src, "-o", "/tmp/kres.o", "-Rpass-analysis=kernel-resource-usage"] + extra
-out = subprocess.run(cmd, capture_output=True, text=True).stderr
+with tempfile.TemporaryDirectory() as tmp:
+    cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I", R + "/include"] + EXTRA_FLAGS.get(src, []) + [
+        "-c", R + "/exoplanet_amd/csrc/" + src, "-o", tmp + "/kres.o", "-Rpass-analysis=kernel-resource-usage"] + extra
+    out = subprocess.run(cmd, capture_output=True, text=True).stderr
 cur = None
 rows = {}
 for line in out.splitlines():
@@ -27,10 +33,13 @@ for line in out.splitlines():
         k, v = txt.split(":", 1)
         rows[cur][k.strip()] = v.strip()
 for name, r in rows.items():
-    try:
-        dem = subprocess.run(["/opt/rocm/lib/llvm/bin/llvm-cxxfilt", name], capture_output=True, text=True).stdout.strip()
-    except Exception:
-        dem = name
+    dem = name
+    for filt in ("/opt/rocm/lib/llvm/bin/llvm-cxxfilt", "c++filt"):
+        try:
+            dem = subprocess.run([filt, name], capture_output=True, text=True).stdout.strip() or name
+            break
+        except OSError:
+            pass
     short = re.sub(r"\(anonymous namespace\)::", "", dem).split("(")[0].replace("void ", "")
     if pat and pat not in short:
         continue
