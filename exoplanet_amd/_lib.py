@@ -150,6 +150,9 @@ _SIGNATURES = {
     # y, exclude, n_exclude, n, n_series, lo, hi, edge, max_window, method, cval, n_iter, trend, scale, stream
     "exo_running_location_f64": (ctypes.c_int, [_c_dp, _c_dp, _i64, _i64, _i64, _c_dp, _c_dp, _c_dp, _i32, _i32, ctypes.c_double,
                                                 _i32, _c_dp, _c_dp, _c_dp]),
+    # t, y, exclude, n_exclude, n, n_series, lo, hi, edge, max_window, order, cval, n_iter, rescale, trend, scale, stream
+    "exo_running_trend_f64": (ctypes.c_int, [_c_dp, _c_dp, _c_dp, _i64, _i64, _i64, _c_dp, _c_dp, _c_dp, _i32, _i32, ctypes.c_double,
+                                             _i32, _i32, _c_dp, _c_dp, _c_dp]),
     # t, n, epochs, n_transit, period, t0, window, linear_time, lo, hi, widest, stream
     "exo_timing_windows_f64": (ctypes.c_int, [_c_dp, _i64, _c_dp, _i64, ctypes.c_double, ctypes.c_double, ctypes.c_double, _c_dp,
                                               _c_dp, _c_dp, _c_dp, _c_dp]),

@@ -2,7 +2,9 @@
 // running_location / flatten / sde): the order-preserving map from a double to a 64-bit key, selection of the k-th smallest
 // value of a window by bisection on those keys, the median, the median absolute deviation and Tukey's biweight location.
 // Definitions: DESIGN.md section 19.  Compiles for the device (exo_detrend.hip) and, with EXO_HOST_BUILD, for the host
-// (tests/flatten_harness.cpp checks it against the numpy restatement tests/flatten_oracle.py without a GPU).
+// (tests/flatten_harness.cpp checks it against the numpy restatement tests/flatten_oracle.py without a GPU).  Below them, for
+// order = 1 and 2 of the same functions, the biweight-weighted local polynomial in the window's time (DESIGN.md section 21;
+// exo_trend.hip, tests/trend_harness.cpp, tests/trend_oracle.py).
 //
 // A window is `len` consecutive doubles v[0 .. len - 1]; a cadence that takes no part (the caller's `exclude`) holds
 // kExcludedBits, a quiet NaN, and drops out of every comparison below by itself (a NaN compares false).  Nothing here sorts
@@ -171,6 +173,163 @@ EXO_DET_HD double window_location(P v, int len, int method, double cval, int n_i
   const double s = mad(v, len, m, med);
   if (want_scale) *scale = s;
   return method == kMethodMedian ? med : biweight(v, len, med, s, cval, n_iter);
+}
+
+// ---- the local polynomial trend -----------------------------------------------------------------------
+//
+// Tukey-biweight M-estimation of a polynomial of degree P <= 2 in the time of a window, evaluated at the cadence's own time.
+// The window is now two runs of `len` doubles read at the same offsets, the values v (an excluded cadence: NaN, as above) and
+// their times t; nothing is stored, and the moments and the factorisation of a fit live in registers.
+
+// a window value beside its time: what the selection functions above see when they select among residuals
+struct Sample {
+  double v, t;
+};
+
+template <class PV, class PT>
+struct Samples {
+  PV v;
+  PT t;
+  EXO_DET_HD Sample operator[](int j) const { return Sample{v[j], t[j]}; }
+};
+
+// the polynomial of a fit in x = (t - t0) * inv_span, by Horner
+template <int P>
+struct Poly {
+  double c[P + 1];
+  double t0, inv_span;
+  EXO_DET_HD double abscissa(double t) const { return (t - t0) * inv_span; }
+  EXO_DET_HD double at(double x) const {
+    double r = c[P];
+    for (int k = P - 1; k >= 0; --k) r = r * x + c[k];
+    return r;
+  }
+};
+
+// |v - P_c(x)|: the residuals whose median rescales a fit (an excluded cadence: NaN, which no comparison counts)
+template <int P>
+struct AbsResidual {
+  Poly<P> poly;
+  EXO_DET_HD double operator()(Sample s) const { return fabs(s.v - poly.at(poly.abscissa(s.t))); }
+};
+
+constexpr double kPivotFloor = 1e-10;  // a pivot <= kPivotFloor * M_0 stops a stage
+
+// the number of distinct times among the participating cadences of a window on a non-decreasing axis: an exact count
+template <class PV, class PT>
+EXO_DET_HD int count_distinct_times(PV v, PT t, int len) {
+  int n = 0;
+  double prev = NAN;
+  EXO_DET_UNROLL
+  for (int j = 0; j < len; ++j) {
+    const double vj = v[j], tj = t[j];
+    const bool in = vj == vj;
+    n += (in && tj != prev) ? 1 : 0;
+    prev = in ? tj : prev;
+  }
+  return n;
+}
+
+// One stage: exactly n_iter steps c += M^-1 b from the coefficients in `poly`, with M_k = sum w x^k, b_k = sum w x^k d,
+// d = v - P_c(x), u = d / (cval scale), w = (1 - u^2)^2 inside |u| < 1; sums in the window's order.  M, the Hankel matrix
+// M_{a+b}, is factored as L D L^T (the Cholesky factorisation without its square roots) in the order written below.  false:
+// the stage stopped -- M_0 == 0 or a pivot <= kPivotFloor * M_0 -- and c is what the last completed step left.
+template <int P, class PV, class PT>
+EXO_DET_HD bool trend_stage(PV v, PT t, int len, Poly<P>& poly, double scale, double cval, int n_iter) {
+  const double r = 1.0 / (cval * scale);
+  for (int it = 0; it < n_iter; ++it) {
+    double M[2 * P + 1], b[P + 1];
+    for (int k = 0; k <= 2 * P; ++k) M[k] = 0.0;
+    for (int k = 0; k <= P; ++k) b[k] = 0.0;
+    EXO_DET_UNROLL
+    for (int j = 0; j < len; ++j) {
+      const double vj = v[j], tj = t[j];
+      const double x = poly.abscissa(tj);
+      const double d = vj - poly.at(x);
+      const double u = d * r;
+      if (fabs(u) < 1.0) {
+        const double q = 1.0 - u * u;
+        double wk = q * q;
+        for (int k = 0; k <= 2 * P; ++k) {
+          M[k] += wk;
+          if (k <= P) b[k] += d * wk;
+          wk = wk * x;
+        }
+      }
+    }
+    if (M[0] == 0.0) return false;
+    const double floor_ = kPivotFloor * M[0];
+    if constexpr (P == 0) {
+      poly.c[0] += b[0] / M[0];
+    } else if constexpr (P == 1) {
+      const double l10 = M[1] / M[0];
+      const double d1 = M[2] - l10 * M[1];
+      if (d1 <= floor_) return false;
+      const double a1 = (b[1] - l10 * b[0]) / d1;
+      poly.c[0] += b[0] / M[0] - l10 * a1;
+      poly.c[1] += a1;
+    } else {
+      const double l10 = M[1] / M[0], l20 = M[2] / M[0];
+      const double d1 = M[2] - l10 * M[1];
+      if (d1 <= floor_) return false;
+      const double e = M[3] - l20 * M[1];
+      const double l21 = e / d1;
+      const double d2 = (M[4] - l20 * M[2]) - l21 * e;
+      if (d2 <= floor_) return false;
+      const double z1 = b[1] - l10 * b[0];
+      const double z2 = (b[2] - l20 * b[0]) - l21 * z1;
+      const double a2 = z2 / d2;
+      const double a1 = z1 / d1 - l21 * a2;
+      poly.c[0] += (b[0] / M[0] - l10 * a1) - l20 * a2;
+      poly.c[1] += a1;
+      poly.c[2] += a2;
+    }
+  }
+  return true;
+}
+
+// the fit of effective order P from the median and the MAD (> 0): the stage, then `rescale` times the median of the
+// absolute residuals as the new scale and another stage.  *scale: the scale of the last stage run.
+template <int P, class PV, class PT>
+EXO_DET_HD double trend_fit(PV v, PT t, int len, int m, double med, double t0, double inv_span, double cval, int n_iter, int rescale,
+                            double* scale) {
+  Poly<P> poly;
+  poly.c[0] = med;
+  for (int k = 1; k <= P; ++k) poly.c[k] = 0.0;
+  poly.t0 = t0;
+  poly.inv_span = inv_span;
+  bool ran = trend_stage<P>(v, t, len, poly, *scale, cval, n_iter);
+  for (int pass = 0; pass < rescale && ran; ++pass) {
+    const double s = median_of(Samples<PV, PT>{v, t}, len, m, AbsResidual<P>{poly}, 62);
+    if (s == 0.0) break;
+    *scale = s;
+    ran = trend_stage<P>(v, t, len, poly, s, cval, n_iter);
+  }
+  return poly.c[0];
+}
+
+// The trend of one window at the time t0 of its cadence, t[0] <= t0 <= t[len - 1], and the last scale used; no participating
+// cadence: NaN and NaN.  ORDER = 1 or 2; the effective order is min(ORDER, number of distinct times - 1).
+template <int ORDER, class PV, class PT>
+EXO_DET_HD double window_trend(PV v, PT t, int len, double t0, double cval, int n_iter, int rescale, double* scale) {
+  const int m = count_valid(v, len);
+  if (m == 0) {
+    *scale = NAN;
+    return NAN;
+  }
+  const double med = median(v, len, m);
+  *scale = mad(v, len, m, med);
+  if (*scale == 0.0) return med;
+  const double first = t[0], last = t[len - 1];
+  const double span = fmax(last - t0, t0 - first);
+  if (span == 0.0) return med;
+  const double inv_span = 1.0 / span;
+  const int distinct = count_distinct_times(v, t, len);
+  const int p = distinct - 1 < ORDER ? distinct - 1 : ORDER;
+  if constexpr (ORDER >= 2)
+    if (p == 2) return trend_fit<2>(v, t, len, m, med, t0, inv_span, cval, n_iter, rescale, scale);
+  if (p >= 1) return trend_fit<1>(v, t, len, m, med, t0, inv_span, cval, n_iter, rescale, scale);
+  return trend_fit<0>(v, t, len, m, med, t0, inv_span, cval, n_iter, rescale, scale);
 }
 
 // ---- the windows -----------------------------------------------------------------------------------------------------------

@@ -5,7 +5,8 @@ keys.  Definitions: DESIGN.md section 9, and section 18 for transit least square
 limb-darkened template in place of the box, whose ``depth`` is the mid-transit depth and therefore a starting ``r`` (not in
 the reference).  Before the search comes the detrending (csrc/exo_detrend.hip): a time-windowed running
 median, MAD or biweight location, divided out of the series, since real photometry is not flat (not in the reference either;
-wotan's biweight and lightkurve's ``flatten`` are the CPU counterparts).
+wotan's biweight and lightkurve's ``flatten`` are the CPU counterparts); with ``order=1`` or ``2`` a robust local line or
+parabola in place of the location (csrc/exo_trend.hip).
 
 After the search come the transits one by one (csrc/exo_timing.hip): the same template slid over a
 grid of shifts of every single transit's mid-time, which gives the times a ``TTVOrbit`` starts from and the per-transit depths
@@ -350,6 +351,7 @@ def lomb_scargle_power(t, y, yerr=None, *, frequencies):
 # ---- detrending: running median, MAD and biweight location --------------------------------------------------------------------
 
 MAX_WINDOW = 8192       # EXO_LOCATION_MAX_WINDOW: cadences in one window
+MAX_TREND_WINDOW = 4096  # EXO_TREND_MAX_WINDOW: the same for order 1 and 2, whose kernel stages the times beside the values
 _METHODS = {"median": 0, "biweight": 1}
 
 
@@ -399,8 +401,14 @@ def location_plan(t, window_length, break_tolerance=None, edge_cutoff=0.0, check
     return LocationPlan(lo, hi, edge, _plan_widest(info, t, check_sorted, MAX_WINDOW, "EXO_LOCATION_MAX_WINDOW", "window_length"))
 
 
+def _check_trend_window(widest):
+    if widest > MAX_TREND_WINDOW:
+        raise ValueError(f"the widest window holds {widest} cadences, more than the {MAX_TREND_WINDOW} a window may hold with order "
+                         f"1 or 2 (EXO_TREND_MAX_WINDOW): shorten window_length or bin the series")
+
+
 def running_location(t, y, window_length=None, *, method="biweight", exclude=None, break_tolerance=None, edge_cutoff=0.0, cval=5.0,
-                     n_iter=10, return_scale=False, plan=None):
+                     n_iter=10, return_scale=False, plan=None, order=0, rescale=1):
     """Running robust location of ``y`` (N,) or (B, N) over time windows of ``window_length`` on ``t`` (N,), finite and
     non-decreasing: the trend that :func:`flatten` divides by (definition: DESIGN.md section 19).  Device tensors in and out.
 
@@ -412,15 +420,33 @@ def running_location(t, y, window_length=None, *, method="biweight", exclude=Non
     known transits with it).  ``break_tolerance``, ``edge_cutoff``: see :func:`location_plan`.  A window with no cadence left,
     and a cadence cut by ``edge_cutoff``, give NaN.
 
-    Returns ``trend``, (N,) or (B, N); with ``return_scale`` also the windows' MAD (unscaled).  With ``plan`` (a
-    :class:`LocationPlan` of the same ``t``; ``window_length``, ``break_tolerance`` and ``edge_cutoff`` are then not read) the call
-    enqueues kernels only and may be captured into a graph.  Bitwise reproducible; a row of a batch is bitwise the single call."""
+    ``order``: 0 (the default) is the location above, a polynomial of degree 0.  1 or 2 (``method="biweight"`` only; DESIGN.md
+    section 21; csrc/exo_trend.hip) fits a polynomial of that degree in time to the window with the same biweight weights --
+    ``n_iter`` weighted least-squares steps from the median, then ``rescale`` times (an integer >= 0, read only here) the median
+    absolute residual as the new scale and ``n_iter`` more steps -- and returns its value at the cadence's own time.  A line
+    removes the location's bias next to a gap or a segment's end, about ``slope * window / 4``, so that ``edge_cutoff`` need not
+    throw those cadences away; a parabola also removes its undershoot of every extremum, ``curvature * window**2 / 24``, so
+    that the window may be twice as long.  A window holds at most ``MAX_TREND_WINDOW`` cadences then.
+
+    Returns ``trend``, (N,) or (B, N); with ``return_scale`` also the windows' MAD (unscaled; for ``order`` 1 and 2 the last scale
+    used).  With ``plan`` (a :class:`LocationPlan` of the same ``t``; ``window_length``, ``break_tolerance`` and ``edge_cutoff`` are
+    then not read) the call enqueues kernels only and may be captured into a graph.  Bitwise reproducible; a row of a batch is
+    bitwise the single call."""
     if method not in _METHODS:
         raise ValueError(f"unknown method {method!r}: 'median' or 'biweight'")
     if not float(cval) > 0:
         raise ValueError(f"cval must be positive, got {cval}")
     if int(n_iter) != n_iter or n_iter < 0:
         raise ValueError(f"n_iter must be an integer >= 0, got {n_iter}")
+    if order not in (0, 1, 2):
+        raise ValueError(f"order must be 0, 1 or 2, got {order}")
+    if order:
+        if method != "biweight":
+            raise ValueError(f"order {order} needs method 'biweight', got {method!r}")
+        if int(rescale) != rescale or rescale < 0:
+            raise ValueError(f"rescale must be an integer >= 0, got {rescale}")
+        if plan is not None:
+            _check_trend_window(plan.max_window)
     t, y, _, batched = _device_series(t, y, None)
     B, N = y.shape
     if exclude is not None:
@@ -434,11 +460,19 @@ def running_location(t, y, window_length=None, *, method="biweight", exclude=Non
     trend = torch.empty((B, N), dtype=torch.float64, device=t.device)
     scale = torch.empty((B, N), dtype=torch.float64, device=t.device) if return_scale else None
     lib = _lib.load()
-    _lib.check(lib.exo_running_location_f64(y.data_ptr(), 0 if exclude is None else exclude.data_ptr(),
-                                            0 if exclude is None else exclude.shape[0], N, B, plan.lo.data_ptr(), plan.hi.data_ptr(),
-                                            plan.edge.data_ptr(), plan.max_window, _METHODS[method], float(cval), int(n_iter),
-                                            trend.data_ptr(), 0 if scale is None else scale.data_ptr(), _stream(t)),
-               "exo_running_location_f64")
+    if order:
+        _check_trend_window(plan.max_window)
+        _lib.check(lib.exo_running_trend_f64(t.data_ptr(), y.data_ptr(), 0 if exclude is None else exclude.data_ptr(),
+                                             0 if exclude is None else exclude.shape[0], N, B, plan.lo.data_ptr(), plan.hi.data_ptr(),
+                                             plan.edge.data_ptr(), plan.max_window, int(order), float(cval), int(n_iter), int(rescale),
+                                             trend.data_ptr(), 0 if scale is None else scale.data_ptr(), _stream(t)),
+                   "exo_running_trend_f64")
+    else:
+        _lib.check(lib.exo_running_location_f64(y.data_ptr(), 0 if exclude is None else exclude.data_ptr(),
+                                                0 if exclude is None else exclude.shape[0], N, B, plan.lo.data_ptr(), plan.hi.data_ptr(),
+                                                plan.edge.data_ptr(), plan.max_window, _METHODS[method], float(cval), int(n_iter),
+                                                trend.data_ptr(), 0 if scale is None else scale.data_ptr(), _stream(t)),
+                   "exo_running_location_f64")
     if not batched:
         trend, scale = trend[0], None if scale is None else scale[0]
     return (trend, scale) if return_scale else trend
@@ -447,9 +481,11 @@ def running_location(t, y, window_length=None, *, method="biweight", exclude=Non
 def flatten(t, y, window_length, *, return_trend=False, **kwargs):
     """Remove the slow variability of a light curve before the period search: ``y / trend`` with ``trend`` the
     :func:`running_location` of ``y`` over windows of ``window_length`` (``kwargs``: its ``method``, ``exclude``,
-    ``break_tolerance``, ``edge_cutoff``, ``cval``, ``n_iter``).  ``t`` sorted, (N,); ``y`` (N,) or (B, N); numpy arrays or tensors
-    in, numpy out.  A window some three times the longest transit keeps the transits' depth; ``exclude`` masks the transits
-    already found before a second search.  With ``return_trend``: ``(flat, trend)``."""
+    ``break_tolerance``, ``edge_cutoff``, ``cval``, ``n_iter``, ``order``, ``rescale``).  ``t`` sorted, (N,); ``y`` (N,) or (B, N);
+    numpy arrays or tensors in, numpy out.  A window some three times the longest transit keeps the transits' depth; ``exclude``
+    masks the transits already found before a second search.  ``order=2`` follows the variability's extrema and the ramps at
+    a segment's ends with a window twice as long, e.g. ``flatten(t, y, 1.5, order=2, break_tolerance=0.5)``.  With
+    ``return_trend``: ``(flat, trend)``."""
     dev = _device_of(t, y)
     if "exclude" in kwargs and kwargs["exclude"] is not None:
         kwargs["exclude"] = torch.as_tensor(kwargs["exclude"], dtype=torch.bool, device=dev)

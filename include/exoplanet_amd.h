@@ -55,7 +55,7 @@ extern "C" {
  * 20: the solve -- exo_celerite_solve_work_doubles, exo_celerite_solve_f64.
  * 21: the astrometric likelihood -- exo_astrometry_loglike_vjp_f64.  (Entry points added since, no new number because no
  *     caller breaks: exo_tls_power_f64; exo_location_windows_f64, exo_running_location_f64, EXO_LOCATION_*;
- *     exo_timing_windows_f64, exo_transit_timing_f64, EXO_TIMING_*.) */
+ *     exo_timing_windows_f64, exo_transit_timing_f64, EXO_TIMING_*; exo_running_trend_f64, EXO_TREND_MAX_WINDOW.) */
 #define EXO_ABI_VERSION 21
 int32_t exo_abi_version(void);
 
@@ -1037,6 +1037,32 @@ int exo_location_windows_f64(const double* t, int64_t n, double half_window, dou
 int exo_running_location_f64(const double* y, const uint8_t* exclude, int64_t n_exclude, int64_t n, int64_t n_series,
                              const int32_t* lo, const int32_t* hi, const uint8_t* edge, int32_t max_window, int32_t method,
                              double cval, int32_t n_iter, double* trend, double* scale, void* stream);
+
+/* ---------------------------------------------------------------------------
+ * The robust local-polynomial trend (exoplanet_amd/estimators.py: running_location and flatten with order = 1 or 2;
+ * definition: DESIGN.md section 21): over the windows of exo_location_windows_f64, Tukey-biweight M-estimation of a
+ * polynomial of degree `order` in time, evaluated at the cadence's own time -- what the location above is for degree 0,
+ * without its bias next to a segment's end and at an extremum.  One kernel on the caller's stream; no atomics, no
+ * workspace: results are bitwise reproducible, and a row of a batch is bitwise the single call.
+ *
+ * exo_running_trend_f64 -- t[n]: the axis the windows were made for; y, exclude, n_exclude, lo, hi, edge (or NULL): as for
+ * exo_running_location_f64.  max_window: at least the widest window; the workgroup stages the values AND the times of its
+ * 256-cadence tile's span, 16 (256 + 2 max_window - 2) bytes of LDS, which bounds it by EXO_TREND_MAX_WINDOW = 4096 cadences
+ * (135 136 of the 163 840 bytes of a CU).  A cadence whose window is wider than max_window or does not hold the cadence
+ * itself gets NaN, never a wrong value; no index leaves [0, n) or the staged span whatever lo and hi hold.
+ * trend[n_series][n]: from the window's median, scaled by its MAD, exactly n_iter weighted least-squares steps of a
+ * polynomial of degree min(order, distinct times of the window - 1) in x = (t - t[i]) / max(t[hi[i]] - t[i], t[i] - t[lo[i]]);
+ * then `rescale` times: the median absolute residual as the new scale and n_iter more steps; the value at x = 0.  The median
+ * where the MAD or the window's extent is 0; a stage stops where the weights sum to 0 or a pivot of the moment matrix is at
+ * most 1e-10 of that sum.  scale[n_series][n], or NULL: the scale of the last stage run (the MAD where none ran).  No
+ * participating value, or edge[i]: NaN in both.  EXO_ERR_INVALID_ARGUMENT, before any launch: a null t, y, lo, hi or
+ * trend, n < 1, n_series < 1, an order other than 1 or 2, cval <= 0 (or NaN), n_iter < 0, rescale < 0, max_window outside
+ * [1, EXO_TREND_MAX_WINDOW], n_exclude other than 0, 1 or n_series, or rows promised and a null exclude.  (Added without a
+ * new ABI number: no caller breaks.) */
+#define EXO_TREND_MAX_WINDOW 4096
+int exo_running_trend_f64(const double* t, const double* y, const uint8_t* exclude, int64_t n_exclude, int64_t n, int64_t n_series,
+                          const int32_t* lo, const int32_t* hi, const uint8_t* edge, int32_t max_window, int32_t order, double cval,
+                          int32_t n_iter, int32_t rescale, double* trend, double* scale, void* stream);
 
 /* ---------------------------------------------------------------------------
  * Per-transit times and depths (exoplanet_amd/estimators.py: timing_plan, transit_times, ttv_estimator; definition:
