@@ -240,10 +240,19 @@ EXO_EST_HD void ls_accumulate(LsSums& a, double w, double wy, double sn, double 
 // the totals W = sum w, Y = sum w y.  Removing the weighted mean of y and of both basis functions leaves the
 // 2 x 2 normal equations  [[SS, CS], [CS, CC]] (a, b) = (YS, YC); the rotation by tau, tan 2 tau = 2 CS / (CC - SS),
 // diagonalises them, and the power is the sum of the two projections.  A direction with no variance contributes nothing.
-EXO_EST_HD double ls_power(const LsSums& a, double W, double Y) {
-  const double ybar = Y / W;
-  const double YS = a.ys - ybar * a.s, YC = a.yc - ybar * a.c;
-  const double CC = a.cc - a.c * a.c / W, SS = a.ss - a.s * a.s / W, CS = a.sc - a.c * a.s / W;
+//
+// In two steps, because the Keplerian periodogram (exo_keplerian_core.hpp) centres its sums instrument by instrument and then
+// solves the same 2 x 2 system: ls_fit_centred takes the centred sums and also gives the coefficients (a of the sine column,
+// b of the cosine column; a direction with no variance gets the coefficient 0), ls_power centres and takes the power.
+struct LsCentred {
+  double YS, YC, SS, CC, CS;
+};
+struct LsFit {
+  double power, a, b;
+};
+
+EXO_EST_HD LsFit ls_fit_centred(const LsCentred& m, double W) {
+  const double YS = m.YS, YC = m.YC, SS = m.SS, CC = m.CC, CS = m.CS;
   const double d = CC - SS, h = hypot(d, 2.0 * CS);
   double c2t = 1.0, s2t = 0.0;
   if (h > 0.0) {
@@ -263,10 +272,23 @@ EXO_EST_HD double ls_power(const LsSums& a, double W, double Y) {
   const double cc = CC * ct * ct + 2.0 * CS * ct * st + SS * st * st;  // the larger eigenvalue: (CC + SS + h) / 2
   const double ss = SS * ct * ct - 2.0 * CS * ct * st + CC * st * st;  // the smaller one
   const double tiny = 1e-14 * W;
-  double pw = 0.0;
-  if (cc > tiny) pw += yc * yc / cc;
-  if (ss > tiny) pw += ys * ys / ss;
-  return 0.5 * pw;
+  double pw = 0.0, ac = 0.0, as = 0.0;  // ac, as: the coefficients of the rotated columns c ct + s st and s ct - c st
+  if (cc > tiny) {
+    pw += yc * yc / cc;
+    ac = yc / cc;
+  }
+  if (ss > tiny) {
+    pw += ys * ys / ss;
+    as = ys / ss;
+  }
+  return LsFit{0.5 * pw, ac * st + as * ct, ac * ct - as * st};
+}
+
+EXO_EST_HD double ls_power(const LsSums& a, double W, double Y) {
+  const double ybar = Y / W;
+  const double YS = a.ys - ybar * a.s, YC = a.yc - ybar * a.c;
+  const double CC = a.cc - a.c * a.c / W, SS = a.ss - a.s * a.s / W, CS = a.sc - a.c * a.s / W;
+  return ls_fit_centred(LsCentred{YS, YC, SS, CC, CS}, W).power;
 }
 
 }  // namespace est

@@ -12,13 +12,19 @@ After the search come the transits one by one (csrc/exo_timing.hip, DESIGN.md se
 grid of shifts of every single transit's mid-time, which gives the times a ``TTVOrbit`` starts from and the per-transit depths
 behind the odd/even test (not in the reference).
 
+For radial velocities the search is the Keplerian periodogram (csrc/exo_keplerian.hip): at every
+frequency a grid of eccentricities and times of periastron, each candidate a linear fit with one constant per instrument,
+which gives the ``ecc``, ``omega``, ``t_periastron``, ``K`` and zero points an RV model starts from (not in the reference).
+
 Low level (device tensors in and out, float64): :func:`bls_power`, :func:`tls_power` (its templates:
-:func:`transit_template`), :func:`lomb_scargle_power`, :func:`running_location` (its windows: :func:`location_plan`),
+:func:`transit_template`), :func:`lomb_scargle_power`, :func:`keplerian_power`, :func:`running_location` (its windows:
+:func:`location_plan`),
 :func:`transit_times` (its windows: :func:`timing_plan`), and the
 grids :func:`bls_autoperiod`, :func:`lomb_scargle_autofrequency` (host arithmetic).
 
 High level (numpy arrays or tensors in, numpy out, ``peaks`` hold Python floats): :func:`flatten`, :func:`bls_estimator`,
-:func:`tls_estimator`, :func:`ttv_estimator`, :func:`lomb_scargle_estimator`, :func:`autocorr_estimator`, :func:`find_peaks`, :func:`sde`,
+:func:`tls_estimator`, :func:`ttv_estimator`, :func:`lomb_scargle_estimator`, :func:`keplerian_estimator`,
+:func:`autocorr_estimator`, :func:`find_peaks`, :func:`sde`,
 :func:`estimate_semi_amplitude`, :func:`estimate_minimum_mass`.  Plain numbers throughout: days, m/s and solar masses in, m/s and
 Jupiter masses out.
 
@@ -34,7 +40,8 @@ Run-to-run differences: the box search and the template search sum each phase bi
 fixed; ``power`` and the other outputs may differ in their last bits between two runs on the same input (and a near-tie
 between two boxes may then resolve differently).  The Lomb-Scargle sums have a fixed order and are bitwise reproducible, and so
 are the running filters (no atomics: selection does no arithmetic, the biweight sums run in the window's order) and the
-per-transit fit (sums in the window's order, a fixed-shape reduction), a row of a batch being bitwise what the single call gives.
+per-transit fit (sums in the window's order, a fixed-shape reduction), a row of a batch being bitwise what the single call gives;
+the same holds for the Keplerian periodogram (a lane sums its candidate over the epochs in order; the only reduction is an arg-max).
 """
 import collections
 import ctypes
@@ -45,10 +52,10 @@ import torch
 from . import _lib
 
 __all__ = [
-    "bls_power", "tls_power", "transit_template", "lomb_scargle_power", "bls_autoperiod", "lomb_scargle_autofrequency",
+    "bls_power", "tls_power", "transit_template", "lomb_scargle_power", "keplerian_power", "bls_autoperiod", "lomb_scargle_autofrequency",
     "LocationPlan", "location_plan", "running_location", "flatten", "sde",
     "TimingPlan", "timing_plan", "transit_times", "ttv_estimator",
-    "find_peaks", "bls_estimator", "tls_estimator", "lomb_scargle_estimator", "autocorr_function", "autocorr_estimator", "estimate_semi_amplitude", "estimate_minimum_mass",
+    "find_peaks", "bls_estimator", "tls_estimator", "lomb_scargle_estimator", "keplerian_estimator", "autocorr_function", "autocorr_estimator", "estimate_semi_amplitude", "estimate_minimum_mass",
 ]
 
 MAX_DURATIONS = 16      # EXO_BLS_MAX_DURATIONS
@@ -346,6 +353,108 @@ def lomb_scargle_power(t, y, yerr=None, *, frequencies):
                                                   0 if yerr is None else yerr.shape[0], N, B, f_dev.data_ptr(), F, out.data_ptr(),
                                                   ws.data_ptr(), ws.numel() * 8, _stream(t)), "exo_lomb_scargle_power_f64")
     return out if batched else out[0]
+
+
+MAX_INSTRUMENTS = 8     # EXO_KEP_MAX_INSTRUMENTS
+MAX_ECC = 64            # EXO_KEP_MAX_ECC: eccentricities of a grid
+MAX_PHASES = 4096       # EXO_KEP_MAX_PHASES
+KEPLERIAN_FIT = ("ecc", "omega", "t_periastron", "K", "zero_point")
+
+
+def _keplerian_grid(ecc, n_phase):
+    """-> the eccentricity grid as a host array and ``n_phase``, checked"""
+    ecc = np.linspace(0.0, 0.9, 10) if ecc is None else np.ascontiguousarray(np.atleast_1d(_np(ecc)))
+    if ecc.ndim != 1 or ecc.size < 1:
+        raise ValueError("ecc must be one-dimensional and hold at least one eccentricity")
+    if not np.all((ecc >= 0.0) & (ecc < 1.0)):
+        raise ValueError("every eccentricity must lie in [0, 1)")
+    if ecc.size > MAX_ECC:
+        raise ValueError(f"at most {MAX_ECC} eccentricities per call")
+    if int(n_phase) != n_phase or not 1 <= n_phase <= MAX_PHASES:
+        raise ValueError(f"n_phase must be an integer in [1, {MAX_PHASES}], got {n_phase}")
+    return ecc, int(n_phase)
+
+
+def _instrument_segments(instrument, n):
+    """-> (order, offsets) of the ``n`` epochs sorted by instrument, stably: ``order`` a host int64 array (None without
+    ``instrument``: one instrument, the epochs as they are), ``offsets`` int32 of length n_inst + 1"""
+    if instrument is None:
+        return None, np.array([0, n], dtype=np.int32)
+    inst = instrument.detach().cpu().numpy() if isinstance(instrument, torch.Tensor) else np.asarray(instrument)
+    if inst.ndim != 1 or inst.size != n:
+        raise ValueError(f"instrument must have shape (N,) with N = {n}, got {tuple(inst.shape)}")
+    if inst.dtype == bool:
+        inst = inst.astype(np.int64)
+    if not np.issubdtype(inst.dtype, np.integer):
+        if not np.all(inst == np.round(inst)):
+            raise ValueError("instrument must hold integers")
+        inst = inst.astype(np.int64)
+    if inst.min() < 0:
+        raise ValueError("instrument must not be negative")
+    counts = np.bincount(inst)
+    if np.count_nonzero(counts) > MAX_INSTRUMENTS:
+        raise ValueError(f"at most {MAX_INSTRUMENTS} instruments per call")
+    if not np.all(counts > 0):
+        raise ValueError("the instruments must be numbered 0 .. n_inst - 1 without gaps: "
+                         f"none of the epochs belongs to instrument {int(np.flatnonzero(counts == 0)[0])}")
+    return np.argsort(inst, kind="stable"), np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
+
+
+def keplerian_power(t, y, yerr=None, *, frequencies, ecc=None, n_phase=64, instrument=None, return_fit=False):
+    """Keplerian periodogram of the radial velocities ``y`` (N,) or (B, N) at the epochs ``t`` (N,), any order: at every
+    frequency the largest ``(chi2_0 - chi2) / 2`` over a grid of eccentricities ``ecc`` (default ``linspace(0, 0.9, 10)``) and
+    ``n_phase`` times of periastron ``t.min() + (k / n_phase) / f``, where ``chi2`` is the weighted least-squares misfit of
+    ``c_inst + A cos nu + B sin nu`` (``nu``: the true anomaly) and ``chi2_0`` that of the constants alone (DESIGN.md section
+    22).  ``instrument``: integers 0 .. n_inst - 1 (at most 8), one per epoch, each instrument with a constant of its own; None:
+    one instrument.  ``yerr`` as in :func:`lomb_scargle_power`; ``frequencies`` (F,), ``ecc``: numpy arrays or tensors.
+    Returns the power, (F,) or (B, F); with ``ecc=[0]`` and one instrument it is :func:`lomb_scargle_power`, and with 0 in the
+    grid it is never below it.
+
+    ``return_fit=True``: also a dict of tensors ``ecc, omega, t_periastron, K`` (..., F) and ``zero_point`` (..., F, n_inst) of
+    the winning candidate's fit (and ``candidate``, its number ``j * n_phase + k`` in the grids, int64), in the convention of
+    ``KeplerianOrbit.get_radial_velocity(t, K=K)`` and ``rv_log_likelihood(K=, zero_point=, instrument=)``: ``period = 1 / f``,
+    and the model is ``zero_point[instrument] + K (cos omega (cos nu + ecc) - sin omega sin nu)``.  Every sum has a fixed
+    order: the results are bitwise reproducible."""
+    e_host, n_phase = _keplerian_grid(ecc, n_phase)
+    n_given = t.shape[-1] if hasattr(t, "shape") and len(t.shape) else 0
+    order, offsets = _instrument_segments(instrument, int(n_given))
+    t, y, yerr, batched = _device_series(t, y, yerr)
+    f_host, f_dev = _grid(frequencies, "frequencies", t.device)
+    B, N, F, n_inst = y.shape[0], y.shape[1], f_host.size, offsets.size - 1
+    t_min = t.min()
+    if order is not None:                                      # the epochs by instrument (the sums need no time order)
+        order = torch.as_tensor(order, device=t.device)
+        t, y = t[order].contiguous(), y[:, order].contiguous()
+        yerr = None if yerr is None else yerr[:, order].contiguous()
+    power = torch.empty((B, F), dtype=torch.float64, device=t.device)
+    cand = torch.empty((B, F), dtype=torch.int32, device=t.device)
+    coef = torch.empty((B, F, 2 + n_inst), dtype=torch.float64, device=t.device)
+    if F:
+        lib = _lib.load()
+        nbytes = lib.exo_keplerian_workspace_bytes(N, B)
+        if nbytes < 0:
+            raise ValueError("keplerian_power: invalid sizes")
+        ws = _workspace(nbytes, t.device)
+        _lib.check(lib.exo_keplerian_power_f64(t.data_ptr(), y.data_ptr(), 0 if yerr is None else yerr.data_ptr(),
+                                               0 if yerr is None else yerr.shape[0], N, B,
+                                               offsets.ctypes.data_as(ctypes.c_void_p), n_inst, f_dev.data_ptr(), F,
+                                               e_host.ctypes.data_as(ctypes.c_void_p), e_host.size, n_phase, power.data_ptr(),
+                                               cand.data_ptr(), coef.data_ptr(), ws.data_ptr(), ws.numel() * 8, _stream(t)),
+                   "exo_keplerian_power_f64")
+    if not return_fit:
+        return power if batched else power[0]
+    # the elements of the winner: A = K cos w, B = -K sin w, c_k = zero_point_k + e A
+    nan = torch.full_like(power, float("nan"))
+    found = cand >= 0
+    c = cand.clamp(min=0).to(torch.int64)
+    e = torch.where(found, _grid(e_host, "ecc", t.device)[1][c // n_phase], nan)
+    phi = (c % n_phase).to(torch.float64) / n_phase
+    A, Bs = coef[..., 0], coef[..., 1]
+    fit = dict(ecc=e, omega=torch.atan2(-Bs, A), t_periastron=torch.where(found, t_min + phi / f_dev, nan), K=torch.hypot(A, Bs),
+               zero_point=coef[..., 2:] - (e * A)[..., None], candidate=cand.to(torch.int64))
+    if not batched:
+        power, fit = power[0], {k: v[0] for k, v in fit.items()}
+    return power, fit
 
 
 # ---- detrending: running median, MAD and biweight location --------------------------------------------------------------------
@@ -920,6 +1029,37 @@ def lomb_scargle_estimator(x, y, yerr=None, min_period=None, max_period=None, fi
     if filter_period is not None:
         power = power / np.sqrt(1 + ((1.0 / filter_period) / freq) ** 6)
     return dict(periodogram=(freq, power_est), peaks=find_peaks(freq, power, max_peaks=max_peaks))
+
+
+def keplerian_estimator(x, y, yerr=None, min_period=None, max_period=None, max_peaks=2, ecc=None, n_phase=64, instrument=None,
+                        **kwargs):
+    """Estimate the period and the orbital elements of a radial-velocity signal from its Keplerian periodogram
+    (:func:`keplerian_power`) on :func:`lomb_scargle_estimator`'s grid (``kwargs``: those of
+    :func:`lomb_scargle_autofrequency`).  Returns ``periodogram = (freq, power / len(x))``, the normalisation of
+    :func:`lomb_scargle_estimator`, and ``peaks`` from :func:`find_peaks`; each peak also carries ``ecc, omega, t_periastron,
+    K, zero_point`` and ``power`` at the grid frequency of the local maximum itself (``power`` as in ``periodogram``;
+    ``zero_point`` a float, or with ``instrument`` a list of one float per instrument).  They go straight into
+    ``KeplerianOrbit(period=, ecc=, omega=, t_periastron=)`` and ``rv_log_likelihood(K=, zero_point=, instrument=)``."""
+    if min_period is not None:
+        kwargs["maximum_frequency"] = 1.0 / min_period
+    if max_period is not None:
+        kwargs["minimum_frequency"] = 1.0 / max_period
+    dev = _device_of(x, y)
+    xh = _np(x)
+    freq = lomb_scargle_autofrequency(xh, **kwargs)
+    power, fit = keplerian_power(_to(xh, dev), _to(y, dev), _to(yerr, dev), frequencies=freq, ecc=ecc, n_phase=n_phase,
+                                 instrument=instrument, return_fit=True)
+    if power.ndim != 1:
+        raise ValueError("keplerian_estimator takes one series: y must have shape (N,)")
+    power = _np(power) / len(xh)
+    fit = {k: _np(v) for k, v in fit.items()}
+    peaks = find_peaks(freq, power, max_peaks=max_peaks)
+    for peak in peaks if max_peaks else [peaks]:
+        i = peak["index"] - 1                 # (find_peaks counts from one: this is the grid's local maximum itself)
+        assert 1 <= i < len(freq) - 1 and power[i] > power[i - 1] and power[i] > power[i + 1], peak
+        peak.update({k: float(fit[k][i]) for k in KEPLERIAN_FIT[:4]}, power=float(power[i]))
+        peak["zero_point"] = float(fit["zero_point"][i, 0]) if instrument is None else [float(v) for v in fit["zero_point"][i]]
+    return dict(periodogram=(freq, power), peaks=peaks)
 
 
 def autocorr_function(x):

@@ -55,7 +55,8 @@ extern "C" {
  * 20: the solve -- exo_celerite_solve_work_doubles, exo_celerite_solve_f64.
  * 21: the astrometric likelihood -- exo_astrometry_loglike_vjp_f64.  (Entry points added since, no new number because no
  *     caller breaks: exo_tls_power_f64; exo_location_windows_f64, exo_running_location_f64, EXO_LOCATION_*;
- *     exo_timing_windows_f64, exo_transit_timing_f64, EXO_TIMING_*; exo_running_trend_f64, EXO_TREND_MAX_WINDOW.) */
+ *     exo_timing_windows_f64, exo_transit_timing_f64, EXO_TIMING_*; exo_running_trend_f64, EXO_TREND_MAX_WINDOW;
+ *     exo_keplerian_workspace_bytes, exo_keplerian_power_f64, EXO_KEP_*.) */
 #define EXO_ABI_VERSION 21
 int32_t exo_abi_version(void);
 
@@ -1108,6 +1109,39 @@ int exo_transit_timing_f64(const double* t, const double* y, const double* ivar,
                            int32_t max_window, double duration, double max_shift, int32_t n_shift, double window,
                            const double* tmpl, int32_t n_template, const double* depth, int64_t n_depth,
                            int32_t min_in_transit, double* out, int32_t* iout, double* curve, void* stream);
+
+/* ---------------------------------------------------------------------------
+ * The Keplerian periodogram of radial velocities (exoplanet_amd/estimators.py: keplerian_power, keplerian_estimator;
+ * definition, kernel and measurements: DESIGN.md section 22).  For every frequency f and every series of y[n_series][n] at the
+ * epochs t[n]: the maximum over the candidates (e_j, phi_k = k / n_phase) of
+ *     power = (chi2_0 - chi2) / 2,    chi2 = min over (c, A, B) of sum w (y - c_inst - A cos nu - B sin nu)^2,
+ * nu the true anomaly at mean anomaly 2 pi (f (t - t_min) - phi_k) and eccentricity e_j, one free constant per instrument,
+ * chi2_0 the same with A = B = 0.  This is the package's radial-velocity model with A = K cos w, B = -K sin w,
+ * c_inst = zero_point_inst + e A and t_periastron = t_min + phi_k / f.  Candidates are numbered j * n_phase + k; where
+ * e_j == 0 only k = 0 is one; the lowest number wins among equal powers.
+ *
+ * The epochs are given SORTED BY INSTRUMENT: instrument k owns the epochs segment_offsets[k] .. segment_offsets[k + 1] - 1 of
+ * t, y and yerr, with 0 = segment_offsets[0] < ... < segment_offsets[n_instrument] = n.  Inside a segment any order.
+ * yerr: n_yerr = 0 (NULL: unit weights), 1 (one row for every series) or n_series rows of n; w = 1 / yerr^2.
+ * segment_offsets and ecc are HOST arrays (they travel by value in the kernel arguments); everything else lives on the
+ * device.  power[n_series][n_frequency]; candidate[n_series][n_frequency] (int32); coef[n_series][n_frequency][2 + n_instrument]
+ * = A, B and the constants c_k.  A (frequency, series) at which no candidate has a power that compares (NaN input): power
+ * -inf, candidate -1, coef NaN.  workspace: exo_keplerian_workspace_bytes(n, n_series) bytes (-1: invalid sizes), written
+ * by a preparation kernel (t - t_min, w, w y and every segment's sum w and sum w y) and read by the search.  Every sum has a
+ * fixed order: the outputs are bitwise reproducible, and a row of a batch is bitwise the single call.
+ * n_frequency == 0: EXO_OK, nothing launched.  EXO_ERR_INVALID_ARGUMENT, before any launch: a null t, y, segment_offsets,
+ * frequencies, ecc, power, candidate, coef or workspace; n < 1, n_series < 1 (or > 65535); n_yerr other than 0, 1 or
+ * n_series, or rows promised and a null pointer; n_instrument outside [1, EXO_KEP_MAX_INSTRUMENTS]; offsets that do not tile
+ * 0 .. n with a non-empty segment each; n_ecc outside [1, EXO_KEP_MAX_ECC]; n_phase outside [1, EXO_KEP_MAX_PHASES]; an e
+ * outside [0, 1) (or NaN).  EXO_ERR_WORKSPACE: workspace_bytes too small.  (Added without a new ABI number: no caller breaks.) */
+#define EXO_KEP_MAX_INSTRUMENTS 8
+#define EXO_KEP_MAX_ECC 64
+#define EXO_KEP_MAX_PHASES 4096
+int64_t exo_keplerian_workspace_bytes(int64_t n, int64_t n_series);
+int exo_keplerian_power_f64(const double* t, const double* y, const double* yerr, int64_t n_yerr, int64_t n, int64_t n_series,
+                            const int32_t* segment_offsets, int32_t n_instrument, const double* frequencies, int64_t n_frequency,
+                            const double* ecc, int32_t n_ecc, int32_t n_phase, double* power, int32_t* candidate, double* coef,
+                            void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------
  * Priors and constrained parameters (exoplanet_amd/distributions.py; definitions and measurements: DESIGN.md section 10).
