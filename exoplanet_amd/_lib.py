@@ -166,6 +166,11 @@ _SIGNATURES = {
     # n_phase, power, candidate, coef, workspace, workspace_bytes, stream
     "exo_keplerian_power_f64": (ctypes.c_int, [_c_dp, _c_dp, _c_dp, _i64, _i64, _i64, _c_dp, _i32, _c_dp, _i64, _c_dp, _i32,
                                                _i32, _c_dp, _c_dp, _c_dp, _c_dp, _i64, _c_dp]),
+    "exo_astrometric_workspace_bytes": (_i64, [_i64, _i64]),
+    # t, rho, rho_err, n_rho_err, theta, theta_err, n_theta_err, n, n_series, frequencies, n_frequency, ecc (host), n_ecc,
+    # n_phase, power, candidate, coef, workspace, workspace_bytes, stream
+    "exo_astrometric_power_f64": (ctypes.c_int, [_c_dp, _c_dp, _c_dp, _i64, _c_dp, _c_dp, _i64, _i64, _i64, _c_dp, _i64, _c_dp,
+                                                 _i32, _i32, _c_dp, _c_dp, _c_dp, _c_dp, _i64, _c_dp]),
     "exo_radial_velocity_fwd_f64": (ctypes.c_int, [_c_dp, _i64, _c_dp, _i64, _i32, _c_dp, _c_dp]),
     "exo_radial_velocity_vjp_f64": (ctypes.c_int, [_c_dp, _i64, _c_dp, _i64, _i32, _c_dp, _c_dp, _c_dp]),
     # t, tau, inst, rv, var, n_cad, n_var, params, n_draw, n_planet, trend, n_trend, offset, jit2, n_inst, loglike, gparams,

@@ -16,14 +16,18 @@ For radial velocities the search is the Keplerian periodogram (csrc/exo_kepleria
 frequency a grid of eccentricities and times of periastron, each candidate a linear fit with one constant per instrument,
 which gives the ``ecc``, ``omega``, ``t_periastron``, ``K`` and zero points an RV model starts from (not in the reference).
 
+For relative astrometry it is the search on the Thiele-Innes constants (csrc/exo_astrometric.hip): the
+same grid of candidates, each a linear fit of four constants to the sky-plane positions, which gives the seven elements
+``astrometry_log_likelihood`` starts from (not in the reference).
+
 Low level (device tensors in and out, float64): :func:`bls_power`, :func:`tls_power` (its templates:
-:func:`transit_template`), :func:`lomb_scargle_power`, :func:`keplerian_power`, :func:`running_location` (its windows:
+:func:`transit_template`), :func:`lomb_scargle_power`, :func:`keplerian_power`, :func:`astrometric_power`, :func:`running_location` (its windows:
 :func:`location_plan`),
 :func:`transit_times` (its windows: :func:`timing_plan`), and the
 grids :func:`bls_autoperiod`, :func:`lomb_scargle_autofrequency` (host arithmetic).
 
 High level (numpy arrays or tensors in, numpy out, ``peaks`` hold Python floats): :func:`flatten`, :func:`bls_estimator`,
-:func:`tls_estimator`, :func:`ttv_estimator`, :func:`lomb_scargle_estimator`, :func:`keplerian_estimator`,
+:func:`tls_estimator`, :func:`ttv_estimator`, :func:`lomb_scargle_estimator`, :func:`keplerian_estimator`, :func:`astrometric_estimator`,
 :func:`autocorr_estimator`, :func:`find_peaks`, :func:`sde`,
 :func:`estimate_semi_amplitude`, :func:`estimate_minimum_mass`.  Plain numbers throughout: days, m/s and solar masses in, m/s and
 Jupiter masses out.
@@ -41,7 +45,8 @@ fixed; ``power`` and the other outputs may differ in their last bits between two
 between two boxes may then resolve differently).  The Lomb-Scargle sums have a fixed order and are bitwise reproducible, and so
 are the running filters (no atomics: selection does no arithmetic, the biweight sums run in the window's order) and the
 per-transit fit (sums in the window's order, a fixed-shape reduction), a row of a batch being bitwise what the single call gives;
-the same holds for the Keplerian periodogram (a lane sums its candidate over the epochs in order; the only reduction is an arg-max).
+the same holds for the Keplerian periodogram and the astrometric search (a lane sums its candidate over the epochs in order; the
+only reduction is an arg-max).
 """
 import collections
 import ctypes
@@ -52,10 +57,10 @@ import torch
 from . import _lib
 
 __all__ = [
-    "bls_power", "tls_power", "transit_template", "lomb_scargle_power", "keplerian_power", "bls_autoperiod", "lomb_scargle_autofrequency",
+    "bls_power", "tls_power", "transit_template", "lomb_scargle_power", "keplerian_power", "astrometric_power", "bls_autoperiod", "lomb_scargle_autofrequency",
     "LocationPlan", "location_plan", "running_location", "flatten", "sde",
     "TimingPlan", "timing_plan", "transit_times", "ttv_estimator",
-    "find_peaks", "bls_estimator", "tls_estimator", "lomb_scargle_estimator", "keplerian_estimator", "autocorr_function", "autocorr_estimator", "estimate_semi_amplitude", "estimate_minimum_mass",
+    "find_peaks", "bls_estimator", "tls_estimator", "lomb_scargle_estimator", "keplerian_estimator", "astrometric_estimator", "autocorr_function", "autocorr_estimator", "estimate_semi_amplitude", "estimate_minimum_mass",
 ]
 
 MAX_DURATIONS = 16      # EXO_BLS_MAX_DURATIONS
@@ -452,6 +457,82 @@ def keplerian_power(t, y, yerr=None, *, frequencies, ecc=None, n_phase=64, instr
     A, Bs = coef[..., 0], coef[..., 1]
     fit = dict(ecc=e, omega=torch.atan2(-Bs, A), t_periastron=torch.where(found, t_min + phi / f_dev, nan), K=torch.hypot(A, Bs),
                zero_point=coef[..., 2:] - (e * A)[..., None], candidate=cand.to(torch.int64))
+    if not batched:
+        power, fit = power[0], {k: v[0] for k, v in fit.items()}
+    return power, fit
+
+
+AST_NCOEF = 10          # EXO_AST_NCOEF
+ASTROMETRIC_FIT = ("TA", "TB", "TF", "TG", "a_angular", "incl", "omega", "Omega", "t_periastron", "chi2")   # the record's order
+
+
+def _astrometric_error(name, err, shape, device):
+    """-> an error bar (a scalar, (N,) or the shape of the series) as contiguous rows (1, N) or (B, N) on the device"""
+    n = shape[-1]
+    if err is None:
+        raise ValueError(f"{name} is required: the weights of the fit are 1 / {name}^2")
+    if isinstance(err, torch.Tensor) and not err.is_cuda and err.ndim > 0:
+        raise ValueError(f"{name} lives on {err.device}: there is no CPU fallback")
+    if not isinstance(err, torch.Tensor) or err.ndim == 0:
+        return torch.full((1, n), float(err), dtype=torch.float64, device=device)
+    if tuple(err.shape) not in ((n,), (1, n), tuple(shape)):
+        raise ValueError(f"{name} must be a scalar or have shape (N,) or that of rho, got {tuple(err.shape)}")
+    return err.to(device=device, dtype=torch.float64).reshape(-1, n).contiguous()
+
+
+def astrometric_power(t, rho, rho_err, theta, theta_err, *, frequencies, ecc=None, n_phase=64, parallax=None, return_fit=False):
+    """Astrometric orbit search of the separations ``rho`` and position angles ``theta`` (radians), each (N,) or (B, N), at
+    the epochs ``t`` (N,), any order: at every frequency the largest ``(chi2_0 - chi2) / 2`` over a grid of eccentricities
+    ``ecc`` (default ``linspace(0, 0.9, 10)``) and ``n_phase`` times of periastron ``t.min() + (k / n_phase) / f``.  At a
+    fixed period, eccentricity and time of periastron the sky-plane position is linear in the four Thiele-Innes constants,
+    ``X = TA xi + TF eta``, ``Y = TB xi + TG eta`` with ``xi = cos E - ecc``, ``eta = sqrt(1 - ecc^2) sin E``; ``chi2`` is the
+    misfit of that least-squares fit with the radial error ``rho_err`` and the tangential error ``rho theta_err`` (the
+    measured ``rho``), and ``chi2_0`` that of no companion.  ``rho_err``, ``theta_err``: a scalar,
+    (N,) or (B, N); ``frequencies`` (F,), ``ecc``: numpy arrays or tensors.  Returns the power, (F,) or (B, F); a frequency
+    at which every candidate's normal equations are singular has power 0.
+
+    ``return_fit=True``: also a dict of tensors (..., F) of the winning candidate: ``candidate`` (its number ``j * n_phase +
+    k`` in the grids, int64, -1 where there is none), ``ecc, t_periastron, omega, Omega, incl, a_angular``, the constants
+    ``TA, TB, TF, TG`` and ``chi2``; with ``parallax`` (arcseconds) also ``a = a_angular / (parallax au_per_R_sun)`` in R_sun.
+    The elements are in the convention of ``KeplerianOrbit(period=1 / f, t_periastron=, ecc=, omega=, Omega=, incl=, a=)``,
+    whose ``get_relative_position(t, parallax)`` then is ``(X, Y)`` and whose ``astrometry_log_likelihood`` they start.
+    Astrometry alone cannot tell ``(omega, Omega)`` from ``(omega + pi, Omega + pi)``: ``Omega`` is given in ``[0, pi)``, the
+    usual rule, and ``omega`` in ``(-pi, pi]``.  Every sum has a fixed order: the results are bitwise reproducible."""
+    e_host, n_phase = _keplerian_grid(ecc, n_phase)
+    t, rho, _, batched = _device_series(t, rho, None)
+    _on_device("theta", theta)
+    if theta.ndim not in (1, 2) or (theta.ndim == 2) != batched or theta.shape[-1] != t.numel():
+        raise ValueError(f"theta must have the shape of rho, got {tuple(theta.shape)}")
+    theta = theta.to(device=t.device, dtype=torch.float64).reshape(-1, t.numel()).contiguous()
+    if theta.shape != rho.shape:
+        raise ValueError(f"theta must have the shape of rho, got {tuple(theta.shape)}")
+    rho_err = _astrometric_error("rho_err", rho_err, rho.shape, t.device)
+    theta_err = _astrometric_error("theta_err", theta_err, rho.shape, t.device)
+    f_host, f_dev = _grid(frequencies, "frequencies", t.device)
+    B, N, F = rho.shape[0], rho.shape[1], f_host.size
+    power = torch.empty((B, F), dtype=torch.float64, device=t.device)
+    cand = torch.empty((B, F), dtype=torch.int32, device=t.device)
+    coef = torch.empty((B, F, AST_NCOEF), dtype=torch.float64, device=t.device)
+    if F:
+        lib = _lib.load()
+        nbytes = lib.exo_astrometric_workspace_bytes(N, B)
+        if nbytes < 0:
+            raise ValueError("astrometric_power: invalid sizes")
+        ws = _workspace(nbytes, t.device)
+        _lib.check(lib.exo_astrometric_power_f64(t.data_ptr(), rho.data_ptr(), rho_err.data_ptr(), rho_err.shape[0], theta.data_ptr(),
+                                                 theta_err.data_ptr(), theta_err.shape[0], N, B, f_dev.data_ptr(), F,
+                                                 e_host.ctypes.data_as(ctypes.c_void_p), e_host.size, n_phase, power.data_ptr(),
+                                                 cand.data_ptr(), coef.data_ptr(), ws.data_ptr(), ws.numel() * 8, _stream(t)),
+                   "exo_astrometric_power_f64")
+    if not return_fit:
+        return power if batched else power[0]
+    c = cand.clamp(min=0).to(torch.int64)
+    e = torch.where(cand >= 0, _grid(e_host, "ecc", t.device)[1][c // n_phase], torch.full_like(power, float("nan")))
+    fit = dict(candidate=cand.to(torch.int64), ecc=e, **{k: coef[..., i] for i, k in enumerate(ASTROMETRIC_FIT)})
+    if parallax is not None:
+        from .orbits.constants import au_per_R_sun
+
+        fit["a"] = fit["a_angular"] / (parallax * au_per_R_sun)
     if not batched:
         power, fit = power[0], {k: v[0] for k, v in fit.items()}
     return power, fit
@@ -1059,6 +1140,50 @@ def keplerian_estimator(x, y, yerr=None, min_period=None, max_period=None, max_p
         assert 1 <= i < len(freq) - 1 and power[i] > power[i - 1] and power[i] > power[i + 1], peak
         peak.update({k: float(fit[k][i]) for k in KEPLERIAN_FIT[:4]}, power=float(power[i]))
         peak["zero_point"] = float(fit["zero_point"][i, 0]) if instrument is None else [float(v) for v in fit["zero_point"][i]]
+    return dict(periodogram=(freq, power), peaks=peaks)
+
+
+def astrometric_estimator(t, rho, rho_err, theta, theta_err, min_period=None, max_period=None, periods=None, max_peaks=2, ecc=None,
+                          n_phase=64, parallax=None):
+    """Estimate the period and the orbital elements of a visual binary or a directly imaged companion from the astrometric
+    orbit search (:func:`astrometric_power`) of its separations ``rho`` and position angles ``theta``.  The grid is
+    ``lomb_scargle_autofrequency(t, samples_per_peak=10, minimum_frequency=1 / max_period, maximum_frequency=1 / min_period)``
+    with the defaults ``max_period = 4 x baseline`` and ``min_period = 4 x baseline / N`` (astrometric orbits are often
+    covered only in part); an explicit ``periods`` (descending, so that the frequencies ascend -- a logarithmic grid, say)
+    overrides them.  Returns ``periodogram = (freq, power)`` and ``peaks`` from :func:`find_peaks`; each peak also carries
+    ``period, ecc, t_periastron, omega, Omega, incl, a_angular`` (with ``parallax`` also ``a``), ``chi2`` and ``power`` at the
+    grid frequency of the local maximum itself, ``period`` included (``period_refined`` keeps the parabola's).  They go straight into ``KeplerianOrbit(period=,
+    t_periastron=, ecc=, omega=, Omega=, incl=, a=)`` and its ``astrometry_log_likelihood``."""
+    th = _np(t)
+    if periods is not None:
+        freq = 1.0 / np.atleast_1d(_np(periods))
+        if freq.ndim != 1 or freq.size < 3 or not np.all(np.diff(freq) > 0):
+            raise ValueError("periods must be one-dimensional, descending and hold at least three periods")
+    else:
+        T = _span(th)
+        if not T > 0:
+            raise ValueError("the times span no baseline")
+        max_period = 4.0 * T if max_period is None else max_period
+        min_period = 4.0 * T / th.size if min_period is None else min_period
+        if not 0 < min_period < max_period:
+            raise ValueError("need 0 < min_period < max_period")
+        freq = lomb_scargle_autofrequency(th, samples_per_peak=10, minimum_frequency=1.0 / max_period,
+                                          maximum_frequency=1.0 / min_period)
+    dev = _device_of(t, rho, theta)
+    err = lambda e: _to(e, dev) if isinstance(e, (torch.Tensor, np.ndarray, list, tuple)) else e   # noqa: E731
+    power, fit = astrometric_power(_to(th, dev), _to(rho, dev), err(rho_err), _to(theta, dev), err(theta_err), frequencies=freq,
+                                   ecc=ecc, n_phase=n_phase, parallax=parallax, return_fit=True)
+    if power.ndim != 1:
+        raise ValueError("astrometric_estimator takes one series: rho and theta must have shape (N,)")
+    power = _np(power)
+    fit = {k: _np(v) for k, v in fit.items()}
+    peaks = find_peaks(freq, power, max_peaks=max_peaks)
+    keys = ("ecc", "t_periastron", "omega", "Omega", "incl", "a_angular") + (("a",) if parallax is not None else ()) + ("chi2",)
+    for peak in peaks if max_peaks else [peaks]:
+        i = peak["index"] - 1                 # (find_peaks counts from one: this is the grid's local maximum itself)
+        assert 1 <= i < len(freq) - 1 and power[i] > power[i - 1] and power[i] > power[i + 1], peak
+        peak.update({k: float(fit[k][i]) for k in keys}, period_refined=peak["period"], period=float(1.0 / freq[i]),
+                    power=float(power[i]))
     return dict(periodogram=(freq, power), peaks=peaks)
 
 

@@ -56,7 +56,8 @@ extern "C" {
  * 21: the astrometric likelihood -- exo_astrometry_loglike_vjp_f64.  (Entry points added since, no new number because no
  *     caller breaks: exo_tls_power_f64; exo_location_windows_f64, exo_running_location_f64, EXO_LOCATION_*;
  *     exo_timing_windows_f64, exo_transit_timing_f64, EXO_TIMING_*; exo_running_trend_f64, EXO_TREND_MAX_WINDOW;
- *     exo_keplerian_workspace_bytes, exo_keplerian_power_f64, EXO_KEP_*.) */
+ *     exo_keplerian_workspace_bytes, exo_keplerian_power_f64, EXO_KEP_*; exo_astrometric_workspace_bytes,
+ *     exo_astrometric_power_f64, EXO_AST_NCOEF.) */
 #define EXO_ABI_VERSION 21
 int32_t exo_abi_version(void);
 
@@ -1142,6 +1143,35 @@ int exo_keplerian_power_f64(const double* t, const double* y, const double* yerr
                             const int32_t* segment_offsets, int32_t n_instrument, const double* frequencies, int64_t n_frequency,
                             const double* ecc, int32_t n_ecc, int32_t n_phase, double* power, int32_t* candidate, double* coef,
                             void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------
+ * The astrometric orbit search on the Thiele-Innes constants (exoplanet_amd/estimators.py: astrometric_power,
+ * astrometric_estimator; definition, kernel and measurements: DESIGN.md section 23).  For every frequency f and every series
+ * of separations rho[n_series][n] and position angles theta[n_series][n] at the epochs t[n]: the maximum over the candidates
+ * (e_j, phi_k = k / n_phase) of the Keplerian periodogram's grid of
+ *     power = (chi2_0 - chi2) / 2,    chi2 = min over (TA, TB, TF, TG) of sum r^T P r,
+ *     r = (rho cos theta - TA xi - TF eta, rho sin theta - TB xi - TG eta),   xi = cos E - e,  eta = sqrt(1 - e^2) sin E,
+ *     P = (c, s)(c, s)^T / rho_err^2 + (-s, c)(-s, c)^T / (rho theta_err)^2,  (c, s) = (cos, sin) theta,
+ * E the eccentric anomaly at the mean anomaly 2 pi (f (t - t_min) - phi_k), chi2_0 = sum (x, y) P (x, y)^T.  A candidate whose
+ * normal matrix, scaled to a unit diagonal, has a squared Cholesky pivot below 1e-12 (or a non-positive diagonal) is none at
+ * that frequency.  Equal powers: the lowest candidate number j * n_phase + k wins.
+ * ecc is a HOST array (it travels by value in the kernel arguments); everything else lives on the device.  rho_err and
+ * theta_err: n_rho_err / n_theta_err rows of n, 1 (shared by the series) or n_series.  power[n_series][n_frequency];
+ * candidate[n_series][n_frequency] (int32); coef[n_series][n_frequency][EXO_AST_NCOEF] = TA, TB, TF, TG, a_angular, incl,
+ * omega, Omega, t_periastron = t_min + phi_k / f, chi2 -- the elements in the convention of KeplerianOrbit (amplitude
+ * -a_angular), Omega in [0, pi), omega in (-pi, pi].  A (frequency, series) with no candidate: power 0, candidate -1, coef NaN.
+ * workspace: exo_astrometric_workspace_bytes(n, n_series) bytes (-1: invalid sizes), written by a preparation kernel and read
+ * by the search.  Every sum has a fixed order: the outputs are bitwise reproducible, and a row of a batch is bitwise the
+ * single call.  n_frequency == 0: EXO_OK, nothing launched.  EXO_ERR_INVALID_ARGUMENT, before any launch: a null pointer;
+ * n < 1, n_series < 1 (or > 65535); n_rho_err or n_theta_err other than 1 or n_series; n_frequency < 0; n_ecc outside
+ * [1, EXO_KEP_MAX_ECC]; n_phase outside [1, EXO_KEP_MAX_PHASES]; an e outside [0, 1) (or NaN).  EXO_ERR_WORKSPACE:
+ * workspace_bytes too small.  (Added without a new ABI number: no caller breaks.) */
+#define EXO_AST_NCOEF 10
+int64_t exo_astrometric_workspace_bytes(int64_t n, int64_t n_series);
+int exo_astrometric_power_f64(const double* t, const double* rho, const double* rho_err, int64_t n_rho_err, const double* theta,
+                              const double* theta_err, int64_t n_theta_err, int64_t n, int64_t n_series, const double* frequencies,
+                              int64_t n_frequency, const double* ecc, int32_t n_ecc, int32_t n_phase, double* power,
+                              int32_t* candidate, double* coef, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------
  * Priors and constrained parameters (exoplanet_amd/distributions.py; definitions and measurements: DESIGN.md section 10).
