@@ -1,19 +1,26 @@
-// exo_contact.hpp -- first / fourth contact of an eccentric orbit (device only).
+// exo_contact.hpp -- first / fourth contact of an eccentric orbit.
 //
 // Replaces exoplanet_core's contact_points Op (reference call site
 // /root/reference/src/exoplanet/orbits/keplerian.py:744-753): the two roots
 // nearest mid-transit of  rho(f)^2 (1 - sin^2 i sin^2(omega+f)) = L^2,
 // L = R_star + r, returned as mean anomalies.  Coarse outward scan for the
 // bracket, then bracketed false position on the definition: O(planets) work per draw.
+// Also compiled for the host (g++, EXO_HOST_BUILD: tests/contact_harness.cpp holds these lines to the multiprecision fixture
+// tests/golden/contact_mp.npz without a GPU); that build is a test harness, not a product path.
 #pragma once
-#include <hip/hip_runtime.h>
 #include <math.h>
 
-#include "exo_math.hpp"
+#include "exo_math.hpp"   // EXO_HD; <hip/hip_runtime.h> unless EXO_HOST_BUILD
+
+#ifdef EXO_HOST_BUILD
+#define EXO_CONTACT_SOLVE inline
+#else
+#define EXO_CONTACT_SOLVE __device__ inline   // (not forced inline: the packing kernel calls it twice)
+#endif
 
 namespace exo {
 
-__device__ __forceinline__ double contact_g(double th, double p, double e, double cw, double sw,
+EXO_HD double contact_g(double th, double p, double e, double cw, double sw,
                                             double ci, double L) {
   double st, ct;
   exo::sincos_any(th, &st, &ct);          // |th| <= pi / 2: the branch-free kernel, a third of libm's instructions
@@ -23,7 +30,7 @@ __device__ __forceinline__ double contact_g(double th, double p, double e, doubl
 }
 
 // g and dg/ds in terms of s = sin(th), th in (-pi/2, pi/2): no trigonometry
-__device__ __forceinline__ double contact_gs(double s, double p, double e, double cw, double sw, double ci, double L,
+EXO_HD double contact_gs(double s, double p, double e, double cw, double sw, double ci, double L,
                                              double* dg) {
   const double c = sqrt(fmax(1.0 - s * s, 0.0));
   const double D = 1.0 + e * (sw * c - cw * s);
@@ -37,7 +44,7 @@ __device__ __forceinline__ double contact_gs(double s, double p, double e, doubl
 
 // mean anomaly of the point th = omega + f - pi/2 given s = sin(th): E from (sin E, cos E), on the revolution of
 // f = th + pi/2 - omega (E and f never differ by half a turn) -- the branch the bracketing path below returns
-__device__ __forceinline__ double contact_mean_anomaly(double s, double e, double cw, double sw) {
+EXO_HD double contact_mean_anomaly(double s, double e, double cw, double sw) {
   const double c = sqrt(fmax(1.0 - s * s, 0.0));
   const double cosf = sw * c - cw * s, sinf = sw * s + cw * c;      // f = th + (pi/2 - omega)
   const double den = 1.0 + e * cosf;
@@ -49,7 +56,7 @@ __device__ __forceinline__ double contact_mean_anomaly(double s, double e, doubl
 }
 
 // returns true on failure (no contact: the caller evaluates every cadence, keplerian.py:771-775)
-__device__ inline bool contact_solve(double a, double e, double cw, double sw, double ci, double L,
+EXO_CONTACT_SOLVE bool contact_solve(double a, double e, double cw, double sw, double ci, double L,
                                      double* M_left, double* M_right) {
   const double p = a * (1.0 - e * e);
   double out[2] = {0.0, 0.0};

@@ -950,10 +950,19 @@ class KeplerianOrbit:
             if secondary_sbr is not None:
                 # occultation window: the flipped orbit's own transit window, shifted to
                 # its mid-occultation time and expressed in [0, P) after t0
-                other = self._flip(r.detach())
-                ts2, te2, flag2 = other._transit_window(self.r_star.detach() + z)
                 P = (self.period + z).detach()
-                shift = torch.remainder((other.t0 - self.t0).detach() + z, P)
+                if self.ecc is None:
+                    # a circular orbit's occultation lasts as long as its transit, half a period later: the flipped orbit's
+                    # closed form is the same number, but reached through the inclination ANGLE, which costs cos i its
+                    # relative precision near 90 degrees (tests/golden/contact_mp.npz, H_circ_a100.0_bgraze4)
+                    ts2, te2, flag2, shift = ts, te, flag, 0.5 * P
+                else:
+                    other = self._flip(r.detach())
+                    ts2, te2, flag2 = other._transit_window(self.r_star.detach() + z)
+                    # t0(flipped) - t0 from the mean anomalies, as the packing kernel forms it: the two orbits share
+                    # t_periastron, and the difference of the two t0 themselves is rounded at their size -- 5e-10 d at
+                    # BJD 2 458 001 (the G_bjd entries of the same fixture)
+                    shift = torch.remainder(((other.M0 - self.M0) / self.n).detach() + z, P)
                 lo, hi = shift + ts2, shift + te2
                 bad2 = (flag2 != 0) | (lo < 0) | (hi > P)
                 cols[ops.P_TS2] = torch.where(bad2, -inf, lo)

@@ -7,8 +7,8 @@ of the two elementwise ops (pairs, pairs + tail, scalar; odd counts; inputs and 
 second grid pass) and the grid-stride loop of the RV / vector kernels past their 65 536-block cap.
 
 Tolerances are derived in tests/orbit_mp_cases.py, none from the code under test; every test prints unit, tolerance and error
-before it asserts.  exo_contact_points_f64 is only exercised for shapes and odd counts here, against the float64 oracle as
-before (a multiprecision reference for it is out of scope).  The public KeplerianOrbit methods are held for the systems
+before it asserts.  exo_contact_points_f64 is exercised for shapes and odd counts here, against the float64 oracle; its values,
+flags and the windows built on them are held to tests/golden/contact_mp.npz by tests/test_gpu_contact.py.  The public KeplerianOrbit methods are held for the systems
 whose record they reproduce (the RV with K: values of all, gradients where the class's own 2 pi / period equals the record's
 mean motion to the bit; the nine vector methods: the edge-on systems without a node rotation); elsewhere only the op level is
 covered."""
