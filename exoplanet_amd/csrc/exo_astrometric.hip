@@ -2,16 +2,9 @@
 // (exoplanet_amd/estimators.py: astrometric_power, astrometric_estimator): at every frequency the best of a grid of
 // (eccentricity, phase of periastron) candidates, each a linear least-squares fit of the four Thiele-Innes constants to the
 // sky-plane positions, with radial and tangential errors.  A translation unit of its own: none of the other kernels changes.
-// The arithmetic lives in exo_astrometric_core.hpp (tested on the host); definition, layout, resources and timings:
-// DESIGN.md section 23.  Compiled with -ffp-contract=off, as the host build of the core is.
-//
-// The search: a workgroup owns one (frequency, series).  A tile of kTile epochs -- the reduced phase f (t - t_min) in turns,
-// the three numbers of the precision matrix P and the two of q = P (x, y) -- is staged in LDS, and lane l takes the candidates
-// l, l + threads, ...: for each it walks all epochs in order, every lane reading the same LDS address (a broadcast), with the
-// thirteen running sums in registers, and solves its 4 x 4 system.  Every sum therefore has one fixed order: no atomics, no
-// sums across lanes.  A lane keeps the power, the number and the four constants of its best candidate; the only reduction
-// is the arg-max of (power, lowest candidate number) over the wave and then the workgroup, and the lane that owns the winner
-// writes the record.  Nothing but kernels is enqueued.
+// The arithmetic lives in exo_astrometric_core.hpp (tested on the host), the search over the candidates in
+// exo_orbit_search.hpp; definition, layout, resources and timings: DESIGN.md section 23.  Compiled with -ffp-contract=off, as
+// the host build of the core is.  Nothing but kernels is enqueued.
 #include <hip/hip_runtime.h>
 #include <limits.h>
 #include <math.h>
@@ -20,23 +13,14 @@
 #include "../../include/exoplanet_amd.h"
 #include "exo_astrometric_core.hpp"
 #include "exo_estimators_launch.hpp"
+#include "exo_orbit_search.hpp"
 
 namespace {
 
 using namespace ast;
+using namespace orb;
 
-constexpr int kWave = 64;
-constexpr int kMaxThreads = 256;
-constexpr int kTile = 256;  // epochs staged at a time: N is not capped by LDS
-constexpr int kPrepThreads = 256;
-constexpr int kMaxEcc = EXO_KEP_MAX_ECC;
 constexpr int kCoef = EXO_AST_NCOEF;
-
-// the eccentricity grid travels by value in the kernel arguments
-struct EccGrid {
-  int32_t n;
-  double e[kMaxEcc];
-};
 
 // workspace, in doubles: tt[n], then per series the columns pxx, pxy, pyy, qx, qy [5][n], then t_min and per series chi2_0
 struct Layout {
@@ -59,16 +43,7 @@ __global__ __launch_bounds__(kPrepThreads) void astrometric_prepare_kernel(const
   __shared__ double red[kPrepThreads];
   const int64_t b = blockIdx.x, n = L.n;
   const int lane = threadIdx.x;
-  double lo = INFINITY;
-  for (int64_t i = lane; i < n; i += kPrepThreads) lo = fmin(lo, t[i]);
-  red[lane] = lo;
-  __syncthreads();
-  for (int o = kPrepThreads / 2; o > 0; o >>= 1) {
-    if (lane < o) red[lane] = fmin(red[lane], red[lane + o]);
-    __syncthreads();
-  }
-  const double t_min = red[0];
-  __syncthreads();  // (the reduction's array is used again below)
+  const double t_min = block_min(t, n, red);
   const double* re = rho_err + (n_rho_err > 1 ? b : 0) * n;
   const double* te = theta_err + (n_theta_err > 1 ? b : 0) * n;
   double* tt = ws + L.tt();
@@ -91,131 +66,66 @@ __global__ __launch_bounds__(kPrepThreads) void astrometric_prepare_kernel(const
     qy[i] = ay;
     part += fma(x, ax, y * ay);
   }
-  red[lane] = part;
-  __syncthreads();
-  for (int o = kPrepThreads / 2; o > 0; o >>= 1) {
-    if (lane < o) red[lane] += red[lane + o];
-    __syncthreads();
-  }
+  const double chi2_0 = block_sum(part, red);
   if (lane == 0) {
     if (b == 0) ws[L.t_min()] = t_min;
-    ws[L.chi2_0(b)] = red[0];
+    ws[L.chi2_0(b)] = chi2_0;
   }
 }
 
-// what a candidate needs beside the staged epochs
-struct Candidate {
-  double e, se, pe, phi;
-  bool live;
-};
+// the problem of exo_orbit_search.hpp: a tile carries the five columns; a candidate keeps the thirteen sums, all zero at
+// first; its score is the power of the 4 x 4 fit where that has every pivot; of the lane's best the four constants are used
+struct AstrometricProblem {
+  const double* __restrict__ col;  // pxx, pxy, pyy, qx, qy of the series: [5][n]
+  int64_t n;
+  double (*col_s)[kTile];
 
-__device__ __forceinline__ Candidate candidate_of(int c, int n_cand, int n_phase, const double* e_s) {
-  Candidate r;
-  const int j = c / n_phase, k = c - j * n_phase;
-  const double e = c < n_cand ? e_s[j] : -1.0;
-  r.live = c < n_cand && kep::is_candidate(e, k);
-  r.e = r.live ? e : 0.5;
-  r.se = sqrt(1.0 - r.e);
-  r.pe = sqrt(1.0 + r.e);
-  r.phi = (double)k / (double)n_phase;
-  return r;
-}
+  using State = Sums;
+  using Fit = ast::Fit;
+
+  __device__ __forceinline__ void stage(int64_t lo, int i) const {
+    for (int k = 0; k < 5; ++k) col_s[k][i] = col[k * n + lo + i];
+  }
+  __device__ __forceinline__ void walk(State& a, const Candidate& cd, const double* turns_s, int64_t, int len) const {
+    for (int i = 0; i < len; ++i) {
+      double xi, eta;
+      orbit_plane(turns_s[i], cd.phi, cd.e, cd.se, cd.pe, &xi, &eta);
+      accumulate(a, xi, eta, col_s[0][i], col_s[1][i], col_s[2][i], col_s[3][i], col_s[4][i]);
+    }
+  }
+  __device__ __forceinline__ Fit fit(const State& a) const { return ast::fit(a); }
+  __device__ __forceinline__ bool counts(const Fit& r) const { return r.ok; }
+};
 
 // The search and the winner's record.  grid: (frequencies, series); blockDim: 64, 128 or 256.
 __global__ __launch_bounds__(kMaxThreads) void astrometric_kernel(const double* __restrict__ freq, Layout L, EccGrid grid, int32_t n_phase,
                                                                   const double* __restrict__ ws, double* __restrict__ power,
                                                                   int32_t* __restrict__ candidate, double* __restrict__ coef) {
-  __shared__ double turns_s[kTile], pxx_s[kTile], pxy_s[kTile], pyy_s[kTile], qx_s[kTile], qy_s[kTile];
-  __shared__ double e_s[kMaxEcc], red_p[kMaxThreads / kWave];
-  __shared__ int32_t red_c[kMaxThreads / kWave];
-  const int64_t jf = blockIdx.x, n_freq = gridDim.x, b = blockIdx.y, n = L.n;
-  const int lane = threadIdx.x, nt = blockDim.x;
+  __shared__ SearchLds sh;
+  __shared__ double col_s[5][kTile];
+  const int64_t jf = blockIdx.x, n_freq = gridDim.x, b = blockIdx.y;
   const double f = freq[jf];
-  const double* __restrict__ tt = ws + L.tt();
-  const double* __restrict__ pxx = ws + L.col(b, 0);
-  const double* __restrict__ pxy = ws + L.col(b, 1);
-  const double* __restrict__ pyy = ws + L.col(b, 2);
-  const double* __restrict__ qx = ws + L.col(b, 3);
-  const double* __restrict__ qy = ws + L.col(b, 4);
-  const int n_cand = grid.n * n_phase;
-  for (int q = lane; q < grid.n; q += nt) e_s[q] = grid.e[q];
-  __syncthreads();
-
-  // ---- the search: this lane's candidates, ascending, so that a strict > keeps the lowest of equal maxima
-  kep::Best mine = kep::best_init();
-  double ta = NAN, tb = NAN, tf = NAN, tg = NAN;
-  for (int c0 = 0; c0 < n_cand; c0 += nt) {
-    const int c = c0 + lane;
-    const Candidate cd = candidate_of(c, n_cand, n_phase, e_s);
-    Sums a = sums_init();
-    for (int64_t lo = 0; lo < n; lo += kTile) {
-      const int len = (int)(n - lo < kTile ? n - lo : kTile);
-      __syncthreads();  // (every lane is done with the tile before)
-      for (int i = lane; i < len; i += nt) {
-        turns_s[i] = est::ls_phase_turns(f, tt[lo + i]);
-        pxx_s[i] = pxx[lo + i];
-        pxy_s[i] = pxy[lo + i];
-        pyy_s[i] = pyy[lo + i];
-        qx_s[i] = qx[lo + i];
-        qy_s[i] = qy[lo + i];
-      }
-      __syncthreads();
-      if (cd.live) {
-        for (int i = 0; i < len; ++i) {
-          double xi, eta;
-          orbit_plane(turns_s[i], cd.phi, cd.e, cd.se, cd.pe, &xi, &eta);
-          accumulate(a, xi, eta, pxx_s[i], pxy_s[i], pyy_s[i], qx_s[i], qy_s[i]);
-        }
-      }
-    }
-    if (cd.live) {
-      const Fit r = fit(a);
-      if (r.ok) {
-        const int32_t before = mine.candidate;
-        kep::best_take(mine, r.power, c);
-        if (mine.candidate != before) {
-          ta = r.ta;
-          tb = r.tb;
-          tf = r.tf;
-          tg = r.tg;
-        }
-      }
-    }
-  }
-  kep::Best best = mine;
-  for (int o = kWave / 2; o > 0; o >>= 1) {
-    const double p = __shfl_down(best.power, o, kWave);
-    const int32_t c = __shfl_down(best.candidate, o, kWave);
-    kep::best_take(best, p, c);
-  }
-  if (lane % kWave == 0) {
-    red_p[lane / kWave] = best.power;
-    red_c[lane / kWave] = best.candidate;
-  }
-  __syncthreads();
-  best = kep::best_init();
-  for (int i = 0; i < nt / kWave; ++i) kep::best_take(best, red_p[i], red_c[i]);
+  const AstrometricProblem problem = {ws + L.col(b, 0), L.n, col_s};
+  Fit beta;  // (of this lane's best candidate: set where the lane has one)
+  const Best mine = lane_search(problem, sh, grid, n_phase, f, ws + L.tt(), L.n, beta);
+  const Best best = block_best(mine, sh);
 
   // ---- the winner's record: power, candidate, the four constants, the elements, t_periastron and chi2
   const int64_t slot = b * n_freq + jf;
   if (best.candidate == INT32_MAX) {  // (no candidate at this frequency: power 0, the rest NaN)
-    if (lane == 0) {
-      power[slot] = 0.0;
-      candidate[slot] = -1;
-      for (int q = 0; q < kCoef; ++q) coef[slot * kCoef + q] = NAN;
-    }
+    write_no_candidate(0.0, slot, kCoef, power, candidate, coef);
     return;
   }
   if (mine.candidate != best.candidate) return;  // (candidate numbers are unique: one lane is left)
-  const Elements el = campbell(ta, tb, tf, tg);
+  const Elements el = campbell(beta.ta, beta.tb, beta.tf, beta.tg);
   const int k = best.candidate % n_phase;
   double* out = coef + slot * kCoef;
   power[slot] = best.power;
   candidate[slot] = best.candidate;
-  out[0] = ta;
-  out[1] = tb;
-  out[2] = tf;
-  out[3] = tg;
+  out[0] = beta.ta;
+  out[1] = beta.tb;
+  out[2] = beta.tf;
+  out[3] = beta.tg;
   out[4] = el.a_angular;
   out[5] = el.incl;
   out[6] = el.omega;
@@ -224,21 +134,12 @@ __global__ __launch_bounds__(kMaxThreads) void astrometric_kernel(const double* 
   out[9] = ws[L.chi2_0(b)] - 2.0 * best.power;
 }
 
-// lanes per workgroup: of 256, 128 and 64 the count whose passes over the candidates leave the fewest lanes idle (the larger
-// of equals)
-inline int threads_for(int64_t n_cand) {
-  int best = kMaxThreads;
-  for (int nt = kMaxThreads; nt >= kWave; nt /= 2)
-    if ((n_cand + nt - 1) / nt * nt < (n_cand + best - 1) / best * best) best = nt;
-  return best;
-}
-
 }  // namespace
 
 extern "C" {
 
 int64_t exo_astrometric_workspace_bytes(int64_t n, int64_t n_series) {
-  if (n < 1 || n > INT32_MAX || n_series < 1 || n_series > 65535) return -1;
+  if (!series_ok(n, n_series)) return -1;
   return 8 * Layout{n, n_series}.size();
 }
 
@@ -248,16 +149,11 @@ int exo_astrometric_power_f64(const double* t, const double* rho, const double* 
                               int32_t* candidate, double* coef, void* workspace, int64_t workspace_bytes, void* stream) {
   if (n_frequency == 0) return EXO_OK;
   if (!t || !rho || !rho_err || !theta || !theta_err || !frequencies || !ecc || !power || !candidate || !coef || !workspace ||
-      n < 1 || n > INT32_MAX || n_series < 1 || n_series > 65535 || (n_rho_err != 1 && n_rho_err != n_series) ||
-      (n_theta_err != 1 && n_theta_err != n_series) || n_frequency < 0 || n_frequency > INT32_MAX || n_ecc < 1 ||
-      n_ecc > kMaxEcc || n_phase < 1 || n_phase > EXO_KEP_MAX_PHASES)
+      !sizes_ok(n, n_series, n_frequency, n_ecc, n_phase) || (n_rho_err != 1 && n_rho_err != n_series) ||
+      (n_theta_err != 1 && n_theta_err != n_series))
     return EXO_ERR_INVALID_ARGUMENT;
   EccGrid grid = {};
-  grid.n = n_ecc;
-  for (int j = 0; j < n_ecc; ++j) {
-    if (!(ecc[j] >= 0.0 && ecc[j] < 1.0)) return EXO_ERR_INVALID_ARGUMENT;
-    grid.e[j] = ecc[j];
-  }
+  if (!ecc_grid(ecc, n_ecc, &grid)) return EXO_ERR_INVALID_ARGUMENT;
   if (workspace_bytes < exo_astrometric_workspace_bytes(n, n_series)) return EXO_ERR_WORKSPACE;
   const Layout L = {n, n_series};
   double* ws = (double*)workspace;

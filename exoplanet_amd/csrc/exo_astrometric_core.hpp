@@ -4,13 +4,13 @@
 // its pivot floor, and the conversion of the four constants to a_angular, incl, omega, Omega.  Definition: DESIGN.md section
 // 23.  Compiles for the device (exo_astrometric.hip) and, with EXO_HOST_BUILD, for the host (tests/astrometric_harness.cpp
 // checks it against the numpy statement without a GPU).  Every product that is meant to be fused is written as an fma: both
-// builds are compiled with -ffp-contract=off.  The candidates, their numbering and the arg-max are those of the Keplerian
-// periodogram: kep::is_candidate, kep::Best, kep::best_take.
+// builds are compiled with -ffp-contract=off.  The candidates, their numbering and the arg-max: exo_orbit_search.hpp.
 #pragma once
 #include <math.h>
-#include <stdint.h>
 
-#include "exo_keplerian_core.hpp"
+#include "exo_estimators_core.hpp"
+#include "exo_math.hpp"
+#include "exo_orbit_search.hpp"
 
 namespace ast {
 
@@ -23,7 +23,7 @@ constexpr double kPi = 3.141592653589793;
 // axis.  `turns` = ls_phase_turns(f, t - t_min); the phase of periastron comes off in turns, and only then the factor 2 pi.
 // Both are the half-angle forms of exo_math.hpp: no reciprocal, no rounded cos E.  se = sqrt(1 - e), pe = sqrt(1 + e).
 EXO_EST_HD void orbit_plane(double turns, double phi, double e, double se, double pe, double* xi, double* eta) {
-  const exo::KeplerHalf kh = exo::kepler_half(kep::kTwoPi * (turns - phi), e, se, pe);
+  const exo::KeplerHalf kh = exo::kepler_half(orb::kTwoPi * (turns - phi), e, se, pe);
   *xi = fma(kh.X, kh.X, -(kh.Y * kh.Y));
   *eta = 2.0 * kh.X * kh.Y;
 }

@@ -1,7 +1,8 @@
-// exo_estimators_launch.hpp -- what the three translation units of the estimators (exo_estimators.hip, exo_detrend.hip,
-// exo_timing.hip) share on the host side of a launch: the status of the launches just enqueued, the widest-window kernel
-// of the two plans, and the permission a kernel needs for more than 64 KiB of dynamic LDS.  Everything sits in an unnamed
-// namespace: no device code crosses translation units, so each unit that includes this gets a copy of its own.
+// exo_estimators_launch.hpp -- what the six translation units of the estimators (exo_estimators.hip, exo_detrend.hip,
+// exo_trend.hip, exo_timing.hip, exo_keplerian.hip, exo_astrometric.hip) share on the host side of a launch: the status of
+// the launches just enqueued, the widest-window kernel of the two plans, and the permission a kernel needs for more than
+// 64 KiB of dynamic LDS.  Everything sits in an unnamed namespace: no device code crosses translation units, so each unit
+// that includes this gets a copy of its own.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

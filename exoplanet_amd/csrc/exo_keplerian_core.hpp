@@ -1,24 +1,18 @@
 // exo_keplerian_core.hpp -- the per-candidate arithmetic of the Keplerian periodogram of a radial-velocity series
 // (exoplanet_amd/estimators.py: keplerian_power, keplerian_estimator): one epoch's true anomaly and its contribution to a
-// candidate's sums, the fold of one instrument's segment, the power and the coefficients from the centred sums, and the
-// comparison of the arg-max.  Definition: DESIGN.md section 22.  Compiles for the device (exo_keplerian.hip) and, with
-// EXO_HOST_BUILD, for the host (tests/keplerian_harness.cpp checks it against the numpy statement without a GPU).  Every
-// product that is meant to be fused is written as an fma: both builds are compiled with -ffp-contract=off.
+// candidate's sums, the fold of one instrument's segment, and the power and the coefficients from the centred sums.  The
+// candidates, their numbering and the arg-max: exo_orbit_search.hpp.  Definition: DESIGN.md section 22.  Compiles for the
+// device (exo_keplerian.hip) and, with EXO_HOST_BUILD, for the host (tests/keplerian_harness.cpp checks it against the numpy
+// statement without a GPU).  Every product that is meant to be fused is written as an fma: both builds are compiled with
+// -ffp-contract=off.
 #pragma once
-#include <limits.h>
 #include <math.h>
-#include <stdint.h>
 
-#include "../../include/exoplanet_amd.h"
 #include "exo_estimators_core.hpp"
 #include "exo_math.hpp"
+#include "exo_orbit_search.hpp"
 
 namespace kep {
-
-constexpr double kTwoPi = 6.283185307179586;
-
-// a candidate's number j * n_phase + k, phase fastest; where e_j == 0 only k = 0 is one (every phase is the same model there)
-EXO_EST_HD bool is_candidate(double e, int k) { return e >= 0.0 && e < 1.0 && (e != 0.0 || k == 0); }
 
 // The five sums of a candidate over the epochs, raw while a segment is open and centred once it is folded:
 // sum w y sin nu, w y cos nu, w sin^2 nu, w cos^2 nu, w cos nu sin nu ...
@@ -37,7 +31,7 @@ struct Segment {
 // off in turns, and only then the factor 2 pi.  The half-angle pair (X, Y) of the solver gives den = X^2 + Y^2 = 1 - e cos E,
 // den cos nu = X^2 - Y^2, den sin nu = 2 X Y (exo_rv_core.hpp): no rounded cos E anywhere.  se = sqrt(1 - e), pe = sqrt(1 + e).
 EXO_EST_HD void true_anomaly(double turns, double phi, double e, double se, double pe, double* sn, double* cs) {
-  const exo::KeplerHalf kh = exo::kepler_half(kTwoPi * (turns - phi), e, se, pe);
+  const exo::KeplerHalf kh = exo::kepler_half(orb::kTwoPi * (turns - phi), e, se, pe);
   const double X2 = kh.X * kh.X, Y2 = kh.Y * kh.Y;
   const double iden = exo::fast_rcp(X2 + Y2);  // (1 - e <= X^2 + Y^2 <= 1 + e: well scaled)
   *cs = (X2 - Y2) * iden;
@@ -89,19 +83,6 @@ EXO_EST_HD Fit fit(const Sums& a, double W) {
 // y - A cos nu - B sin nu
 EXO_EST_HD double constant(double Wk, double Yk, const Segment& g, double A, double B) {
   return (Yk - A * g.c - B * g.s) / Wk - (A * g.c0 + B * g.s0);
-}
-
-// the arg-max as one value: a larger power wins, an equal one only with a lower candidate number, NaN never
-struct Best {
-  double power;
-  int32_t candidate;
-};
-EXO_EST_HD Best best_init() { return Best{-INFINITY, INT32_MAX}; }
-EXO_EST_HD void best_take(Best& a, double power, int32_t candidate) {
-  if (power > a.power || (power == a.power && candidate < a.candidate)) {
-    a.power = power;
-    a.candidate = candidate;
-  }
 }
 
 }  // namespace kep

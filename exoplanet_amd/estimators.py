@@ -424,42 +424,54 @@ def keplerian_power(t, y, yerr=None, *, frequencies, ecc=None, n_phase=64, instr
     n_given = t.shape[-1] if hasattr(t, "shape") and len(t.shape) else 0
     order, offsets = _instrument_segments(instrument, int(n_given))
     t, y, yerr, batched = _device_series(t, y, yerr)
-    f_host, f_dev = _grid(frequencies, "frequencies", t.device)
-    B, N, F, n_inst = y.shape[0], y.shape[1], f_host.size, offsets.size - 1
+    _, f_dev = _grid(frequencies, "frequencies", t.device)
+    B, N, n_inst = y.shape[0], y.shape[1], offsets.size - 1
     t_min = t.min()
     if order is not None:                                      # the epochs by instrument (the sums need no time order)
         order = torch.as_tensor(order, device=t.device)
         t, y = t[order].contiguous(), y[:, order].contiguous()
         yerr = None if yerr is None else yerr[:, order].contiguous()
+    lead = (t.data_ptr(), y.data_ptr(), 0 if yerr is None else yerr.data_ptr(), 0 if yerr is None else yerr.shape[0], N, B,
+            offsets.ctypes.data_as(ctypes.c_void_p), n_inst)
+
+    def fit(cand, c, e, coef):
+        # the elements of the winner: A = K cos w, B = -K sin w, c_k = zero_point_k + e A
+        phi = (c % n_phase).to(torch.float64) / n_phase
+        t_p = torch.where(cand >= 0, t_min + phi / f_dev, torch.full_like(e, float("nan")))
+        A, Bs = coef[..., 0], coef[..., 1]
+        return dict(ecc=e, omega=torch.atan2(-Bs, A), t_periastron=t_p, K=torch.hypot(A, Bs),
+                    zero_point=coef[..., 2:] - (e * A)[..., None], candidate=cand.to(torch.int64))
+
+    return _orbit_search("keplerian", t, lead, (B, N), f_dev, e_host, n_phase, 2 + n_inst, batched, fit if return_fit else None)
+
+
+def _orbit_search(name, t, lead, shape, f_dev, e_host, n_phase, n_coef, batched, fit):
+    """What :func:`keplerian_power` and :func:`astrometric_power` do alike around ``exo_<name>_power_f64``: the outputs, the
+    workspace and the call (``lead``: the entry's arguments before the frequencies; ``shape``: (B, N)); then the power, (F,)
+    or (B, F) -- with ``fit`` also ``fit(candidate, c, ecc, coef)`` of the winners' records, unbatched alike: ``candidate``
+    int32 (-1: none), ``c`` the same clamped to the grid (int64), ``ecc`` the winner's eccentricity, NaN where there is none."""
+    (B, N), F = shape, f_dev.numel()
     power = torch.empty((B, F), dtype=torch.float64, device=t.device)
     cand = torch.empty((B, F), dtype=torch.int32, device=t.device)
-    coef = torch.empty((B, F, 2 + n_inst), dtype=torch.float64, device=t.device)
+    coef = torch.empty((B, F, n_coef), dtype=torch.float64, device=t.device)
     if F:
         lib = _lib.load()
-        nbytes = lib.exo_keplerian_workspace_bytes(N, B)
+        nbytes = getattr(lib, f"exo_{name}_workspace_bytes")(N, B)
         if nbytes < 0:
-            raise ValueError("keplerian_power: invalid sizes")
+            raise ValueError(f"{name}_power: invalid sizes")
         ws = _workspace(nbytes, t.device)
-        _lib.check(lib.exo_keplerian_power_f64(t.data_ptr(), y.data_ptr(), 0 if yerr is None else yerr.data_ptr(),
-                                               0 if yerr is None else yerr.shape[0], N, B,
-                                               offsets.ctypes.data_as(ctypes.c_void_p), n_inst, f_dev.data_ptr(), F,
-                                               e_host.ctypes.data_as(ctypes.c_void_p), e_host.size, n_phase, power.data_ptr(),
-                                               cand.data_ptr(), coef.data_ptr(), ws.data_ptr(), ws.numel() * 8, _stream(t)),
-                   "exo_keplerian_power_f64")
-    if not return_fit:
+        entry = f"exo_{name}_power_f64"
+        _lib.check(getattr(lib, entry)(*lead, f_dev.data_ptr(), F, e_host.ctypes.data_as(ctypes.c_void_p), e_host.size, n_phase,
+                                       power.data_ptr(), cand.data_ptr(), coef.data_ptr(), ws.data_ptr(), ws.numel() * 8, _stream(t)),
+                   entry)
+    if fit is None:
         return power if batched else power[0]
-    # the elements of the winner: A = K cos w, B = -K sin w, c_k = zero_point_k + e A
-    nan = torch.full_like(power, float("nan"))
-    found = cand >= 0
     c = cand.clamp(min=0).to(torch.int64)
-    e = torch.where(found, _grid(e_host, "ecc", t.device)[1][c // n_phase], nan)
-    phi = (c % n_phase).to(torch.float64) / n_phase
-    A, Bs = coef[..., 0], coef[..., 1]
-    fit = dict(ecc=e, omega=torch.atan2(-Bs, A), t_periastron=torch.where(found, t_min + phi / f_dev, nan), K=torch.hypot(A, Bs),
-               zero_point=coef[..., 2:] - (e * A)[..., None], candidate=cand.to(torch.int64))
+    e = torch.where(cand >= 0, _grid(e_host, "ecc", t.device)[1][c // n_phase], torch.full_like(power, float("nan")))
+    out = fit(cand, c, e, coef)
     if not batched:
-        power, fit = power[0], {k: v[0] for k, v in fit.items()}
-    return power, fit
+        power, out = power[0], {k: v[0] for k, v in out.items()}
+    return power, out
 
 
 AST_NCOEF = 10          # EXO_AST_NCOEF
@@ -508,34 +520,20 @@ def astrometric_power(t, rho, rho_err, theta, theta_err, *, frequencies, ecc=Non
         raise ValueError(f"theta must have the shape of rho, got {tuple(theta.shape)}")
     rho_err = _astrometric_error("rho_err", rho_err, rho.shape, t.device)
     theta_err = _astrometric_error("theta_err", theta_err, rho.shape, t.device)
-    f_host, f_dev = _grid(frequencies, "frequencies", t.device)
-    B, N, F = rho.shape[0], rho.shape[1], f_host.size
-    power = torch.empty((B, F), dtype=torch.float64, device=t.device)
-    cand = torch.empty((B, F), dtype=torch.int32, device=t.device)
-    coef = torch.empty((B, F, AST_NCOEF), dtype=torch.float64, device=t.device)
-    if F:
-        lib = _lib.load()
-        nbytes = lib.exo_astrometric_workspace_bytes(N, B)
-        if nbytes < 0:
-            raise ValueError("astrometric_power: invalid sizes")
-        ws = _workspace(nbytes, t.device)
-        _lib.check(lib.exo_astrometric_power_f64(t.data_ptr(), rho.data_ptr(), rho_err.data_ptr(), rho_err.shape[0], theta.data_ptr(),
-                                                 theta_err.data_ptr(), theta_err.shape[0], N, B, f_dev.data_ptr(), F,
-                                                 e_host.ctypes.data_as(ctypes.c_void_p), e_host.size, n_phase, power.data_ptr(),
-                                                 cand.data_ptr(), coef.data_ptr(), ws.data_ptr(), ws.numel() * 8, _stream(t)),
-                   "exo_astrometric_power_f64")
-    if not return_fit:
-        return power if batched else power[0]
-    c = cand.clamp(min=0).to(torch.int64)
-    e = torch.where(cand >= 0, _grid(e_host, "ecc", t.device)[1][c // n_phase], torch.full_like(power, float("nan")))
-    fit = dict(candidate=cand.to(torch.int64), ecc=e, **{k: coef[..., i] for i, k in enumerate(ASTROMETRIC_FIT)})
-    if parallax is not None:
-        from .orbits.constants import au_per_R_sun
+    _, f_dev = _grid(frequencies, "frequencies", t.device)
+    B, N = rho.shape
+    lead = (t.data_ptr(), rho.data_ptr(), rho_err.data_ptr(), rho_err.shape[0], theta.data_ptr(), theta_err.data_ptr(),
+            theta_err.shape[0], N, B)
 
-        fit["a"] = fit["a_angular"] / (parallax * au_per_R_sun)
-    if not batched:
-        power, fit = power[0], {k: v[0] for k, v in fit.items()}
-    return power, fit
+    def fit(cand, c, e, coef):
+        out = dict(candidate=cand.to(torch.int64), ecc=e, **{k: coef[..., i] for i, k in enumerate(ASTROMETRIC_FIT)})
+        if parallax is not None:
+            from .orbits.constants import au_per_R_sun
+
+            out["a"] = out["a_angular"] / (parallax * au_per_R_sun)
+        return out
+
+    return _orbit_search("astrometric", t, lead, (B, N), f_dev, e_host, n_phase, AST_NCOEF, batched, fit if return_fit else None)
 
 
 # ---- detrending: running median, MAD and biweight location --------------------------------------------------------------------
@@ -1094,14 +1092,27 @@ def tls_estimator(x, y, yerr=None, duration=0.2, min_period=None, max_period=Non
     return results
 
 
-def lomb_scargle_estimator(x, y, yerr=None, min_period=None, max_period=None, filter_period=None, max_peaks=2, **kwargs):
-    """Estimate the period of a series from its Lomb-Scargle periodogram on the automatic grid (``kwargs``: those of
-    :func:`lomb_scargle_autofrequency`).  Returns ``periodogram = (freq, power / len(x))`` and ``peaks``, found after the
-    optional high-pass weight ``1 / sqrt(1 + (f0 / f)^6)``, ``f0 = 1 / filter_period``."""
+def _period_bounds(kwargs, min_period, max_period):
+    """``min_period`` / ``max_period`` into the keywords of :func:`lomb_scargle_autofrequency`, in place"""
     if min_period is not None:
         kwargs["maximum_frequency"] = 1.0 / min_period
     if max_period is not None:
         kwargs["minimum_frequency"] = 1.0 / max_period
+
+
+def _grid_maxima(peaks, max_peaks, freq, power):
+    """every peak of :func:`find_peaks` with the index ``i`` of the grid's local maximum itself, where a search's fit is read"""
+    for peak in peaks if max_peaks else [peaks]:
+        i = peak["index"] - 1                 # (find_peaks counts from one)
+        assert 1 <= i < len(freq) - 1 and power[i] > power[i - 1] and power[i] > power[i + 1], peak
+        yield peak, i
+
+
+def lomb_scargle_estimator(x, y, yerr=None, min_period=None, max_period=None, filter_period=None, max_peaks=2, **kwargs):
+    """Estimate the period of a series from its Lomb-Scargle periodogram on the automatic grid (``kwargs``: those of
+    :func:`lomb_scargle_autofrequency`).  Returns ``periodogram = (freq, power / len(x))`` and ``peaks``, found after the
+    optional high-pass weight ``1 / sqrt(1 + (f0 / f)^6)``, ``f0 = 1 / filter_period``."""
+    _period_bounds(kwargs, min_period, max_period)
     dev = _device_of(x, y)
     xh = _np(x)
     freq = lomb_scargle_autofrequency(xh, **kwargs)
@@ -1121,10 +1132,7 @@ def keplerian_estimator(x, y, yerr=None, min_period=None, max_period=None, max_p
     K, zero_point`` and ``power`` at the grid frequency of the local maximum itself (``power`` as in ``periodogram``;
     ``zero_point`` a float, or with ``instrument`` a list of one float per instrument).  They go straight into
     ``KeplerianOrbit(period=, ecc=, omega=, t_periastron=)`` and ``rv_log_likelihood(K=, zero_point=, instrument=)``."""
-    if min_period is not None:
-        kwargs["maximum_frequency"] = 1.0 / min_period
-    if max_period is not None:
-        kwargs["minimum_frequency"] = 1.0 / max_period
+    _period_bounds(kwargs, min_period, max_period)
     dev = _device_of(x, y)
     xh = _np(x)
     freq = lomb_scargle_autofrequency(xh, **kwargs)
@@ -1135,9 +1143,7 @@ def keplerian_estimator(x, y, yerr=None, min_period=None, max_period=None, max_p
     power = _np(power) / len(xh)
     fit = {k: _np(v) for k, v in fit.items()}
     peaks = find_peaks(freq, power, max_peaks=max_peaks)
-    for peak in peaks if max_peaks else [peaks]:
-        i = peak["index"] - 1                 # (find_peaks counts from one: this is the grid's local maximum itself)
-        assert 1 <= i < len(freq) - 1 and power[i] > power[i - 1] and power[i] > power[i + 1], peak
+    for peak, i in _grid_maxima(peaks, max_peaks, freq, power):
         peak.update({k: float(fit[k][i]) for k in KEPLERIAN_FIT[:4]}, power=float(power[i]))
         peak["zero_point"] = float(fit["zero_point"][i, 0]) if instrument is None else [float(v) for v in fit["zero_point"][i]]
     return dict(periodogram=(freq, power), peaks=peaks)
@@ -1179,9 +1185,7 @@ def astrometric_estimator(t, rho, rho_err, theta, theta_err, min_period=None, ma
     fit = {k: _np(v) for k, v in fit.items()}
     peaks = find_peaks(freq, power, max_peaks=max_peaks)
     keys = ("ecc", "t_periastron", "omega", "Omega", "incl", "a_angular") + (("a",) if parallax is not None else ()) + ("chi2",)
-    for peak in peaks if max_peaks else [peaks]:
-        i = peak["index"] - 1                 # (find_peaks counts from one: this is the grid's local maximum itself)
-        assert 1 <= i < len(freq) - 1 and power[i] > power[i - 1] and power[i] > power[i + 1], peak
+    for peak, i in _grid_maxima(peaks, max_peaks, freq, power):
         peak.update({k: float(fit[k][i]) for k in keys}, period_refined=peak["period"], period=float(1.0 / freq[i]),
                     power=float(power[i]))
     return dict(periodogram=(freq, power), peaks=peaks)

@@ -3,8 +3,10 @@
 // kernel of exo_astrometric.hip walks them; and the Campbell conversion on its own.
 #define EXO_HOST_BUILD
 #include "../exoplanet_amd/csrc/exo_astrometric_core.hpp"
+#include "orbit_lanes.hpp"
 
 using namespace ast;
+using namespace orb;
 
 extern "C" {
 
@@ -21,29 +23,23 @@ void harness_astrometric(const double* tt, const double* pxx, const double* pxy,
   const int n_cand = n_ecc * n_phase;
   Fit* fits = new Fit[n_cand];
   for (int c = 0; c < n_cand; ++c) {
-    const int j = c / n_phase, k = c % n_phase;
+    const Candidate cd = candidate_of(c, n_cand, n_phase, ecc);
     table[c] = -INFINITY;
     pivot[c] = NAN;
     fits[c].ok = false;
-    if (!kep::is_candidate(ecc[j], k)) continue;
-    const double e = ecc[j], se = sqrt(1.0 - e), pe = sqrt(1.0 + e);
+    if (!cd.live) continue;
     Sums a = sums_init();
     for (int32_t i = 0; i < n; ++i) {
       double xi, eta;
-      orbit_plane(turns[i], (double)k / (double)n_phase, e, se, pe, &xi, &eta);
+      orbit_plane(turns[i], cd.phi, cd.e, cd.se, cd.pe, &xi, &eta);
       accumulate(a, xi, eta, pxx[i], pxy[i], pyy[i], qx[i], qy[i]);
     }
     fits[c] = fit(a);
     pivot[c] = fits[c].pivot;
     if (fits[c].ok) table[c] = fits[c].power;
   }
-  kep::Best best = kep::best_init();
-  for (int lane = n_lane - 1; lane >= 0; --lane) {
-    kep::Best mine = kep::best_init();
-    for (int c = lane; c < n_cand; c += n_lane)
-      if (fits[c].ok) kep::best_take(mine, table[c], c);
-    kep::best_take(best, mine.power, mine.candidate);
-  }
+  const Best best = lanes_best(
+      n_cand, n_lane, [&](int c) { return fits[c].ok; }, [&](int c) { return table[c]; });
   record[0] = 0.0;
   record[1] = -1.0;
   for (int q = 2; q < 10; ++q) record[q] = NAN;

@@ -299,6 +299,11 @@ def shapes():
         "one frequency": (series(40, 16), F8[3:4], [0.0, 0.45, 0.8], 16),
         "scalar errors": (dict(series(40, 17), rho_err=0.01, theta_err=0.02), F8, [0.0, 0.45, 0.8], 16),
         "isotropic weights": (iso, F8, [0.0, 0.45, 0.8], 16),
+        # (what the search shared with the Keplerian one owns, csrc/exo_orbit_search.hpp: 128 lanes of which 63 have no
+        # candidate; 64 lanes and three passes; three tiles with a short last one)
+        "65 candidates": (series(40, 16), F8, [0.15, 0.3, 0.45, 0.6, 0.75], 13),
+        "192 candidates": (series(40, 16), F8, [0.2, 0.5, 0.8], 64),
+        "three tiles": (series(2 * TILE + 5, 18), F8, [0.0, 0.45, 0.8], 8),
     }
     return out
 

@@ -3,21 +3,22 @@
 // them; and the Lomb-Scargle path of exo_estimators_core.hpp on the same columns, which ecc = [0] must reproduce.
 #define EXO_HOST_BUILD
 #include "../exoplanet_amd/csrc/exo_keplerian_core.hpp"
+#include "orbit_lanes.hpp"
 
 using namespace kep;
+using namespace orb;
 
 namespace {
 
 // one candidate over the epochs in order, segment by segment; seg_g (or null) receives the segments as they were folded
 Sums walk(const double* turns, const double* w, const double* wy, const int32_t* off, int n_inst, const double* Wk, const double* Yk,
-          double e, double phi, Segment* seg_g) {
+          const Candidate& cd, Segment* seg_g) {
   Sums a = {0.0, 0.0, 0.0, 0.0, 0.0};
   Segment g = {0.0, 0.0, 0.0, 0.0};
-  const double se = sqrt(1.0 - e), pe = sqrt(1.0 + e);
   for (int k = 0; k < n_inst; ++k) {
     for (int32_t i = off[k]; i < off[k + 1]; ++i) {
       double sn, cs;
-      true_anomaly(turns[i], phi, e, se, pe, &sn, &cs);
+      true_anomaly(turns[i], cd.phi, cd.e, cd.se, cd.pe, &sn, &cs);
       accumulate(a, g, i == off[k], w[i], wy[i], sn, cs);
     }
     if (seg_g) seg_g[k] = g;
@@ -47,24 +48,16 @@ void harness_keplerian(const double* tt, const double* w, const double* wy, int3
   }
   const int n_cand = n_ecc * n_phase;
   for (int c = 0; c < n_cand; ++c) {
-    const int j = c / n_phase, k = c % n_phase;
-    table[c] = is_candidate(ecc[j], k)
-                   ? fit(walk(turns, w, wy, off, n_inst, Wk, Yk, ecc[j], (double)k / (double)n_phase, nullptr), W).power
-                   : -INFINITY;
+    const Candidate cd = candidate_of(c, n_cand, n_phase, ecc);
+    table[c] = cd.live ? fit(walk(turns, w, wy, off, n_inst, Wk, Yk, cd, nullptr), W).power : -INFINITY;
   }
-  Best best = best_init();
-  for (int lane = n_lane - 1; lane >= 0; --lane) {
-    Best mine = best_init();
-    for (int c = lane; c < n_cand; c += n_lane)
-      if (is_candidate(ecc[c / n_phase], c % n_phase)) best_take(mine, table[c], c);
-    best_take(best, mine.power, mine.candidate);
-  }
+  const Best best = lanes_best(
+      n_cand, n_lane, [&](int c) { return candidate_of(c, n_cand, n_phase, ecc).live; }, [&](int c) { return table[c]; });
   record[0] = best.power;
   record[1] = best.candidate == INT32_MAX ? -1.0 : (double)best.candidate;
   for (int q = 2; q < 4 + n_inst; ++q) record[q] = NAN;
   if (best.candidate != INT32_MAX) {
-    const int j = best.candidate / n_phase, k = best.candidate % n_phase;
-    const Fit r = fit(walk(turns, w, wy, off, n_inst, Wk, Yk, ecc[j], (double)k / (double)n_phase, seg_g), W);
+    const Fit r = fit(walk(turns, w, wy, off, n_inst, Wk, Yk, candidate_of(best.candidate, n_cand, n_phase, ecc), seg_g), W);
     record[0] = r.power;
     record[2] = r.A;
     record[3] = r.B;

@@ -24,8 +24,8 @@ def harness():
     os.makedirs(out, exist_ok=True)
     so = os.path.join(out, "astrometric_harness.so")
     csrc = os.path.join(ROOT, "exoplanet_amd", "csrc")
-    srcs = [os.path.join(ROOT, "tests", "astrometric_harness.cpp")] + [
-        os.path.join(csrc, h) for h in ("exo_astrometric_core.hpp", "exo_keplerian_core.hpp", "exo_estimators_core.hpp", "exo_math.hpp")]
+    srcs = [os.path.join(ROOT, "tests", "astrometric_harness.cpp"), os.path.join(ROOT, "tests", "orbit_lanes.hpp")] + [
+        os.path.join(csrc, h) for h in ("exo_astrometric_core.hpp", "exo_orbit_search.hpp", "exo_estimators_core.hpp", "exo_math.hpp")]
     if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
         subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-shared", "-fPIC", "-o", so, srcs[0]], check=True)
     lib = ctypes.CDLL(so)

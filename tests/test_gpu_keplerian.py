@@ -161,13 +161,15 @@ def test_elements_go_straight_into_the_orbit_and_the_likelihood():
 
 # ---- 5: shapes where the kernel can go wrong ------------------------------------------------------------------------------------
 
-def series(n, n_inst=1, seed=11, single=False):
+def series(n, n_inst=1, seed=11, single=False, first=None):
     rs = np.random.RandomState(seed)
     t = np.sort(rs.uniform(0, 120, n))
     inst = rs.randint(0, n_inst, n) if n_inst > 1 else None
     if single:                                               # the last instrument owns one epoch only
         inst = np.arange(n) % (n_inst - 1)
         inst[n // 2] = n_inst - 1
+    if first is not None:                                    # the first of two instruments owns exactly `first` epochs
+        inst = (np.arange(n) >= first).astype(np.int64)
     err = rs.uniform(0.5, 2.0, n)
     zp = 3.0 * rs.randn(n_inst)
     y = O.rv_model(t, 9.7, 0.45, 0.7, 12.0, 3.1, zp, inst) + err * rs.randn(n)
@@ -185,6 +187,13 @@ SHAPES = {
     "two candidates per lane": (series(40, 2), F8, [0.1, 0.2, 0.3, 0.4, 0.5, 0.6, 0.7, 0.8], 64),
     "eight instruments, one of a single epoch": (series(40, 8, single=True), F8, [0.0, 0.45], 16),
     "one frequency": (series(40, 2), F8[3:4], [0.0, 0.45, 0.8], 16),
+    # (what the search shared with the astrometric one owns, csrc/exo_orbit_search.hpp: 128 lanes of which 63 have no candidate;
+    # 64 lanes and three passes; three tiles with a short last one -- a segment folded at a tile's last epoch, and one that
+    # stays open across two tile boundaries)
+    "65 candidates": (series(40, 2), F8, [0.15, 0.3, 0.45, 0.6, 0.75], 13),
+    "192 candidates": (series(40, 2), F8, [0.2, 0.5, 0.8], 64),
+    "three tiles, the first instrument one tile exactly": (series(2 * TILE + 5, 2, first=TILE), F8, [0.0, 0.45, 0.8], 8),
+    "three tiles, one instrument": (series(2 * TILE + 5), F8, [0.0, 0.45, 0.8], 8),
 }
 
 
