@@ -2301,3 +2301,41 @@ def chain_diagnostics(x_split, x_full, n_half, check_every=4, timings=None):
     if timings is not None:
         timings["lag_blocks"] = used
     return out
+
+
+# ---- quantiles along the strided axis (exo_column_quantiles_f64; the definition is stated in exoplanet_amd/predictive.py) ----------
+QUANTILE_MAX_Q = 16   # include/exoplanet_amd.h EXO_QUANTILE_MAX_Q
+
+
+def column_quantiles(values, num, den, return_count=False):
+    """Per column of ``values`` (S, N) -- float64 on a ROCm device, last axis contiguous, any row stride >= N (no copy) -- the
+    quantiles at the exact fractions ``num[q] / den[q]`` (whole numbers, 0 <= num <= den <= 1e9) of its values that are not
+    NaN: (Q, N), and with ``return_count`` the int32 (N,) number of those values.  Selection by counting passes in the
+    library: no sort, no copy of ``values``.  More than QUANTILE_MAX_Q fractions go in groups of that many."""
+    if not isinstance(values, torch.Tensor) or values.dim() != 2:
+        raise ValueError("values must be a tensor of shape (S, N)")
+    if not values.is_cuda:
+        _dev(values, "values")
+    if values.dtype != torch.float64:
+        raise TypeError("values must be float64")
+    S, N = (int(v) for v in values.shape)
+    num, den = [int(v) for v in num], [int(v) for v in den]
+    if len(num) != len(den) or not num:
+        raise ValueError("num and den must be two lists of one length, at least one fraction")
+    if any(b < 1 or b > 10 ** 9 or a < 0 or a > b for a, b in zip(num, den)):
+        raise ValueError("a fraction num / den needs 0 <= num <= den <= 1e9")
+    if S >= 2 ** 31:
+        raise ValueError("at most 2^31 - 1 rows")
+    values = values.detach()
+    if (N > 1 and values.stride(1) != 1) or (S > 1 and values.stride(0) < N):
+        values = values.contiguous()
+    stride = int(values.stride(0)) if S > 1 else N
+    dev, Q = values.device, len(num)
+    out = torch.empty((Q, N), dtype=torch.float64, device=dev)
+    count = torch.empty(N, dtype=torch.int32, device=dev) if return_count else None
+    for lo in range(0, Q, QUANTILE_MAX_Q):
+        n_q = min(QUANTILE_MAX_Q, Q - lo)
+        a, b = (ctypes.c_int64 * n_q)(*num[lo:lo + n_q]), (ctypes.c_int64 * n_q)(*den[lo:lo + n_q])
+        _call("exo_column_quantiles_f64", dev, _ptr(values), S, N, stride, ctypes.addressof(a), ctypes.addressof(b), n_q,
+              _ptr(out[lo:lo + n_q]), _ptr(count) if lo == 0 else 0, _stream(values))
+    return (out, count) if return_count else out

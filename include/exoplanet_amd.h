@@ -57,7 +57,7 @@ extern "C" {
  *     caller breaks: exo_tls_power_f64; exo_location_windows_f64, exo_running_location_f64, EXO_LOCATION_*;
  *     exo_timing_windows_f64, exo_transit_timing_f64, EXO_TIMING_*; exo_running_trend_f64, EXO_TREND_MAX_WINDOW;
  *     exo_keplerian_workspace_bytes, exo_keplerian_power_f64, EXO_KEP_*; exo_astrometric_workspace_bytes,
- *     exo_astrometric_power_f64, EXO_AST_NCOEF.) */
+ *     exo_astrometric_power_f64, EXO_AST_NCOEF; exo_column_quantiles_f64, EXO_QUANTILE_MAX_Q.) */
 #define EXO_ABI_VERSION 21
 int32_t exo_abi_version(void);
 
@@ -1277,6 +1277,25 @@ int exo_diag_autocov_f64(const double* sets, int64_t n_param, int64_t n_half, in
                          void* workspace, int64_t workspace_bytes, void* stream);
 int exo_diag_finish_f64(int64_t n_param, int64_t n_half, int64_t n_len, int64_t block, const double* moments, double* out,
                         int32_t* done, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* -------------------------------------------------------------------------
+ * Quantiles along the strided axis of an array of curves: the posterior bands of a model over a trace's draws
+ * (exoplanet_amd/predictive.py).  x: n_rows rows of n_cols doubles, row_stride >= n_cols doubles apart
+ * (the last axis contiguous), on the device.  For every column and every q < n_q (1 .. EXO_QUANTILE_MAX_Q), with the
+ * fraction num[q] / den[q] (HOST arrays, read before the launch; 0 <= num <= den, 1 <= den <= 1e9):
+ *   the m values of the column that are not NaN take part; m = 0: NaN.  Position (m - 1) num / den = lo + rem / den in whole
+ *   numbers; rem = 0: x_(lo), the lo-th smallest, untouched; otherwise x_(lo) + (rem / den) (x_(lo+1) - x_(lo)), these four
+ *   operations in this order, none fused.  An order statistic is a NUMBER: a zero of either sign is +0.
+ * out [n_q][n_cols]; n_valid [n_cols] (int32, or NULL) = m.  Selection by counting passes over the column: no sort, no
+ * workspace, no atomics on floating-point numbers; kernels only, no host synchronisation, bit-reproducible, capturable.
+ * EXO_ERR_INVALID_ARGUMENT, before any launch: negative sizes, n_rows >= 2^31, n_q > EXO_QUANTILE_MAX_Q, row_stride < n_cols,
+ * a null x (with n_rows > 0), num, den or out, den <= 0 or > 1e9, num outside [0, den].  n_cols == 0 or n_q == 0: EXO_OK,
+ * nothing launched (sizes are checked first).  n_rows == 0: NaN and m = 0 everywhere.  (Added without a new ABI number: no
+ * caller breaks.)
+ * ------------------------------------------------------------------------- */
+#define EXO_QUANTILE_MAX_Q 16
+int exo_column_quantiles_f64(const double* x, int64_t n_rows, int64_t n_cols, int64_t row_stride, const int64_t* num,
+                             const int64_t* den, int n_q, double* out, int32_t* n_valid, void* stream);
 
 #ifdef __cplusplus
 }
