@@ -227,6 +227,8 @@ _SIGNATURES = {
     "exo_diag_finish_f64": (ctypes.c_int, [_i64, _i64, _i64, _i64, _c_dp, _c_dp, _c_dp, _c_dp, _i64, _c_dp]),
     # x, n_rows, n_cols, row_stride, num (host), den (host), n_q, out, n_valid, stream
     "exo_column_quantiles_f64": (ctypes.c_int, [_c_dp, _i64, _i64, _i64, _c_dp, _c_dp, _i32, _c_dp, _c_dp, _c_dp]),
+    # x, n_rows, n_cols, row_stride, n_tail_max, out_elpd, out_k, out_lppd, out_var, out_n_tail, stream
+    "exo_column_psis_f64": (ctypes.c_int, [_c_dp, _i64, _i64, _i64, _i32, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp]),
     "exo_sho_coefficients_f64": (ctypes.c_int, [_c_dp, _c_dp, _c_dp, _u32, ctypes.c_double, _i64, _c_dp, _c_dp, _c_dp]),
     "exo_sho_coefficients_vjp_f64": (ctypes.c_int, [_c_dp, _c_dp, _c_dp, _u32, ctypes.c_double, _i64, _c_dp, _c_dp, _c_dp,
                                                     _c_dp, _c_dp]),

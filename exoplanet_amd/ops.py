@@ -2339,3 +2339,36 @@ def column_quantiles(values, num, den, return_count=False):
         _call("exo_column_quantiles_f64", dev, _ptr(values), S, N, stride, ctypes.addressof(a), ctypes.addressof(b), n_q,
               _ptr(out[lo:lo + n_q]), _ptr(count) if lo == 0 else 0, _stream(values))
     return (out, count) if return_count else out
+
+
+# ---- PSIS-LOO and WAIC per column (exo_column_psis_f64; the definition is stated in exoplanet_amd/comparison.py) --------------------
+PSIS_MAX_TAIL = 1024   # include/exoplanet_amd.h EXO_PSIS_MAX_TAIL
+
+
+def column_psis(values, n_tail_max):
+    """Per column of ``values`` (S, N) -- pointwise log-likelihoods, float64 on a ROCm device, last axis contiguous, any row
+    stride >= N (no copy) -- the PSIS leave-one-out density, the Pareto k, the lppd, the variance over the draws and the
+    length of the fitted tail, with the tail's largest length ``n_tail_max`` = M (1 .. PSIS_MAX_TAIL): a dict of (N,) tensors
+    "elpd", "k", "lppd", "var" (float64) and "n_tail" (int32).  One kernel of the library: no sort and no copy of ``values``."""
+    if not isinstance(values, torch.Tensor) or values.dim() != 2:
+        raise ValueError("values must be a tensor of shape (S, N)")
+    if not values.is_cuda:
+        _dev(values, "values")
+    if values.dtype != torch.float64:
+        raise TypeError("values must be float64")
+    S, N = (int(v) for v in values.shape)
+    n_tail_max = int(n_tail_max)
+    if n_tail_max < 1 or n_tail_max > PSIS_MAX_TAIL:
+        raise ValueError(f"n_tail_max must be in 1 .. {PSIS_MAX_TAIL}")
+    if S >= 2 ** 31:
+        raise ValueError("at most 2^31 - 1 rows")
+    values = values.detach()
+    if (N > 1 and values.stride(1) != 1) or (S > 1 and values.stride(0) < N):
+        values = values.contiguous()
+    stride = int(values.stride(0)) if S > 1 else N
+    dev = values.device
+    out = {k: torch.empty(N, dtype=torch.float64, device=dev) for k in ("elpd", "k", "lppd", "var")}
+    out["n_tail"] = torch.empty(N, dtype=torch.int32, device=dev)
+    _call("exo_column_psis_f64", dev, _ptr(values), S, N, stride, n_tail_max, _ptr(out["elpd"]), _ptr(out["k"]), _ptr(out["lppd"]),
+          _ptr(out["var"]), _ptr(out["n_tail"]), _stream(values))
+    return out

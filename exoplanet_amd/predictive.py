@@ -123,19 +123,9 @@ def _draw_rows(trace, space):
     return None, z, int(z.shape[0])
 
 
-def bands(model, trace, space=None, *, percent=(16, 50, 84), n_draws=None, chunk=1024, mean=False):
-    """The band of ``model`` over the draws of ``trace``.
-
-    ``trace``: a `sampling.Trace` or an (S, n_free) tensor of unconstrained rows, with ``space`` (a `ParameterSpace`); or a
-    dict {name: (n_draws, chains, count)} as ``Trace.constrain`` returns, with ``space=None`` (a "log_prior" key is ignored).
-    The n_draws * chains rows are taken in order; ``n_draws=`` takes the rows ``(arange(n_draws) * total) // n_draws`` instead
-    (deterministic thinning).  Under ``torch.no_grad()`` the rows go through ``space.constrain`` in chunks of ``chunk``, and
-    ``model(**theta)`` -- the names ``space.wrap`` would pass (a dict: its keys), each (chunk, count) -- must return (chunk, N).
-    Every chunk is written into its rows of one (S, N) array; then `quantiles`.
-
-    Returns {"percent", "quantiles" (Q, N), "n_valid" (N,), "n_draws": S} and, with ``mean=True``, "mean" (N,): the
-    ``torch.nanmean`` over the draws.  The host reads nothing from the device."""
-    fractions = _fractions(percent)
+def _model_over_draws(model, trace, space, n_draws, chunk):
+    """``model`` at the kept draws of ``trace``, in chunks, as one (S, N) float64 array (`bands`: its curves; `comparison.loo`:
+    its pointwise log-likelihoods).  The arguments are those of `bands`."""
     chunk = int(chunk)
     if chunk < 1:
         raise ValueError("chunk must be at least 1")
@@ -184,6 +174,25 @@ def bands(model, trace, space=None, *, percent=(16, 50, 84), n_draws=None, chunk
             if y.shape[1] != N:
                 raise ValueError(f"model returned {y.shape[1]} columns after {N}")
             buf[lo:hi] = y
+    return buf
+
+
+def bands(model, trace, space=None, *, percent=(16, 50, 84), n_draws=None, chunk=1024, mean=False):
+    """The band of ``model`` over the draws of ``trace``.
+
+    ``trace``: a `sampling.Trace` or an (S, n_free) tensor of unconstrained rows, with ``space`` (a `ParameterSpace`); or a
+    dict {name: (n_draws, chains, count)} as ``Trace.constrain`` returns, with ``space=None`` (a "log_prior" key is ignored).
+    The n_draws * chains rows are taken in order; ``n_draws=`` takes the rows ``(arange(n_draws) * total) // n_draws`` instead
+    (deterministic thinning).  Under ``torch.no_grad()`` the rows go through ``space.constrain`` in chunks of ``chunk``, and
+    ``model(**theta)`` -- the names ``space.wrap`` would pass (a dict: its keys), each (chunk, count) -- must return (chunk, N).
+    Every chunk is written into its rows of one (S, N) array; then `quantiles`.
+
+    Returns {"percent", "quantiles" (Q, N), "n_valid" (N,), "n_draws": S} and, with ``mean=True``, "mean" (N,): the
+    ``torch.nanmean`` over the draws.  The host reads nothing from the device."""
+    fractions = _fractions(percent)
+    buf = _model_over_draws(model, trace, space, n_draws, chunk)
+    S = int(buf.shape[0])
+    with torch.no_grad():
         q, n_valid = _quantiles(buf, fractions)
         out = {"percent": tuple(percent) if isinstance(percent, (list, tuple)) else percent, "quantiles": q, "n_valid": n_valid,
                "n_draws": S}

@@ -57,7 +57,8 @@ extern "C" {
  *     caller breaks: exo_tls_power_f64; exo_location_windows_f64, exo_running_location_f64, EXO_LOCATION_*;
  *     exo_timing_windows_f64, exo_transit_timing_f64, EXO_TIMING_*; exo_running_trend_f64, EXO_TREND_MAX_WINDOW;
  *     exo_keplerian_workspace_bytes, exo_keplerian_power_f64, EXO_KEP_*; exo_astrometric_workspace_bytes,
- *     exo_astrometric_power_f64, EXO_AST_NCOEF; exo_column_quantiles_f64, EXO_QUANTILE_MAX_Q.) */
+ *     exo_astrometric_power_f64, EXO_AST_NCOEF; exo_column_quantiles_f64, EXO_QUANTILE_MAX_Q;
+ *     exo_column_psis_f64, EXO_PSIS_MAX_TAIL.) */
 #define EXO_ABI_VERSION 21
 int32_t exo_abi_version(void);
 
@@ -1296,6 +1297,27 @@ int exo_diag_finish_f64(int64_t n_param, int64_t n_half, int64_t n_len, int64_t 
 #define EXO_QUANTILE_MAX_Q 16
 int exo_column_quantiles_f64(const double* x, int64_t n_rows, int64_t n_cols, int64_t row_stride, const int64_t* num,
                              const int64_t* den, int n_q, double* out, int32_t* n_valid, void* stream);
+
+/* -------------------------------------------------------------------------
+ * PSIS-LOO and WAIC per column of an array of pointwise log-likelihoods (exoplanet_amd/comparison.py).
+ * x: n_rows draws of n_cols observations, row_stride >= n_cols doubles apart (the last axis contiguous), on the device.  For
+ * every column l_s, with M = n_tail_max (1 .. EXO_PSIS_MAX_TAIL; the caller's ceil(min(S / 5, 3 sqrt(S / reff)))):
+ *   a NaN or an infinity in the column, or n_rows == 0: NaN in every floating output, n_tail = 0.  Otherwise x_s = l_min - l_s,
+ *   the cut-off c = max(x_(max(S-M-1, 0)), log(DBL_MIN)), the tail {x_s > c} of n <= M values; n <= 4: k = +inf, nothing is
+ *   smoothed; otherwise the generalised-Pareto fit of Zhang & Stephens (2009) to exp(x) - exp(c) of the tail ascending, with
+ *   the prior of ArviZ's _gpdfit, gives k and sigma, and a finite k replaces the j-th tail value by
+ *   min(log(sigma expm1(-k log1p(-p_j)) / k + exp(c)), 0), p_j = (j + 0.5) / n.  With the smoothed x':
+ *   out_elpd = logsumexp_s(x'_s + l_s) - logsumexp_s(x'_s); out_k = k; out_lppd = logsumexp_s(l_s) - log S; out_var = the
+ *   variance of l_s over the draws with divisor S, about the mean; out_n_tail = n.  Each [n_cols].
+ * One kernel: selection by counting passes for the cut-off, the tail gathered, sorted and fitted in LDS; no workspace, no
+ * atomics on floating-point numbers, no host synchronisation; bit-reproducible, capturable.
+ * EXO_ERR_INVALID_ARGUMENT, before any launch: negative sizes, n_rows >= 2^31, n_tail_max outside 1 .. EXO_PSIS_MAX_TAIL,
+ * row_stride < n_cols, a null x (with n_rows > 0) or a null output.  n_cols == 0: EXO_OK, nothing launched (sizes are checked
+ * first).  (Added without a new ABI number: no caller breaks.)
+ * ------------------------------------------------------------------------- */
+#define EXO_PSIS_MAX_TAIL 1024
+int exo_column_psis_f64(const double* x, int64_t n_rows, int64_t n_cols, int64_t row_stride, int32_t n_tail_max, double* out_elpd,
+                        double* out_k, double* out_lppd, double* out_var, int32_t* out_n_tail, void* stream);
 
 #ifdef __cplusplus
 }
