@@ -42,6 +42,21 @@ def _buffer(*shape, device):
     return x
 
 
+def _reverse_consumes_state(lib, N, D, n_real, n_complex, nstate, n_chunks):
+    """The reverse pass of the time-parallel plan works inside the chunk workspace that lives in the forward call's state and
+    overwrites what the forward call left there: it can run ONCE per forward call -- a second one on the same state returned
+    wrong gradients without a word.  The sequential plan, whose state is the factorisation alone and is
+    only read, can be run again; it is told apart by the size of its state."""
+    return nstate != lib.exo_celerite_state_doubles(N, D, n_real, n_complex, 1 | (n_chunks & PREPARE_ADJOINT))
+
+
+def _spend_state(ctx):
+    if getattr(ctx, "spent", False):
+        raise RuntimeError("the reverse pass of the time-parallel celerite likelihood consumes the state of its forward call: a "
+                           "second backward through the same graph (retain_graph=True) needs a new forward call, or n_chunks=1")
+    ctx.spent = ctx.once
+
+
 class _CeleriteLogLike(torch.autograd.Function):
     @staticmethod
     def forward(ctx, t, resid, diag, coef_real, coef_complex, obs, pair_kind, n_chunks):
@@ -109,12 +124,14 @@ class _CeleriteLogLike(torch.autograd.Function):
             ctx.save_for_backward(t, resid, diag, coef_real, coef_complex, state, obs, pair_kind)
             ctx.dims = (D, N, n_real, n_complex, nstate, n_chunks)
             ctx.cm = cm
+            ctx.once = _reverse_consumes_state(lib, N, D, n_real, n_complex, nstate, n_chunks)
         return loglike
 
     @staticmethod
     def backward(ctx, gll):
         t, resid, diag, coef_real, coef_complex, state, obs, pair_kind = ctx.saved_tensors
         D, N, n_real, n_complex, nstate, n_chunks = ctx.dims
+        _spend_state(ctx)
         gll = _dev(gll, "gloglike")
         lib = _lib.load()
         if ctx.cm:     # the cotangent of a cadence-major model in the model's layout
@@ -235,6 +252,7 @@ class _CeleriteLogLikeSparse(torch.autograd.Function):
             ctx.save_for_backward(t, vals, diag, coef_real, coef_complex, state, obs, pair_kind, perm)
             ctx.dims = (D, N, n_real, n_complex, nstate, n_chunks)
             ctx.sp = sp
+            ctx.once = _reverse_consumes_state(lib, N, D, n_real, n_complex, nstate, n_chunks)
         return loglike
 
     @staticmethod
@@ -243,6 +261,7 @@ class _CeleriteLogLikeSparse(torch.autograd.Function):
 
         t, vals, diag, coef_real, coef_complex, state, obs, pair_kind, perm = ctx.saved_tensors
         D, N, n_real, n_complex, nstate, n_chunks = ctx.dims
+        _spend_state(ctx)
         gll = _dev(gll, "gloglike")
         lib = _lib.load()
         # Only the positions a segment covers are DEFINED -- in `vals` (the rest of the sweep's value array is workspace the

@@ -36,6 +36,12 @@ its smallest value set so that the conditioning score of exo_celerite_core.hpp (
   cadence, cadence_jitter, bjd_grid, stiff, fast_osc   the time axis: a 2-minute grid, the same with the steps' last bits
                      jittered and a gap, stamps on a 2^-20 d grid at 2 457 000 d, c dt = 30 next to c dt = 1e-3, d dt = 10
   n1, n2, n63, n64, n193_j06, n193_j10    sizes: the edges, either side of the shortest series that is cut, six chunks
+
+Routes (ROUTES, further down) include the two ways the benchmark's configurations reach the likelihood: a cadence-major model and
+a sparse mean.  For those this file also holds how the fixture's y reaches kernels that see obs - model with one obs per call
+(sparse_obs / entry_model), the builder of sparse layouts and descriptors both the host test and the GPU test use (SPARSE_LAYOUTS,
+sparse_segments, sparse_model, sparse_entry, sparse_batch), the hand-filled sparse light curve the wrappers take
+(sparse_light_curve), the benign draws of a batch (benign, batch) and the sentinel of the untouched-position check (SENTINEL).
 """
 import copy
 import os
@@ -242,15 +248,18 @@ def yardstick(c):
 
 # ------------------------------------------------------------------------------------------------------------------
 # the routes of tests/test_gpu_gp_like.py: every (entry, route) pair runs or sits in EXCLUDED with its reason
-ROUTES = ("default", "one_chunk", "forced", "batch", "obs_minus_model", "gaussian_process", "no_grad")
+ROUTES = ("default", "one_chunk", "forced", "batch", "obs_minus_model", "gaussian_process", "no_grad", "cadence_major", "sparse_mean")
 FORCED = (2, 5)                     # the chunk counts of route "forced" (and of the host pipeline)
 BATCH, BATCH_RAGGED = 5, 70         # draws of route "batch"; the entries of RAGGED also in a batch whose last wave is ragged
+BATCH_WAVES = 130                   # ... and in one of two full waves and a ragged third
 RAGGED = ("j03", "j08", "j10")
 # (entry, route) -> (the quantities not asserted -- None: the pair does not run --, the reason).  The tree scans amplify rounding
 # by up to the conditioning score x 1e-16 where the score comes from b / a (a term next to critical damping) and, on a cadence
 # grid with c dt = 1e-3, lose d / d a with every level of the trees; the sequential kernels do neither (DESIGN.md section 17.4,
-# which has the cause; the errors below are those measured on the MI355X, as error / tolerance)
-TREES = ("default", "forced", "batch", "obs_minus_model")
+# which has the cause; the errors below are those measured on the MI355X, as error / tolerance).  The cadence-major and the
+# sparse-mean route run the same scans on the same numbers and inherit these entries, nothing else (DESIGN.md section 17.3 has
+# their figures: the same); with n_chunks = 1 the quantities are asserted on those two routes all the same
+TREES = ("default", "forced", "batch", "obs_minus_model", "cadence_major", "sparse_mean")
 EXCLUDED = {(e, "forced"): (None, "N < 64: chunk_plan does not cut a series that short, whatever n_chunks") for e in ("n1", "n2", "n63")}
 EXCLUDED.update({("q05001", r): (("gy", "gdiag", "gpairs"), "tree scans at b / a = 50, score 1e6: gy 5.1e-10 / 3.9e-10, gdiag 1.0e-9 / 5.1e-10, "
                                  "gpairs 1.3e-10 / 1.2e-12") for r in TREES})
@@ -263,6 +272,199 @@ MAX_EXCLUDED = 0.10
 # entry -> the quantities not asserted there (measured: q04999 1.2e-12 / 1.1e-13, q05001 4.0e-12 / 1.2e-12, matern 5.4e-11 / 1.2e-11,
 # cadence 2.3e-13 / 1e-13, cadence_jitter 4.7e-13 / 1.5e-13)
 HOST_EXCLUDED = {e: ("gpairs",) for e in ("q04999", "q05001", "matern", "cadence", "cadence_jitter")}
+
+
+def benign(c, rng, D):
+    """D benign draws of the layout of ``c`` on its time axis: (y, diag, real, pairs), a kind-1 slot two positive real terms"""
+    jr, jc, n = len(c.coef_real), len(c.pairs), c.n
+    real = np.stack([rng.uniform(0.3, 1.0, (D, jr)), rng.uniform(0.1, 1.0, (D, jr))], -1)
+    a, cc, d = rng.uniform(0.3, 1.0, (D, jc)), rng.uniform(0.1, 0.8, (D, jc)), rng.uniform(0.5, 3.0, (D, jc))
+    pairs = np.stack([a, 0.3 * a * cc / d, cc, d], -1)
+    k1 = np.broadcast_to(c.pair_kind.astype(bool), (D, jc))
+    pairs[k1] = np.stack([a, cc, 0.5 * a, d], -1)[k1]
+    return rng.normal(size=(D, n)), rng.uniform(0.07, 0.1, (D, n)), real, pairs
+
+
+def batch(c, D, at, seed=7):
+    """(y, diag, real, pairs) of D draws: the entry at the positions ``at`` between benign draws"""
+    y, diag, real, pairs = benign(c, np.random.default_rng(seed), D)
+    for d in at:
+        y[d], diag[d], real[d], pairs[d] = c.y, c.diag, c.coef_real, c.pairs
+    return y, diag, real, pairs
+
+
+def restricted(c, idx):
+    """the case whose gy is held at the cadences ``idx`` alone (a sparse model has a cotangent only where it has a value);
+    the scale, max |alpha| over the whole series, stays"""
+    r = copy.copy(c)
+    r.want = dict(c.want, gy=c.want["gy"][idx])
+    return r
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# Routes "cadence_major" and "sparse_mean": the fixture's y has to reach the kernels exactly although they see obs - model with
+# one obs for all draws of a call.  For a set H of cadences  obs = where(H, y / 2, y);  a draw that carries the entry has the
+# model -y / 2 on H and +0.0 -- or no value at all -- elsewhere: y / 2 - (-y / 2) and y - 0 are exact in float64.  Every
+# entry-carrying draw of a call covers the same H (cadence-major: H is everything).
+#
+# Sparse layouts (exo_sparse_model, include/exoplanet_amd.h), by name, for a series of n cadences -- clipped to it:
+#   none       no segment: obs = y, and the whole of gvals stays untouched
+#   whole      [0, n)
+#   edges      [0, 1) and [n - 1, n)                                  (n = 1: the one cadence once)
+#   comb       [i, i + 1) for every even i: the most segments a series can have, an edge on either side of every chunk boundary
+#   blocks     [7 k, 7 k + 5) for all k: 7 is prime to the block of four cadences and to every chunk length, so the segment
+#              edges meet block and chunk boundaries in every phase
+#   blocks3    the same shifted by 3                                  (n <= 3: by n - 1)
+#   touching   [0, 40), [40, 41), [41, n): hi_k == lo_(k+1)           (n <= 41: cut at n / 2 instead of 40)
+#   padded     H as in blocks, every segment widened by two cadences either side that carry +0.0 -- the gaps between the
+#              blocks are two cadences wide, so neighbours would overlap: they meet half way, one cadence each (the outer edges
+#              of the first and the last segment get their two, clipped to the series).  A padded cadence has a value: its
+#              cotangent is -gy there like anywhere else
+# Descriptor forms: "sweep" (seg_step = 4, hi_at = 3: rows of r_max runs (lo, a, b, hi), a, b and the unused runs poisoned) and
+# "merged" (seg_step = 2, hi_at = 1).  ``off``: "prefix" (exclusive prefix sums) or "gaps" (the values do not start at 0 and
+# leave holes between the segments).  Unused entries of seg and off hold SEG_POISON; every position of vals that no segment
+# covers holds NaN -- a kernel that reads one shows it.
+SPARSE_LAYOUTS = ("none", "whole", "edges", "comb", "blocks", "blocks3", "touching", "padded")
+SPARSE_FORMS = {"sweep": (4, 3), "merged": (2, 1)}      # name -> (seg_step, hi_at)
+SPARSE_OFFS = ("prefix", "gaps")
+SPARSE_VARIANTS = tuple((f, o) for f in SPARSE_FORMS for o in SPARSE_OFFS)
+SPARSE_EVERY_ENTRY = ("whole", "comb", "blocks")        # the layouts every entry takes in every variant (the ladder: all of them)
+SEG_POISON = np.iinfo(np.int32).min
+SENTINEL = -6.0221407612345678e+299                      # what a cotangent array holds before the call, compared bit for bit
+
+
+def sparse_segments(layout, n):
+    """-> (segments [(lo, hi)], ascending and disjoint, H (n,) bool: the cadences at which an entry-carrying draw holds -y / 2)"""
+    H = np.zeros(n, bool)
+    if layout == "none":
+        segs = []
+    elif layout == "whole":
+        segs = [(0, n)]
+    elif layout == "edges":
+        segs = [(0, 1)] + ([(n - 1, n)] if n > 1 else [])
+    elif layout == "comb":
+        segs = [(i, i + 1) for i in range(0, n, 2)]
+    elif layout in ("blocks", "blocks3", "padded"):
+        s = min(3, n - 1) if layout == "blocks3" else 0
+        segs = [(lo, min(lo + 5, n)) for lo in range(s, n, 7)]
+    elif layout == "touching":
+        a = 40 if n > 41 else n // 2
+        segs = [(lo, hi) for lo, hi in ((0, a), (a, a + 1), (a + 1, n)) if hi > lo]
+    else:
+        raise KeyError(layout)
+    for lo, hi in segs:
+        H[lo:hi] = True
+    if layout == "padded":
+        wide = []
+        for k, (lo, hi) in enumerate(segs):
+            left = 2 if k == 0 else min(2, (lo - segs[k - 1][1]) // 2)
+            right = 2 if k + 1 == len(segs) else min(2, (segs[k + 1][0] - hi + 1) // 2)
+            wide.append((max(lo - left, 0), min(hi + right, n)))
+        segs = wide
+        assert all(a[1] <= b[0] for a, b in zip(segs, segs[1:]))
+    return segs, H
+
+
+class SparseModel:
+    """the arrays of an exo_sparse_model for D draws (nseg, seg, off, vals; seg_row, off_row, val_row, seg_step, hi_at), ``H``,
+    and per draw ``cad[d]`` / ``pos[d]``: the covered cadences and the positions of their values in row d of vals"""
+
+    def dense(self, d):
+        m = np.zeros(self.n)
+        m[self.cad[d]] = self.vals[d, self.pos[d]]
+        return m
+
+    def untouched(self, d):
+        mask = np.ones(self.val_row, bool)
+        mask[self.pos[d]] = False
+        return mask
+
+
+def sparse_model(n, draws, form="sweep", offs="prefix", seed=3):
+    """``draws``: per draw (layout, model (n,)) -- the model's values at the cadences the layout's segments cover"""
+    rng = np.random.default_rng(seed)
+    m = SparseModel()
+    segs = [sparse_segments(layout, n)[0] for layout, _ in draws]
+    D, cap = len(draws), max(len(s) for s in segs) + 2
+    m.n, m.D, m.form, m.offs = n, D, form, offs
+    m.seg_step, m.hi_at = SPARSE_FORMS[form]
+    m.seg_row, m.off_row, m.val_row = cap * m.seg_step, cap + 1, n + (3 * cap + 5 if offs == "gaps" else 0)
+    m.nseg = np.array([len(s) for s in segs], np.int32)
+    m.seg = np.full((D, cap, m.seg_step), SEG_POISON, np.int32)
+    m.off = np.full((D, cap + 1), SEG_POISON, np.int32)
+    m.vals = np.full((D, m.val_row), np.nan)
+    m.cad, m.pos = [], []
+    for d, (sg, (_, model)) in enumerate(zip(segs, draws)):
+        at = int(rng.integers(1, 5)) if offs == "gaps" else 0
+        cad, pos = [], []
+        for k, (lo, hi) in enumerate(sg):
+            m.seg[d, k, 0], m.seg[d, k, m.hi_at], m.off[d, k] = lo, hi, at
+            m.vals[d, at:at + hi - lo] = model[lo:hi]
+            cad.append(np.arange(lo, hi))
+            pos.append(np.arange(at, at + hi - lo))
+            at += hi - lo + (int(rng.integers(0, 3)) if offs == "gaps" else 0)
+        assert at <= m.val_row
+        m.cad.append(np.concatenate(cad).astype(np.int64) if cad else np.zeros(0, np.int64))
+        m.pos.append(np.concatenate(pos).astype(np.int64) if pos else np.zeros(0, np.int64))
+    return m
+
+
+def entry_model(c, H):
+    """the model of a draw that carries the entry: -y / 2 on H, +0.0 elsewhere"""
+    return np.where(H, -0.5 * c.y, 0.0)
+
+
+def sparse_obs(c, H):
+    return np.where(H, 0.5 * c.y, c.y)
+
+
+def sparse_entry(c, layout, form="sweep", offs="prefix"):
+    """one draw carrying the entry in ``layout`` -> (obs, SparseModel)"""
+    _, H = sparse_segments(layout, c.n)
+    m = sparse_model(c.n, [(layout, entry_model(c, H))], form, offs)
+    m.H = H
+    return sparse_obs(c, H), m
+
+
+def sparse_batch(c, D, at, form="sweep", offs="prefix", seed=9):
+    """D draws: the entry at the positions ``at``, alternately as ``blocks`` and ``padded`` (the same H, other segment counts),
+    between benign draws of layouts none / edges / whole / comb / touching with arbitrary values -> (obs, SparseModel)"""
+    rng = np.random.default_rng(seed)
+    _, H = sparse_segments("blocks", c.n)
+    other = ("none", "comb", "edges", "touching", "whole")        # (five draws with the entry at 1 and 3: none, edges, whole)
+    draws = [(other[d % len(other)], 0.3 * rng.normal(size=c.n)) for d in range(D)]
+    for k, d in enumerate(at):
+        draws[d] = (("blocks", "padded")[k % 2], entry_model(c, H))
+    m = sparse_model(c.n, draws, form, offs)
+    m.H = H
+    return sparse_obs(c, H), m
+
+
+def sparse_light_curve(m, dev):
+    """a hand-filled sparse light curve the celerite wrappers take (values, n_draw, n_cad, model_struct()): the arrays of
+    SparseModel ``m`` on device ``dev``, ``values`` a leaf that requires a gradient"""
+    import torch
+
+    from exoplanet_amd import _lib, ops
+
+    class HandMadeSparseLightCurve(ops.SparseLightCurve):
+        def __init__(self):
+            self.values = torch.as_tensor(m.vals, device=dev).requires_grad_(True)
+            self._tables = [torch.as_tensor(np.ascontiguousarray(a), device=dev) for a in (m.nseg, m.seg, m.off)]
+            self.n_cad, self.n_draw, self.n_planet, self.flags, self.shape = m.n, m.D, 1, 0, (m.D, m.n)
+
+        def model_struct(self):
+            s = _lib.SparseModel()
+            s.nseg, s.seg, s.off = (a.data_ptr() for a in self._tables)
+            s.vals = self.values.data_ptr()
+            s.seg_row, s.off_row, s.val_row, s.seg_step, s.hi_at = m.seg_row, m.off_row, m.val_row, m.seg_step, m.hi_at
+            s.row_of_draw = None
+            return s
+
+        def merged(self):
+            return self
+
+    return HandMadeSparseLightCurve()
 
 
 def expected_route(c):

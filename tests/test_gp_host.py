@@ -38,15 +38,31 @@ def _p(a):
     return None if a is None else a.ctypes.data_as(_dp)
 
 
-def run(lib, t, y, diag, real, cplx, kind=None, obs=None, n_chunks=0, gll=None, cadence_major=False):
+def run_sparse(lib, t, sp, *args, **kw):
+    """run() with the model as the segments and values of ``sp`` (nseg, seg, off, vals and the strides of an exo_sparse_model:
+    gp_like_cases.SparseModel); g["y"] is then the cotangent of the VALUE array, in its shape"""
+    i64 = ctypes.c_int64
+    nseg, seg, off = (np.ascontiguousarray(a, dtype=np.int32) for a in (sp.nseg, sp.seg, sp.off))
+    lib.harness_gp_set_sparse(nseg.ctypes.data_as(_ip), seg.ctypes.data_as(_ip), off.ctypes.data_as(_ip), i64(sp.seg_row),
+                              i64(sp.off_row), i64(sp.val_row), sp.seg_step, sp.hi_at)
+    try:
+        return run(lib, t, sp.vals, *args, n_cad=np.asarray(t).size, **kw)
+    finally:
+        lib.harness_gp_set_sparse(None, None, None, i64(0), i64(0), i64(0), 0, 0)
+
+
+def run(lib, t, y, diag, real, cplx, kind=None, obs=None, n_chunks=0, gll=None, cadence_major=False, n_cad=None, gfill=None):
     """-> loglike (D,), flags (D,), and with gll: dict of gradients.  cadence_major: the kernels are handed y (and write its
-    cotangent) as [cadence][draw] arrays (Series::cm)"""
+    cotangent) as [cadence][draw] arrays (Series::cm).  n_cad: the series' length where it is not y's row length (run_sparse);
+    gfill: what the cotangent of y holds before the call"""
     t = np.ascontiguousarray(t, dtype=np.float64)
     y = np.ascontiguousarray(y, dtype=np.float64)
     diag = np.ascontiguousarray(diag, dtype=np.float64)
     real = np.ascontiguousarray(real, dtype=np.float64)
     cplx = np.ascontiguousarray(cplx, dtype=np.float64)
     D, n = y.shape
+    if n_cad is not None:
+        n = int(n_cad)
     if cadence_major:
         y = np.ascontiguousarray(y.T)
     lib.harness_gp_set_cadence_major(1 if cadence_major else 0)
@@ -67,8 +83,8 @@ def run(lib, t, y, diag, real, cplx, kind=None, obs=None, n_chunks=0, gll=None, 
     if gll is None:
         return ll, flags, C_used
     gll = np.ascontiguousarray(gll, dtype=np.float64)
-    g = {"y": np.empty((D, n)), "diag": np.empty((D, n)), "diag_sum": np.empty(D), "real": np.empty_like(real),
-         "cplx": np.empty_like(cplx)}
+    g = {"y": np.empty(y.shape) if gfill is None else np.full(y.shape, gfill), "diag": np.empty((D, n)), "diag_sum": np.empty(D),
+         "real": np.empty_like(real), "cplx": np.empty_like(cplx)}
     rc = lib.harness_gp_vjp(*args, _p(gll), _p(state), _p(g["y"]), _p(g["diag"]), _p(g["diag_sum"]), _p(g["real"]),
                             _p(g["cplx"]))
     assert rc == C_used
