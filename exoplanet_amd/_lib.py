@@ -166,6 +166,11 @@ _SIGNATURES = {
     # n_phase, power, candidate, coef, workspace, workspace_bytes, stream
     "exo_keplerian_power_f64": (ctypes.c_int, [_c_dp, _c_dp, _c_dp, _i64, _i64, _i64, _c_dp, _i32, _c_dp, _i64, _c_dp, _i32,
                                                _i32, _c_dp, _c_dp, _c_dp, _c_dp, _i64, _c_dp]),
+    "exo_keplerian_max_workspace_bytes": (_i64, [_i64, _i64, _i64, _i32]),
+    # t, y, yerr, n_yerr, n, n_series, segment_offsets (host), n_instrument, frequencies, n_frequency, ecc (host), n_ecc,
+    # n_phase, frequencies_per_block, max_power, frequency_index, candidate, workspace, workspace_bytes, stream
+    "exo_keplerian_max_f64": (ctypes.c_int, [_c_dp, _c_dp, _c_dp, _i64, _i64, _i64, _c_dp, _i32, _c_dp, _i64, _c_dp, _i32,
+                                             _i32, _i32, _c_dp, _c_dp, _c_dp, _c_dp, _i64, _c_dp]),
     "exo_astrometric_workspace_bytes": (_i64, [_i64, _i64]),
     # t, rho, rho_err, n_rho_err, theta, theta_err, n_theta_err, n, n_series, frequencies, n_frequency, ecc (host), n_ecc,
     # n_phase, power, candidate, coef, workspace, workspace_bytes, stream

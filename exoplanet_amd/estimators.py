@@ -16,12 +16,18 @@ For radial velocities the search is the Keplerian periodogram (csrc/exo_kepleria
 frequency a grid of eccentricities and times of periastron, each candidate a linear fit with one constant per instrument,
 which gives the ``ecc``, ``omega``, ``t_periastron``, ``K`` and zero points an RV model starts from (not in the reference).
 
+Whether a peak of either periodogram is a detection is the question of :func:`false_alarm`: the highest
+peak of shuffled or bootstrapped series, for the Keplerian periodogram through :func:`keplerian_max_power`, a kernel in which a
+group of series shares every solve of Kepler's equation and only the arg-max leaves the device (not in the reference).
+
 For relative astrometry it is the search on the Thiele-Innes constants (csrc/exo_astrometric.hip): the
 same grid of candidates, each a linear fit of four constants to the sky-plane positions, which gives the seven elements
 ``astrometry_log_likelihood`` starts from (not in the reference).
 
 Low level (device tensors in and out, float64): :func:`bls_power`, :func:`tls_power` (its templates:
-:func:`transit_template`), :func:`lomb_scargle_power`, :func:`keplerian_power`, :func:`astrometric_power`, :func:`running_location` (its windows:
+:func:`transit_template`), :func:`lomb_scargle_power`, :func:`keplerian_power`, :func:`keplerian_max_power`,
+:func:`false_alarm` (its pieces: :func:`resample_indices`, :func:`series_chi2_0`, :func:`false_alarm_probability`,
+:func:`false_alarm_level`), :func:`astrometric_power`, :func:`running_location` (its windows:
 :func:`location_plan`),
 :func:`transit_times` (its windows: :func:`timing_plan`), and the
 grids :func:`bls_autoperiod`, :func:`lomb_scargle_autofrequency` (host arithmetic).
@@ -50,6 +56,7 @@ only reduction is an arg-max).
 """
 import collections
 import ctypes
+import types
 
 import numpy as np
 import torch
@@ -57,7 +64,8 @@ import torch
 from . import _lib
 
 __all__ = [
-    "bls_power", "tls_power", "transit_template", "lomb_scargle_power", "keplerian_power", "astrometric_power", "bls_autoperiod", "lomb_scargle_autofrequency",
+    "bls_power", "tls_power", "transit_template", "lomb_scargle_power", "keplerian_power", "keplerian_max_power", "astrometric_power",
+    "resample_indices", "series_chi2_0", "false_alarm_probability", "false_alarm_level", "false_alarm", "bls_autoperiod", "lomb_scargle_autofrequency",
     "LocationPlan", "location_plan", "running_location", "flatten", "sde",
     "TimingPlan", "timing_plan", "transit_times", "ttv_estimator",
     "find_peaks", "bls_estimator", "tls_estimator", "lomb_scargle_estimator", "keplerian_estimator", "astrometric_estimator", "autocorr_function", "autocorr_estimator", "estimate_semi_amplitude", "estimate_minimum_mass",
@@ -405,6 +413,26 @@ def _instrument_segments(instrument, n):
     return np.argsort(inst, kind="stable"), np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
 
 
+def _keplerian_arguments(t, y, yerr, frequencies, ecc, n_phase, instrument):
+    """What :func:`keplerian_power` and :func:`keplerian_max_power` do alike before their entry point: the grids checked, the
+    series on the device with the epochs sorted by instrument, and ``lead``, the entry's arguments before the frequencies.  ->
+    a namespace that also keeps alive what ``lead`` points to"""
+    e_host, n_phase = _keplerian_grid(ecc, n_phase)
+    n_given = t.shape[-1] if hasattr(t, "shape") and len(t.shape) else 0
+    order, offsets = _instrument_segments(instrument, int(n_given))
+    t, y, yerr, batched = _device_series(t, y, yerr)
+    _, f_dev = _grid(frequencies, "frequencies", t.device)
+    t_min = t.min()
+    if order is not None:                                      # the epochs by instrument (the sums need no time order)
+        order = torch.as_tensor(order, device=t.device)
+        t, y = t[order].contiguous(), y[:, order].contiguous()
+        yerr = None if yerr is None else yerr[:, order].contiguous()
+    lead = (t.data_ptr(), y.data_ptr(), 0 if yerr is None else yerr.data_ptr(), 0 if yerr is None else yerr.shape[0], y.shape[1],
+            y.shape[0], offsets.ctypes.data_as(ctypes.c_void_p), offsets.size - 1)
+    return types.SimpleNamespace(t=t, y=y, yerr=yerr, batched=batched, f_dev=f_dev, e_host=e_host, n_phase=n_phase, offsets=offsets,
+                                 t_min=t_min, lead=lead)
+
+
 def keplerian_power(t, y, yerr=None, *, frequencies, ecc=None, n_phase=64, instrument=None, return_fit=False):
     """Keplerian periodogram of the radial velocities ``y`` (N,) or (B, N) at the epochs ``t`` (N,), any order: at every
     frequency the largest ``(chi2_0 - chi2) / 2`` over a grid of eccentricities ``ecc`` (default ``linspace(0, 0.9, 10)``) and
@@ -420,19 +448,8 @@ def keplerian_power(t, y, yerr=None, *, frequencies, ecc=None, n_phase=64, instr
     ``KeplerianOrbit.get_radial_velocity(t, K=K)`` and ``rv_log_likelihood(K=, zero_point=, instrument=)``: ``period = 1 / f``,
     and the model is ``zero_point[instrument] + K (cos omega (cos nu + ecc) - sin omega sin nu)``.  Every sum has a fixed
     order: the results are bitwise reproducible."""
-    e_host, n_phase = _keplerian_grid(ecc, n_phase)
-    n_given = t.shape[-1] if hasattr(t, "shape") and len(t.shape) else 0
-    order, offsets = _instrument_segments(instrument, int(n_given))
-    t, y, yerr, batched = _device_series(t, y, yerr)
-    _, f_dev = _grid(frequencies, "frequencies", t.device)
-    B, N, n_inst = y.shape[0], y.shape[1], offsets.size - 1
-    t_min = t.min()
-    if order is not None:                                      # the epochs by instrument (the sums need no time order)
-        order = torch.as_tensor(order, device=t.device)
-        t, y = t[order].contiguous(), y[:, order].contiguous()
-        yerr = None if yerr is None else yerr[:, order].contiguous()
-    lead = (t.data_ptr(), y.data_ptr(), 0 if yerr is None else yerr.data_ptr(), 0 if yerr is None else yerr.shape[0], N, B,
-            offsets.ctypes.data_as(ctypes.c_void_p), n_inst)
+    a = _keplerian_arguments(t, y, yerr, frequencies, ecc, n_phase, instrument)
+    t_min, f_dev, n_phase = a.t_min, a.f_dev, a.n_phase
 
     def fit(cand, c, e, coef):
         # the elements of the winner: A = K cos w, B = -K sin w, c_k = zero_point_k + e A
@@ -442,7 +459,8 @@ def keplerian_power(t, y, yerr=None, *, frequencies, ecc=None, n_phase=64, instr
         return dict(ecc=e, omega=torch.atan2(-Bs, A), t_periastron=t_p, K=torch.hypot(A, Bs),
                     zero_point=coef[..., 2:] - (e * A)[..., None], candidate=cand.to(torch.int64))
 
-    return _orbit_search("keplerian", t, lead, (B, N), f_dev, e_host, n_phase, 2 + n_inst, batched, fit if return_fit else None)
+    return _orbit_search("keplerian", a.t, a.lead, tuple(a.y.shape), f_dev, a.e_host, n_phase, 2 + a.offsets.size - 1, a.batched,
+                         fit if return_fit else None)
 
 
 def _orbit_search(name, t, lead, shape, f_dev, e_host, n_phase, n_coef, batched, fit):
@@ -472,6 +490,212 @@ def _orbit_search(name, t, lead, shape, f_dev, e_host, n_phase, n_coef, batched,
     if not batched:
         power, out = power[0], {k: v[0] for k, v in out.items()}
     return power, out
+
+
+KEPLERIAN_MAX_GROUP = 8  # series that share a solve in exo_keplerian_max_f64 (csrc/exo_keplerian.hip: kGroup)
+MAX_SERIES = 65535       # series of one call of the orbit searches
+
+
+def keplerian_max_power(t, y, yerr=None, *, frequencies, ecc=None, n_phase=64, instrument=None, frequencies_per_block=None):
+    """The highest peak of :func:`keplerian_power` for every series of ``y`` (N,) or (B, N), without the periodogram: a dict of
+    ``power``, the largest power over the grid, ``frequency_index``, the lowest index at which it is reached, and ``candidate``,
+    the winner's number there (int64), each (B,) or a scalar tensor; ``-inf, -1, -1`` for a series without a finite power.  The
+    numbers are bit for bit those of ``keplerian_power(..., return_fit=True)`` and its row maximum, for any batch; what makes
+    it several times cheaper for a large one is that ``KEPLERIAN_MAX_GROUP`` series share every solve of Kepler's equation
+    (DESIGN.md section 26).  The other arguments are :func:`keplerian_power`'s; ``frequencies_per_block``: consecutive
+    frequencies searched by one workgroup (None: chosen to fill the device; the results do not depend on it)."""
+    per_block = 0 if frequencies_per_block is None else frequencies_per_block
+    if int(per_block) != per_block or (frequencies_per_block is not None and per_block < 1):
+        raise ValueError(f"frequencies_per_block must be a positive integer or None, got {frequencies_per_block}")
+    a = _keplerian_arguments(t, y, yerr, frequencies, ecc, n_phase, instrument)
+    (B, N), F, device = a.y.shape, a.f_dev.numel(), a.t.device
+    power = torch.full((B,), float("-inf"), dtype=torch.float64, device=device)
+    index = torch.full((B,), -1, dtype=torch.int32, device=device)
+    cand = torch.full((B,), -1, dtype=torch.int32, device=device)
+    if F:
+        lib = _lib.load()
+        nbytes = lib.exo_keplerian_max_workspace_bytes(N, B, F, int(per_block))
+        if nbytes < 0:
+            raise ValueError("keplerian_max_power: invalid sizes")
+        ws = _workspace(nbytes, device)
+        _lib.check(lib.exo_keplerian_max_f64(*a.lead, a.f_dev.data_ptr(), F, a.e_host.ctypes.data_as(ctypes.c_void_p), a.e_host.size,
+                                             a.n_phase, int(per_block), power.data_ptr(), index.data_ptr(), cand.data_ptr(),
+                                             ws.data_ptr(), ws.numel() * 8, _stream(a.t)), "exo_keplerian_max_f64")
+    out = dict(power=power, frequency_index=index.to(torch.int64), candidate=cand.to(torch.int64))
+    return out if a.batched else {k: v[0] for k, v in out.items()}
+
+
+# ---- false-alarm probabilities by resampling (DESIGN.md section 26) ------------------------------------------------------------
+
+def _instrument_of(instrument, n):
+    """-> the instrument of every epoch as a host int64 array (zeros without ``instrument``), checked as the searches check it"""
+    if instrument is None:
+        return np.zeros(n, dtype=np.int64)
+    _instrument_segments(instrument, n)
+    inst = instrument.detach().cpu().numpy() if isinstance(instrument, torch.Tensor) else np.asarray(instrument)
+    return inst.astype(np.int64)
+
+
+def resample_indices(n, n_resample, *, instrument=None, replace=False, seed=0):
+    """A resampling table (R, N), int64, made on the host with ``np.random.default_rng(seed)``, row by row: resampled series
+    ``r`` takes ``y[idx[r, i]]`` at epoch ``i``.  Every index stays within its epoch's instrument, so the segments and the free
+    constants keep their meaning.  ``replace=False``: each instrument's entries of a row are a permutation of its epochs (the
+    shuffle of the radial-velocity literature); ``replace=True``: drawn from them with replacement (the bootstrap)."""
+    if int(n) != n or n < 1 or int(n_resample) != n_resample or n_resample < 1:
+        raise ValueError(f"n and n_resample must be positive integers, got {n} and {n_resample}")
+    inst = _instrument_of(instrument, int(n))
+    members = [np.flatnonzero(inst == k) for k in np.unique(inst)]
+    rng = np.random.default_rng(seed)
+    idx = np.empty((int(n_resample), int(n)), dtype=np.int64)
+    for row in idx:
+        for m in members:
+            row[m] = rng.choice(m, size=m.size, replace=True) if replace else rng.permutation(m)
+    return idx
+
+
+def _check_resamples(resamples, inst):
+    """-> a caller's table as a host int64 array (R, N), or ValueError: shape, dtype, range, and no index across instruments"""
+    idx = resamples.detach().cpu().numpy() if isinstance(resamples, torch.Tensor) else np.asarray(resamples)
+    if idx.ndim != 2 or idx.shape[0] < 1 or idx.shape[1] != inst.size:
+        raise ValueError(f"resamples must have shape (R, N) with R >= 1 and N = {inst.size}, got {tuple(idx.shape)}")
+    if idx.dtype != np.int64:
+        raise ValueError(f"resamples must be int64, got {idx.dtype}")
+    if idx.min() < 0 or idx.max() >= inst.size:
+        raise ValueError(f"resamples holds an index outside 0 .. {inst.size - 1}")
+    if not np.array_equal(inst[idx], np.broadcast_to(inst, idx.shape)):
+        raise ValueError("resamples takes an epoch's value from another instrument: resample within the instruments")
+    return np.ascontiguousarray(idx)
+
+
+def _ordered_sum(x):
+    """the sum over the last axis by a tree of one fixed shape, whatever the batch: ``torch.sum`` chooses its order by the
+    tensor's shape, and a row of a batch must give bit for bit what the single series gives"""
+    n = x.shape[-1]
+    x = torch.nn.functional.pad(x, (0, (1 << max(n - 1, 0).bit_length()) - n))
+    while x.shape[-1] > 1:
+        half = x.shape[-1] // 2
+        x = x[..., :half] + x[..., half:]
+    return x[..., 0]
+
+
+def series_chi2_0(y, yerr=None, instrument=None):
+    """``chi2_0 = sum w (y - ybar_inst)^2`` of every row of ``y`` (N,) or (B, N), ``ybar_inst`` the weighted mean of the epoch's
+    instrument: the misfit of the constants alone, which ``2 power / chi2_0`` of a periodogram is relative to.  ``yerr``: None, a
+    scalar, (N,) or the shape of ``y``.  Plain torch, on the device of ``y`` (a CPU tensor too); every sum has one fixed order, so a
+    row of a batch is bit for bit the single series."""
+    y = torch.as_tensor(y)
+    y = y.to(torch.float64)
+    w = torch.ones_like(y) if yerr is None else (1.0 / torch.as_tensor(yerr, dtype=torch.float64, device=y.device) ** 2).expand_as(y)
+    inst = _instrument_of(instrument, y.shape[-1])
+    total = torch.zeros(y.shape[:-1], dtype=torch.float64, device=y.device)
+    for k in range(int(inst.max()) + 1):
+        members = torch.as_tensor(np.flatnonzero(inst == k), device=y.device)
+        wk, yk = w[..., members], y[..., members]
+        ybar = (_ordered_sum(wk * yk) / _ordered_sum(wk))[..., None]
+        total = total + _ordered_sum(wk * (yk - ybar) ** 2)
+    return total
+
+
+def false_alarm_probability(z_null, z):
+    """``FAP(z) = (1 + #{r : z_null[r] >= z}) / (R + 1)`` for the maxima ``z_null`` (R,) of R resamplings: never zero; a NaN in
+    ``z_null`` never counts (and stays in R).  ``z``: any shape; NaN gives NaN.  Tensors give a tensor, arrays an array."""
+    if isinstance(z_null, torch.Tensor) or isinstance(z, torch.Tensor):
+        zn = torch.as_tensor(z_null).to(torch.float64).reshape(-1)
+        zz = torch.as_tensor(z).to(device=zn.device, dtype=torch.float64)
+        fap = (1 + (zn >= zz[..., None]).sum(-1)).to(torch.float64) / (zn.numel() + 1)
+        return torch.where(torch.isnan(zz), zz, fap)
+    zn, zz = np.asarray(z_null, dtype=np.float64).reshape(-1), np.asarray(z, dtype=np.float64)
+    with np.errstate(invalid="ignore"):
+        fap = (1.0 + (zn >= zz[..., None]).sum(-1)) / (zn.size + 1.0)
+    return np.where(np.isnan(zz), zz, fap)
+
+
+def false_alarm_level(z_null, alpha):
+    """The level of the false-alarm probability ``alpha`` from the maxima ``z_null`` (R,) of R resamplings: with ``k = floor(alpha
+    (R + 1))`` the k-th largest of them (a NaN ranks below every number), so that a peak strictly above it has ``FAP <= alpha``;
+    NaN when ``k < 1``: R resamplings resolve no level below ``1 / (R + 1)``.  -> a float"""
+    if not 0.0 < alpha < 1.0:
+        raise ValueError(f"a false-alarm level must lie in (0, 1), got {alpha}")
+    zn = np.sort(_np(z_null).reshape(-1))[::-1]                 # (descending: np.sort puts NaN last, reversed they come first ...)
+    zn = np.concatenate([zn[~np.isnan(zn)], zn[np.isnan(zn)]])  # (... and belong behind the numbers)
+    k = int(np.floor(alpha * (zn.size + 1) + 1e-9))             # (1e-9: 0.29 * 100 is 28.999999999999996 in binary)
+    return float(zn[k - 1]) if k >= 1 else float("nan")
+
+
+def _default_chunk(method, n, n_freq):
+    """rows of the resampling table searched per call: under the entry points' series limit, about 256 MiB of workspace and
+    output, whole groups of the Keplerian kernel"""
+    per_row = 8 * (4 * n + n_freq) if method == "lomb_scargle" else 8 * 4 * n + 4096     # (the columns; the partials)
+    chunk = max(1, min(MAX_SERIES, (256 << 20) // per_row))
+    return chunk - chunk % KEPLERIAN_MAX_GROUP if chunk > KEPLERIAN_MAX_GROUP else chunk
+
+
+def false_alarm(t, y, yerr=None, *, frequencies, method="keplerian", n_resample=1000, replace=False, seed=0, resamples=None,
+                ecc=None, n_phase=64, instrument=None, power=None, levels=(0.1, 0.01, 0.001), chunk=None):
+    """False-alarm probability of the highest peak of one series' periodogram, by resampling (Cumming 2004; astropy's
+    ``method="bootstrap"``): the velocities ``y`` (N,) are shuffled (``replace=False``) or drawn with replacement on their
+    epochs ``t``, within each instrument, ``n_resample`` times (:func:`resample_indices`; ``resamples``: a table (R, N) of the
+    caller's instead), a per-epoch ``yerr`` travelling with its velocity, and the highest peak of every resampled series is
+    recorded as ``z = 2 max_f power(f) / chi2_0``, ``chi2_0`` the resampled series' own (:func:`series_chi2_0`; NaN where it is
+    zero).  ``method="keplerian"``: the peak of :func:`keplerian_power` (``ecc``, ``n_phase``, ``instrument``), found by
+    :func:`keplerian_max_power`; ``"lomb_scargle"``: that of :func:`lomb_scargle_power` (one instrument).  ``chunk``: rows of
+    the table searched per call (None: bounded by the kernels' series limit and a modest memory budget; the results do not
+    depend on it).
+
+    Returns a dict: ``z``, ``max_power``, ``frequency_index`` (R,), device tensors; ``observed``, the same three for the data
+    itself; ``fap``, the probability of the observed peak (a float) or, with ``power=`` raw powers of that periodogram, of each
+    of them (an array); ``levels`` ``{alpha: z}`` (:func:`false_alarm_level`) and ``power_levels`` ``{alpha: z chi2_0 / 2}``, the
+    lines to draw on the data's own :func:`keplerian_power` plot; ``resamples``, the table.  The same seed gives the same
+    numbers bit for bit."""
+    if method not in ("keplerian", "lomb_scargle"):
+        raise ValueError(f"method must be 'keplerian' or 'lomb_scargle', got {method!r}")
+    if method == "lomb_scargle" and instrument is not None:
+        raise ValueError("method='lomb_scargle' fits one constant: instrument must be None")
+    if not hasattr(y, "shape") or len(y.shape) != 1 or not hasattr(t, "shape") or tuple(t.shape) != tuple(y.shape):
+        raise ValueError("false_alarm takes one series: t and y must have the same shape (N,)")
+    n = y.shape[0]
+    levels = tuple(float(a) for a in levels)
+    for alpha in levels:
+        if not 0.0 < alpha < 1.0:
+            raise ValueError(f"a false-alarm level must lie in (0, 1), got {alpha}")
+    inst = _instrument_of(instrument, n)
+    if resamples is not None:
+        idx = _check_resamples(resamples, inst)
+    elif int(n_resample) != n_resample or n_resample < 1:
+        raise ValueError(f"n_resample must be a positive integer (or give resamples=), got {n_resample}")
+    else:
+        idx = resample_indices(n, n_resample, instrument=instrument, replace=replace, seed=seed)
+    if chunk is not None and (int(chunk) != chunk or not 1 <= chunk <= MAX_SERIES):
+        raise ValueError(f"chunk must be an integer in [1, {MAX_SERIES}], got {chunk}")
+
+    dev = _device_of(t, y)
+    td, yd = _to(t, dev), _to(y, dev)
+    per_epoch = yerr is not None and len(getattr(yerr, "shape", ())) > 0
+    ed = _to(yerr, dev) if per_epoch else yerr
+    f_host, _ = _grid(frequencies, "frequencies", dev)
+    chunk = _default_chunk(method, n, f_host.size) if chunk is None else int(chunk)
+
+    def peaks(rows):
+        """rows (C, N) of indices on the device (None: the data itself) -> z, max_power, frequency_index, each (C,)"""
+        ys = yd[None] if rows is None else yd[rows]
+        es = ed if rows is None or not per_epoch else ed[rows]
+        if method == "keplerian":
+            res = keplerian_max_power(td, ys, es, frequencies=frequencies, ecc=ecc, n_phase=n_phase, instrument=instrument)
+            top, where = res["power"], res["frequency_index"]
+        else:
+            top, where = lomb_scargle_power(td, ys, es, frequencies=frequencies).max(dim=1)
+        chi2_0 = series_chi2_0(ys, es, inst)
+        return torch.where(chi2_0 == 0, torch.full_like(top, float("nan")), 2.0 * top / chi2_0), top, where, chi2_0
+
+    z_obs, top_obs, where_obs, chi2_obs = (v[0] for v in peaks(None))
+    idx_dev = torch.as_tensor(idx, device=dev)
+    parts = [peaks(idx_dev[r:r + chunk])[:3] for r in range(0, idx.shape[0], chunk)]
+    z, top, where = (torch.cat(col) for col in zip(*parts))
+    z_host, half = _np(z), 0.5 * float(chi2_obs)
+    fap = float(false_alarm_probability(z_host, float(z_obs))) if power is None else false_alarm_probability(z_host, _np(power) / half)
+    z_levels = {alpha: false_alarm_level(z_host, alpha) for alpha in levels}
+    return dict(z=z, max_power=top, frequency_index=where, observed=dict(z=z_obs, max_power=top_obs, frequency_index=where_obs),
+                fap=fap, levels=z_levels, power_levels={alpha: v * half for alpha, v in z_levels.items()}, resamples=idx)
 
 
 AST_NCOEF = 10          # EXO_AST_NCOEF
@@ -1108,30 +1332,53 @@ def _grid_maxima(peaks, max_peaks, freq, power):
         yield peak, i
 
 
-def lomb_scargle_estimator(x, y, yerr=None, min_period=None, max_period=None, filter_period=None, max_peaks=2, **kwargs):
+def _peak_false_alarms(results, peaks, raw, n, **kwargs):
+    """``fap`` into every peak ((peak, i) pairs, ``i`` the grid index of its maximum) and ``power_levels`` into ``results``, in
+    the normalisation of the estimators' ``periodogram`` (``/ n``), from :func:`false_alarm` on the same grid; ``raw``: the
+    periodogram as the kernel gives it"""
+    peaks = list(peaks)
+    fa = false_alarm(power=raw[[i for _, i in peaks]], **kwargs)
+    for (peak, _), fap in zip(peaks, fa["fap"]):
+        peak["fap"] = float(fap)
+    results["power_levels"] = {alpha: v / n for alpha, v in fa["power_levels"].items()}
+
+
+def lomb_scargle_estimator(x, y, yerr=None, min_period=None, max_period=None, filter_period=None, max_peaks=2, n_resample=0,
+                           replace=False, seed=0, **kwargs):
     """Estimate the period of a series from its Lomb-Scargle periodogram on the automatic grid (``kwargs``: those of
     :func:`lomb_scargle_autofrequency`).  Returns ``periodogram = (freq, power / len(x))`` and ``peaks``, found after the
-    optional high-pass weight ``1 / sqrt(1 + (f0 / f)^6)``, ``f0 = 1 / filter_period``."""
+    optional high-pass weight ``1 / sqrt(1 + (f0 / f)^6)``, ``f0 = 1 / filter_period``.  ``n_resample > 0``: every peak also
+    carries ``fap``, the false-alarm probability of the unfiltered power at its grid maximum from that many resamplings
+    (:func:`false_alarm` with ``replace`` and ``seed``), and the result ``power_levels`` ``{0.1, 0.01, 0.001: power}``, the
+    lines to draw on ``periodogram``."""
     _period_bounds(kwargs, min_period, max_period)
     dev = _device_of(x, y)
     xh = _np(x)
     freq = lomb_scargle_autofrequency(xh, **kwargs)
-    power = _np(lomb_scargle_power(_to(xh, dev), _to(y, dev), _to(yerr, dev), frequencies=freq)) / len(xh)
+    raw = _np(lomb_scargle_power(_to(xh, dev), _to(y, dev), _to(yerr, dev), frequencies=freq))
+    power = raw / len(xh)
     power_est = np.array(power)
     if filter_period is not None:
         power = power / np.sqrt(1 + ((1.0 / filter_period) / freq) ** 6)
-    return dict(periodogram=(freq, power_est), peaks=find_peaks(freq, power, max_peaks=max_peaks))
+    results = dict(periodogram=(freq, power_est), peaks=find_peaks(freq, power, max_peaks=max_peaks))
+    if n_resample:
+        _peak_false_alarms(results, _grid_maxima(results["peaks"], max_peaks, freq, power), raw, len(xh), t=_to(xh, dev), y=_to(y, dev),
+                           yerr=_to(yerr, dev), frequencies=freq, method="lomb_scargle", n_resample=n_resample, replace=replace,
+                           seed=seed)
+    return results
 
 
 def keplerian_estimator(x, y, yerr=None, min_period=None, max_period=None, max_peaks=2, ecc=None, n_phase=64, instrument=None,
-                        **kwargs):
+                        n_resample=0, replace=False, seed=0, **kwargs):
     """Estimate the period and the orbital elements of a radial-velocity signal from its Keplerian periodogram
     (:func:`keplerian_power`) on :func:`lomb_scargle_estimator`'s grid (``kwargs``: those of
     :func:`lomb_scargle_autofrequency`).  Returns ``periodogram = (freq, power / len(x))``, the normalisation of
     :func:`lomb_scargle_estimator`, and ``peaks`` from :func:`find_peaks`; each peak also carries ``ecc, omega, t_periastron,
     K, zero_point`` and ``power`` at the grid frequency of the local maximum itself (``power`` as in ``periodogram``;
     ``zero_point`` a float, or with ``instrument`` a list of one float per instrument).  They go straight into
-    ``KeplerianOrbit(period=, ecc=, omega=, t_periastron=)`` and ``rv_log_likelihood(K=, zero_point=, instrument=)``."""
+    ``KeplerianOrbit(period=, ecc=, omega=, t_periastron=)`` and ``rv_log_likelihood(K=, zero_point=, instrument=)``.
+    ``n_resample > 0``: every peak also carries ``fap`` and the result ``power_levels``, as in :func:`lomb_scargle_estimator`,
+    from resamplings searched with the same grids (:func:`false_alarm`, ``method="keplerian"``)."""
     _period_bounds(kwargs, min_period, max_period)
     dev = _device_of(x, y)
     xh = _np(x)
@@ -1140,13 +1387,19 @@ def keplerian_estimator(x, y, yerr=None, min_period=None, max_period=None, max_p
                                  instrument=instrument, return_fit=True)
     if power.ndim != 1:
         raise ValueError("keplerian_estimator takes one series: y must have shape (N,)")
-    power = _np(power) / len(xh)
+    raw = _np(power)
+    power = raw / len(xh)
     fit = {k: _np(v) for k, v in fit.items()}
     peaks = find_peaks(freq, power, max_peaks=max_peaks)
     for peak, i in _grid_maxima(peaks, max_peaks, freq, power):
         peak.update({k: float(fit[k][i]) for k in KEPLERIAN_FIT[:4]}, power=float(power[i]))
         peak["zero_point"] = float(fit["zero_point"][i, 0]) if instrument is None else [float(v) for v in fit["zero_point"][i]]
-    return dict(periodogram=(freq, power), peaks=peaks)
+    results = dict(periodogram=(freq, power), peaks=peaks)
+    if n_resample:
+        _peak_false_alarms(results, _grid_maxima(peaks, max_peaks, freq, power), raw, len(xh), t=_to(xh, dev), y=_to(y, dev),
+                           yerr=_to(yerr, dev), frequencies=freq, method="keplerian", n_resample=n_resample, replace=replace,
+                           seed=seed, ecc=ecc, n_phase=n_phase, instrument=instrument)
+    return results
 
 
 def astrometric_estimator(t, rho, rho_err, theta, theta_err, min_period=None, max_period=None, periods=None, max_peaks=2, ecc=None,

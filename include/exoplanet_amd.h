@@ -58,7 +58,7 @@ extern "C" {
  *     exo_timing_windows_f64, exo_transit_timing_f64, EXO_TIMING_*; exo_running_trend_f64, EXO_TREND_MAX_WINDOW;
  *     exo_keplerian_workspace_bytes, exo_keplerian_power_f64, EXO_KEP_*; exo_astrometric_workspace_bytes,
  *     exo_astrometric_power_f64, EXO_AST_NCOEF; exo_column_quantiles_f64, EXO_QUANTILE_MAX_Q;
- *     exo_column_psis_f64, EXO_PSIS_MAX_TAIL.) */
+ *     exo_column_psis_f64, EXO_PSIS_MAX_TAIL; exo_keplerian_max_workspace_bytes, exo_keplerian_max_f64.) */
 #define EXO_ABI_VERSION 21
 int32_t exo_abi_version(void);
 
@@ -1144,6 +1144,26 @@ int exo_keplerian_power_f64(const double* t, const double* y, const double* yerr
                             const int32_t* segment_offsets, int32_t n_instrument, const double* frequencies, int64_t n_frequency,
                             const double* ecc, int32_t n_ecc, int32_t n_phase, double* power, int32_t* candidate, double* coef,
                             void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------
+ * The highest peak of that periodogram for every series, without the periodogram (exoplanet_amd/estimators.py:
+ * keplerian_max_power, false_alarm): what the resamplings behind a false-alarm probability need.  The
+ * arguments are those of exo_keplerian_power_f64; the series are searched in groups that share every solve of Kepler's
+ * equation (the true anomaly depends on the epoch, the frequency and the candidate alone), in blocks of
+ * frequencies_per_block consecutive frequencies (0: the host chooses; the results do not depend on it).  Per series:
+ * max_power[n_series], the largest power over the grid -- bit for bit the largest entry of exo_keplerian_power_f64's row --,
+ * frequency_index[n_series] (int32) the lowest index at which it is reached, candidate[n_series] (int32) the winning
+ * candidate there.  A series without a finite power (NaN input, or n_frequency == 0): -inf, -1, -1.  workspace:
+ * exo_keplerian_max_workspace_bytes(n, n_series, n_frequency, frequencies_per_block) bytes (-1: invalid sizes), pure
+ * arithmetic; every slot of it that is read is written by a kernel first.  Nothing but kernels is enqueued, no atomics: the
+ * outputs are bitwise reproducible, and a row of a batch is bitwise the single call.  EXO_ERR_INVALID_ARGUMENT, before any
+ * launch: what exo_keplerian_power_f64 rejects, a null output, frequencies_per_block < 0.  EXO_ERR_WORKSPACE: workspace_bytes
+ * too small.  (Added without a new ABI number: no caller breaks.) */
+int64_t exo_keplerian_max_workspace_bytes(int64_t n, int64_t n_series, int64_t n_frequency, int32_t frequencies_per_block);
+int exo_keplerian_max_f64(const double* t, const double* y, const double* yerr, int64_t n_yerr, int64_t n, int64_t n_series,
+                          const int32_t* segment_offsets, int32_t n_instrument, const double* frequencies, int64_t n_frequency,
+                          const double* ecc, int32_t n_ecc, int32_t n_phase, int32_t frequencies_per_block, double* max_power,
+                          int32_t* frequency_index, int32_t* candidate, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------
  * The astrometric orbit search on the Thiele-Innes constants (exoplanet_amd/estimators.py: astrometric_power,
