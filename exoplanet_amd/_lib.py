@@ -234,6 +234,12 @@ _SIGNATURES = {
     "exo_column_quantiles_f64": (ctypes.c_int, [_c_dp, _i64, _i64, _i64, _c_dp, _c_dp, _i32, _c_dp, _c_dp, _c_dp]),
     # x, n_rows, n_cols, row_stride, n_tail_max, out_elpd, out_k, out_lppd, out_var, out_n_tail, stream
     "exo_column_psis_f64": (ctypes.c_int, [_c_dp, _i64, _i64, _i64, _i32, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp]),
+    # chol, center, in, out, n_row, n, mode, stream
+    "exo_metric_apply_f64": (ctypes.c_int, [_c_dp, _c_dp, _c_dp, _c_dp, _i64, _i32, _i32, _c_dp]),
+    # q, n_row, n, shift, sum1, sum2, count, stream
+    "exo_metric_accumulate_f64": (ctypes.c_int, [_c_dp, _i64, _i32, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp]),
+    # sum1, sum2, count, shift, n, cov, chol, center, status, stream
+    "exo_metric_update_f64": (ctypes.c_int, [_c_dp, _c_dp, _c_dp, _c_dp, _i32, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp]),
     "exo_sho_coefficients_f64": (ctypes.c_int, [_c_dp, _c_dp, _c_dp, _u32, ctypes.c_double, _i64, _c_dp, _c_dp, _c_dp]),
     "exo_sho_coefficients_vjp_f64": (ctypes.c_int, [_c_dp, _c_dp, _c_dp, _u32, ctypes.c_double, _i64, _c_dp, _c_dp, _c_dp,
                                                     _c_dp, _c_dp]),

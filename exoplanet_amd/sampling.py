@@ -26,13 +26,80 @@ import torch
 
 from .graph import GraphedStep
 
-__all__ = ["HMC", "NUTS", "Trace", "sample"]
+__all__ = ["HMC", "NUTS", "Trace", "sample", "adaptation_windows", "MAX_METRIC_N"]
+
+MAX_METRIC_N = 64                                        # EXO_METRIC_MAX_N of include/exoplanet_amd.h
+METRIC_FORWARD, METRIC_TRANSPOSED, METRIC_SOLVE = 0, 1, 2   # EXO_METRIC_FORWARD, _TRANSPOSED, _SOLVE
+
+
+def adaptation_windows(tune):
+    """Stan's warm-up schedule for a metric learnt in windows: [(start, end), ...], transitions start <= it < end of a warm-up
+    of ``tune`` feed window k, and the metric is replaced after transition end - 1.  ``tune >= 150``: an initial buffer of 75,
+    a final one of 50, windows of 25, 50, 100, ... in between, the last stretched to the final buffer when the next would not
+    fit (500: (75, 100) (100, 150) (150, 250) (250, 450)).  ``20 <= tune < 150``: buffers of 15 % and 10 %, one window."""
+    tune = int(tune)
+    if tune < 20:
+        raise ValueError("a metric adapted in windows needs tune >= 20")
+    if tune < 150:
+        return [(int(0.15 * tune), tune - int(0.1 * tune))]
+    start, width, stop, out = 75, 25, tune - 50, []
+    while start < stop:
+        end = start + width
+        if end + 2 * width > stop:
+            end = stop
+        out.append((start, end))
+        start, width = end, 2 * width
+    return out
+
+
+# ---- the dense metric, stated in torch: what runs for CPU tensors, and the definition the kernels of csrc/exo_metric.hip are held
+# to (tests/test_metric_host.py, tests/test_gpu_metric.py) ----------------------------------------------------------------------
+def _metric_apply_torch(chol, center, rows, mode):
+    """rows (D, n) through the metric: forward Q = c + X L^T, transposed GX = GQ L, solve X from L x = q - c"""
+    L = torch.tril(chol)
+    if mode == METRIC_FORWARD:
+        return center + rows @ L.T
+    if mode == METRIC_TRANSPOSED:
+        return rows @ L
+    return torch.linalg.solve_triangular(L, (rows - center).T, upper=False).T
+
+
+def _metric_accumulate_torch(q, shift, sum1, sum2, count):
+    """the rows of q (D, n) without a non-finite element, less ``shift``, into the window's sums (in place): first moments,
+    the lower triangle of the products, the number of rows"""
+    ok = torch.isfinite(q).all(1)
+    dq = torch.where(ok.unsqueeze(1), q - shift, torch.zeros_like(q))
+    sum1 += dq.sum(0)
+    sum2 += torch.tril(dq.T @ dq)
+    count += ok.sum()
+
+
+def _metric_update_torch(sum1, sum2, count, shift, cov, chol, center, shrink=True):
+    """the metric of the next window from the sums of this one: mean, sample covariance (divisor N - 1), Stan's shrinkage
+    made relative to each parameter's own variance, N / (N + 5) S + 1e-3 * 5 / (N + 5) diag(S), its Cholesky factor.  Writes cov, chol, center and returns 0; on a failure -- 1: fewer
+    than two rows, 2: a non-finite entry, 3: a pivot <= 0 -- writes nothing."""
+    N = float(count)
+    if N < 2:
+        return 1
+    m = shift + sum1 / N
+    full = torch.tril(sum2) + torch.tril(sum2, -1).T
+    S = (full - torch.outer(sum1, sum1) / N) / (N - 1.0)
+    Sigma = (N / (N + 5.0)) * S + 1e-3 * (5.0 / (N + 5.0)) * torch.diag(torch.diag(S)) if shrink else S
+    if not (bool(torch.isfinite(m).all()) and bool(torch.isfinite(Sigma).all())):
+        return 2
+    L, info = torch.linalg.cholesky_ex(Sigma)
+    if int(info) != 0:
+        return 3
+    if not bool(torch.isfinite(L).all()):
+        return 2
+    cov.copy_(Sigma); chol.copy_(L); center.copy_(m)
+    return 0
 
 
 class _ChainSampler:
     """what HMC and NUTS share: parameter / mass bookkeeping, one value + gradient evaluation of all chains, warm-up"""
 
-    def _setup(self, logp_fn, params, step_size, mass, generator):
+    def _setup(self, logp_fn, params, step_size, mass, generator, cov=None, center=None):
         self.params = [p.detach() for p in params]
         if not self.params or any(p.shape[0] != self.params[0].shape[0] for p in self.params):
             raise ValueError("params must be tensors with a common leading chain dimension")
@@ -48,6 +115,128 @@ class _ChainSampler:
         self.n_steps = 0
         self._shapes = [tuple(p.shape) for p in self.params]
         self._sizes = [int(p[0].numel()) for p in self.params]
+        # the dense metric (set_metric): covariance, its Cholesky factor and the centre, device tensors at fixed addresses
+        self.cov = self.chol = self.center = None
+        if cov is not None:
+            self._install_metric(cov, center)
+        elif center is not None:
+            raise ValueError("center comes with cov")
+
+    # ---- the dense metric: the sampler runs at unit masses in x, q = center + chol x ------------------------------------------
+    def _install_metric(self, cov, center):
+        """the host-side checks of a metric, then its values into the device tensors (allocated at the first call)"""
+        n = sum(self._sizes)
+        p0 = self.params[0]
+        if any(bool((m != 1).any()) for m in self.mass):
+            raise ValueError("a dense metric (cov) replaces the masses: it cannot be combined with a non-unit mass")
+        if n > MAX_METRIC_N:
+            raise ValueError(f"a dense metric takes at most {MAX_METRIC_N} parameters per chain (MAX_METRIC_N), got {n}")
+        C = torch.as_tensor(cov).detach().to(device="cpu", dtype=torch.float64)
+        if tuple(C.shape) != (n, n):
+            raise ValueError(f"cov must be ({n}, {n}), got {tuple(C.shape)}")
+        if not bool(torch.isfinite(C).all()) or float((C - C.T).abs().max()) > 1e-12 * float(C.abs().max()):
+            raise ValueError("cov must be finite and symmetric")
+        L, info = torch.linalg.cholesky_ex(C)
+        if int(info) != 0 or not bool(torch.isfinite(L).all()):
+            raise ValueError("cov must be symmetric positive definite")
+        if center is None:
+            c = torch.zeros(n, dtype=torch.float64) if self.center is None else None
+        else:
+            c = torch.as_tensor(center).detach().to(device="cpu", dtype=torch.float64).reshape(-1)
+            if tuple(c.shape) != (n,) or not bool(torch.isfinite(c).all()):
+                raise ValueError(f"center must be {n} finite numbers")
+        if self.cov is None:
+            if p0.is_cuda and p0.dtype != torch.float64:
+                raise TypeError("a dense metric on the device needs float64 parameters")
+            new = lambda *shape, dtype=p0.dtype: torch.zeros(shape, dtype=dtype, device=p0.device)  # noqa: E731
+            self.cov, self.chol, self.center = new(n, n), new(n, n), new(n)
+            # positions and gradient in q around the likelihood call; the sums of a warm-up window, their shift, the update's word
+            self._Q, self._GQ = new(self.D, n), new(self.D, n)
+            self._sum1, self._sum2, self._shift = new(n), new(n, n), new(n)
+            self._count = new(1, dtype=torch.int64)
+            self.metric_status = new(1, dtype=torch.int32)
+        self.cov.copy_(C)
+        self.chol.copy_(L)
+        if c is not None:
+            self.center.copy_(c)
+
+    def set_metric(self, cov, center=None):
+        """A dense metric: ``cov`` (n, n), symmetric positive definite over the flat parameters of a chain (all blocks side by
+        side, n <= MAX_METRIC_N), and ``center`` (n; default: the present one, zero at first).  HMC / NUTS with the mass matrix
+        cov^-1 is run as HMC / NUTS at unit masses in x, q = center + L x, cov = L L^T.  The checks -- shape, symmetry, a
+        Cholesky factorisation -- are made here, on the host.  ``cov``, ``chol`` and ``center`` are device tensors at fixed
+        addresses, updated in place: captured graphs read the new metric without re-capture (a sampler built without a
+        metric captures once more at its first one)."""
+        first = self.cov is None
+        self._install_metric(cov, center)
+        self._metric_changed()
+        if first:
+            self._capture()
+
+    def _metric_changed(self):
+        """(whatever a sampler caches in x is void)"""
+
+    def _metric_apply(self, mode, rows, out=None):
+        rows = rows.contiguous()
+        out = torch.empty_like(rows) if out is None else out
+        if rows.is_cuda:
+            from . import _lib
+
+            if not out.is_contiguous() or out.shape != rows.shape or rows.shape[1] != self.chol.shape[0]:
+                raise ValueError("the metric maps contiguous (D, n) rows")
+            with torch.cuda.device(rows.device):
+                _lib.check(_lib.load().exo_metric_apply_f64(self.chol.data_ptr(), self.center.data_ptr(), rows.data_ptr(),
+                                                            out.data_ptr(), int(rows.shape[0]), int(rows.shape[1]), mode,
+                                                            torch.cuda.current_stream(rows.device).cuda_stream),
+                           "exo_metric_apply_f64")
+            return out
+        return out.copy_(_metric_apply_torch(self.chol, self.center, rows, mode))
+
+    def _to_x(self, q):
+        """the flat positions as the sampler integrates them"""
+        return q if self.cov is None else self._metric_apply(METRIC_SOLVE, q)
+
+    def _vg(self, x, grad_out=None):
+        """log-density and gradient as functions of what the sampler integrates: of q itself without a metric; with one,
+        Q = c + X L^T before the likelihood and G_x = G_q L after it"""
+        if self.cov is None:
+            return self._value_and_grad_flat(x, grad_out=grad_out)
+        lp, gq = self._value_and_grad_flat(self._metric_apply(METRIC_FORWARD, x, self._Q), grad_out=self._GQ)
+        return lp, self._metric_apply(METRIC_TRANSPOSED, gq, grad_out)
+
+    def _window_accumulate(self):
+        q = self._flat(self.params).contiguous()
+        if q.is_cuda:
+            from . import _lib
+
+            with torch.cuda.device(q.device):
+                _lib.check(_lib.load().exo_metric_accumulate_f64(q.data_ptr(), int(q.shape[0]), int(q.shape[1]), self._shift.data_ptr(),
+                                                                 self._sum1.data_ptr(), self._sum2.data_ptr(),
+                                                                 self._count.data_ptr(),
+                                                                 torch.cuda.current_stream(q.device).cuda_stream),
+                           "exo_metric_accumulate_f64")
+        else:
+            _metric_accumulate_torch(q, self._shift, self._sum1, self._sum2, self._count)
+
+    def _window_update(self):
+        """a window ends: the metric from its sums (a failed update leaves the previous one in force; ``metric_status`` says
+        so), the sums cleared, the next window's shift the new centre"""
+        if self.cov.is_cuda:
+            from . import _lib
+
+            with torch.cuda.device(self.cov.device):
+                _lib.check(_lib.load().exo_metric_update_f64(self._sum1.data_ptr(), self._sum2.data_ptr(), self._count.data_ptr(),
+                                                             self._shift.data_ptr(), int(self.center.shape[0]),
+                                                             self.cov.data_ptr(), self.chol.data_ptr(), self.center.data_ptr(),
+                                                             self.metric_status.data_ptr(),
+                                                             torch.cuda.current_stream(self.cov.device).cuda_stream),
+                           "exo_metric_update_f64")
+        else:
+            self.metric_status.fill_(_metric_update_torch(self._sum1, self._sum2, self._count, self._shift, self.cov, self.chol,
+                                                          self.center))
+        self._sum1.zero_(); self._sum2.zero_(); self._count.zero_()
+        self._shift.copy_(self.center)
+        self._metric_changed()
 
     # one value + gradient evaluation of all chains
     def _value_and_grad(self, q):
@@ -95,8 +284,25 @@ class _ChainSampler:
         """``n_steps`` transitions that adapt, per chain, the step size to the acceptance statistic ``target_accept``
         by dual averaging; afterwards the averaged step sizes are kept.  ``adapt_mass``: half way through, the
         diagonal masses become 1 / variance of every parameter element, pooled over chains and the draws so far (the
-        chains of a batch target one posterior), and the step-size adaptation restarts.  Nothing here synchronises
-        with the host (beyond what ``step`` does); statistics of the sampling phase start after the warm-up."""
+        chains of a batch target one posterior), and the step-size adaptation restarts.  ``adapt_mass="dense"``: a dense
+        metric (`set_metric`) learnt in the windows of `adaptation_windows`: inside a window every transition's positions of
+        all chains enter the window's sums; at its end the pooled covariance, shrunk towards its own diagonal with Stan's weights, and the pooled mean
+        become the metric and its centre, the step sizes become the averaged ones and their adaptation restarts.  Nothing here
+        synchronises with the host (beyond what ``step`` does); statistics of the sampling phase start after the warm-up."""
+        dense = isinstance(adapt_mass, str)
+        if dense and adapt_mass != "dense":
+            raise ValueError('adapt_mass is False, True (diagonal) or "dense"')
+        windows = adaptation_windows(n_steps) if dense else []
+        if dense:
+            if self.cov is None:
+                # the identity about the finite starting points' mean: the first window's shift
+                q = self._flat(self.params)
+                ok = torch.isfinite(q).all(1)
+                c = torch.where(ok.unsqueeze(1), q, torch.zeros_like(q)).sum(0) / torch.clamp(ok.sum(), min=1)
+                self.set_metric(torch.eye(q.shape[1], dtype=torch.float64), center=c)
+            self._sum1.zero_(); self._sum2.zero_(); self._count.zero_()
+            self._shift.copy_(self.center)
+            adapt_mass = False
         def restart():
             mu = torch.log(10.0 * self.eps)
             return mu, torch.zeros_like(self.eps), torch.zeros_like(self.eps)   # mu, Hbar, log eps_bar
@@ -131,6 +337,14 @@ class _ChainSampler:
                 self.eps.copy_(torch.exp(log_eps_bar))
                 mu, Hbar, log_eps_bar = restart()
                 m = 0
+            if windows and windows[0][0] <= it:
+                self._window_accumulate()
+                if it + 1 == windows[0][1]:
+                    windows.pop(0)
+                    self._window_update()
+                    self.eps.copy_(torch.exp(log_eps_bar))
+                    mu, Hbar, log_eps_bar = restart()
+                    m = 0
         self.eps.copy_(torch.exp(log_eps_bar))
         self._reset_statistics()
         return self.eps
@@ -151,22 +365,26 @@ class HMC(_ChainSampler):
     instead) and ``last_diverged`` (the proposal's energy error is not finite or beyond 1000).
     """
 
-    def __init__(self, logp_fn, params, step_size, n_leapfrog, mass=None, graph=True, generator=None):
+    def __init__(self, logp_fn, params, step_size, n_leapfrog, mass=None, graph=True, generator=None, cov=None, center=None):
         self.L = int(n_leapfrog)
         if self.L < 1 or not float(step_size) > 0:
             raise ValueError("need step_size > 0 and n_leapfrog >= 1")
-        self._setup(logp_fn, params, step_size, mass, generator)
+        self._setup(logp_fn, params, step_size, mass, generator, cov, center)
         self.n_accept = torch.zeros(self.D, dtype=torch.float64, device=self.params[0].device)
         self._mflat = self._flat(self.mass)
+        self._use_graph = graph
+        self._capture()
+
+    def _capture(self):
         self._graph = None
-        if graph and self.params[0].is_cuda:
+        if self._use_graph and self.params[0].is_cuda:
             # static inputs: positions, momenta (flat); static outputs: proposal, its momenta, both log-densities
             q0 = self._flat(self.params)
             self._graph = GraphedStep(self._trajectory, q0, torch.zeros_like(q0))
 
     def _trajectory(self, q, p):
-        """leapfrog on the flat (D, n) arrays: (q, p) -> (q', p', logp(q), logp(q'))"""
-        lp0, g = self._value_and_grad_flat(q)
+        """leapfrog on the flat (D, n) arrays: (q, p) -> (q', p', logp(q), logp(q')); under a dense metric q is x"""
+        lp0, g = self._vg(q)
         lp = lp0
         e = self.eps.unsqueeze(1)
         eh, em = 0.5 * e, e / self._mflat
@@ -175,7 +393,7 @@ class HMC(_ChainSampler):
         p = torch.addcmul(p, eh, g)
         for i in range(self.L):
             q = torch.addcmul(q, em, p)
-            lp, g = self._value_and_grad_flat(q)
+            lp, g = self._vg(q)
             p = torch.addcmul(p, e if i + 1 < self.L else eh, g)
         return q, p, lp0, lp
 
@@ -184,7 +402,10 @@ class HMC(_ChainSampler):
         self._mflat.copy_(self._flat(self.mass))          # (warm-up may have changed the masses; the captured graph reads this)
         q0 = self._flat(self.params)
         p0 = torch.randn(q0.shape, dtype=q0.dtype, device=q0.device, generator=self.generator) * torch.sqrt(self._mflat)
-        q1, p1, lp0, lp1 = self._graph(q0, p0) if self._graph is not None else self._trajectory(q0, p0)
+        x0 = self._to_x(q0)
+        q1, p1, lp0, lp1 = self._graph(x0, p0) if self._graph is not None else self._trajectory(x0, p0)
+        if self.cov is not None:
+            q1 = self._metric_apply(METRIC_FORWARD, q1)    # (a rejected chain keeps q0 itself, bit for bit, below)
         kin = lambda p: (0.5 * p * p / self._mflat).sum(1)  # noqa: E731
         k0 = kin(p0)
         dH = (lp1 - kin(p1)) - (lp0 - k0)                                # -(H1 - H0)
@@ -244,11 +465,11 @@ class NUTS(_ChainSampler):
     """
 
     def __init__(self, logp_fn, params, step_size, max_depth=8, mass=None, graph=True, generator=None,
-                 max_energy_error=1000.0):
+                 max_energy_error=1000.0, cov=None, center=None):
         self.max_depth = int(max_depth)
         if self.max_depth < 1:
             raise ValueError("need max_depth >= 1")
-        self._setup(logp_fn, params, step_size, mass, generator)
+        self._setup(logp_fn, params, step_size, mass, generator, cov, center)
         self.max_energy_error = float(max_energy_error)
         dev = self.params[0].device
         self.n_divergent = torch.zeros(self.D, dtype=torch.float64, device=dev)
@@ -288,9 +509,16 @@ class NUTS(_ChainSampler):
             ptrs = [self._mflat.data_ptr() if k is None else (self.eps.data_ptr() if k == "eps_abs" else st[k].data_ptr())
                     for k in order]
             self._native = ((ctypes.c_void_p * len(ptrs))(*ptrs), int(q.shape[1]), S)
+        self._use_graph = graph
+        self._capture()
+
+    def _capture(self):
         self._graph = None
-        if graph and self.params[0].is_cuda:
+        if self._use_graph and self.params[0].is_cuda:
             self._graph = GraphedStep(lambda *a: self._leaf_update(), *[v for v in self._st.values()])
+
+    def _metric_changed(self):
+        self._lp = self._g = None          # (the cached gradient is the one with respect to x of the previous metric)
 
     def _phase(self, phase):
         from . import _lib
@@ -306,7 +534,7 @@ class NUTS(_ChainSampler):
         e = eps.unsqueeze(1)
         p = p + 0.5 * e * g
         q = q + e * p / self._mflat
-        lp, g = self._value_and_grad_flat(q)
+        lp, g = self._vg(q)
         p = p + 0.5 * e * g
         return q, p, g, lp
 
@@ -339,7 +567,7 @@ class NUTS(_ChainSampler):
         st = self._st
         if self._native is not None:
             self._phase(0)
-            lp, _ = self._value_and_grad_flat(st["qn"], grad_out=st["gn"])     # (the gradient lands in the leaf's buffer)
+            lp, _ = self._vg(st["qn"], grad_out=st["gn"])     # (the gradient lands in the leaf's buffer)
             st["lpn"].copy_(lp)
             self._phase(1)
             return st["on"]
@@ -407,9 +635,10 @@ class NUTS(_ChainSampler):
     def step(self):
         st = self._st
         self._mflat.copy_(self._flat(self.mass))         # (warm-up may have changed the masses; captured graphs read this)
-        q0 = self._flat(self.params)
+        q_start = self._flat(self.params)
+        q0 = self._to_x(q_start)                          # (under a dense metric the tree is built in x)
         if self._lp is None:
-            self._lp, self._g = self._value_and_grad_flat(q0)
+            self._lp, self._g = self._vg(q0)
         lp0, g0 = self._lp, self._g
         p0 = torch.randn(q0.shape, dtype=q0.dtype, device=q0.device, generator=self.generator) * torch.sqrt(self._mflat)
         H0 = -lp0 + (0.5 * p0 * p0 / self._mflat).sum(1)
@@ -432,7 +661,13 @@ class NUTS(_ChainSampler):
             self._merge()
             if j + 1 < self.max_depth and not bool(st["active"].any()):   # (the one host synchronisation per doubling)
                 break
-        for x, y in zip(self.params, self._parts(st["propq"])):
+        qnew = st["propq"]
+        if self.cov is not None:
+            # back to q; a chain that did not move -- outside the support, at a wall -- keeps its position bit for bit
+            bits = torch.int64 if q0.element_size() == 8 else torch.int32
+            moved = (st["propq"].view(bits) != q0.view(bits)).any(1, keepdim=True)
+            qnew = torch.where(moved, self._metric_apply(METRIC_FORWARD, st["propq"]), q_start)
+        for x, y in zip(self.params, self._parts(qnew)):
             x.copy_(y)
         self._lp, self._g = st["proplp"].clone(), st["propg"].clone()
         self.n_steps += 1
@@ -461,11 +696,13 @@ class Trace:
     """What `sample` returns.  ``draws`` (n_draws, chains, n): the unconstrained flat array -- all parameter blocks of a chain
     side by side, as the samplers hold them -- on the sampler's device; ``stats``: {"logp", "energy", "accept_prob",
     "diverging" and "depth" (NUTS) / "accepted" (HMC)}, each (n_draws, chains); ``eps`` (chains,) and ``mass`` (one tensor per
-    parameter block): the step sizes and masses at the end of the warm-up; ``n_tune``; ``sampler`` ("hmc" / "nuts").
+    parameter block): the step sizes and masses at the end of the warm-up; ``cov`` (n, n) and ``center`` (n): the dense metric
+    the draws were made with, both None for a diagonal run; ``n_tune``; ``sampler`` ("hmc" / "nuts").
     Plain tensors: no xarray, no pandas.  `diagnostics.summary` takes a trace as it is."""
 
-    def __init__(self, draws, stats, eps, mass, n_tune, sampler):
+    def __init__(self, draws, stats, eps, mass, n_tune, sampler, cov=None, center=None):
         self.draws, self.stats, self.eps, self.mass, self.n_tune, self.sampler = draws, stats, eps, mass, n_tune, sampler
+        self.cov, self.center = cov, center
 
     def __len__(self):
         return int(self.draws.shape[0])
@@ -484,7 +721,8 @@ class Trace:
 @torch.no_grad()
 def sample(sampler, draws=1000, tune=0, target_accept=0.8, adapt_mass=False):
     """``draws`` transitions of an `HMC` or `NUTS` sampler, kept: a `Trace`.  ``tune > 0`` runs the sampler's own
-    ``warmup(tune, target_accept=..., adapt_mass=...)`` first.  The draws and the per-draw statistics go into arrays
+    ``warmup(tune, target_accept=..., adapt_mass=...)`` first (``adapt_mass="dense"``: a dense metric learnt in windows, kept
+    in ``trace.cov`` / ``trace.center``).  The draws and the per-draw statistics go into arrays
     allocated once, before the loop; the loop calls ``step()`` and copies device to device -- it reads nothing on the host
     (NUTS's one look per doubling is the sampler's own) and takes no random numbers: the chain is, bit for bit, the one
     that as many plain ``step()`` calls produce from the same generator state."""
@@ -511,4 +749,6 @@ def sample(sampler, draws=1000, tune=0, target_accept=0.8, adapt_mass=False):
         stats["accept_prob"][i].copy_(sampler.last_accept_prob)
         stats["diverging"][i].copy_(sampler.last_diverged)
         stats["depth" if nuts else "accepted"][i].copy_(ret)
-    return Trace(out, stats, sampler.eps.clone(), [m.clone() for m in sampler.mass], tune, "nuts" if nuts else "hmc")
+    dense = sampler.cov is not None
+    return Trace(out, stats, sampler.eps.clone(), [m.clone() for m in sampler.mass], tune, "nuts" if nuts else "hmc",
+                 cov=sampler.cov.clone() if dense else None, center=sampler.center.clone() if dense else None)

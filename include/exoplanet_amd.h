@@ -58,7 +58,8 @@ extern "C" {
  *     exo_timing_windows_f64, exo_transit_timing_f64, EXO_TIMING_*; exo_running_trend_f64, EXO_TREND_MAX_WINDOW;
  *     exo_keplerian_workspace_bytes, exo_keplerian_power_f64, EXO_KEP_*; exo_astrometric_workspace_bytes,
  *     exo_astrometric_power_f64, EXO_AST_NCOEF; exo_column_quantiles_f64, EXO_QUANTILE_MAX_Q;
- *     exo_column_psis_f64, EXO_PSIS_MAX_TAIL; exo_keplerian_max_workspace_bytes, exo_keplerian_max_f64.) */
+ *     exo_column_psis_f64, EXO_PSIS_MAX_TAIL; exo_keplerian_max_workspace_bytes, exo_keplerian_max_f64;
+ *     exo_metric_apply_f64, exo_metric_accumulate_f64, exo_metric_update_f64, EXO_METRIC_*.) */
 #define EXO_ABI_VERSION 21
 int32_t exo_abi_version(void);
 
@@ -1338,6 +1339,43 @@ int exo_column_quantiles_f64(const double* x, int64_t n_rows, int64_t n_cols, in
 #define EXO_PSIS_MAX_TAIL 1024
 int exo_column_psis_f64(const double* x, int64_t n_rows, int64_t n_cols, int64_t row_stride, int32_t n_tail_max, double* out_elpd,
                         double* out_k, double* out_lppd, double* out_var, int32_t* out_n_tail, void* stream);
+
+/* -------------------------------------------------------------------------
+ * The dense metric of HMC / NUTS (exoplanet_amd/sampling.py, set_metric and adapt_mass="dense"): a
+ * covariance Sigma = L L^T, L lower triangular, and a centre c; the samplers run at unit masses in x, q = c + L x.
+ * chol: row-major (n, n), only the lower triangle is read; n <= EXO_METRIC_MAX_N.  Rows are contiguous, (n_row, n).  Every sum
+ * has the one order stated here and no product is fused with an addition, so a result is bitwise reproducible and bitwise
+ * that of the host build of csrc/exo_metric_core.hpp.  No atomics, no workspace, no host synchronisation; capturable.
+ *
+ * exo_metric_apply_f64, per row, `out` may be `in`:
+ *   EXO_METRIC_FORWARD     out_i = c_i + sum_{j <= i} L_ij in_j, the sum from its first product on, j ascending, c_i last;
+ *   EXO_METRIC_TRANSPOSED  out_j = sum_{i >= j} in_i L_ij, i ascending (center is not read and may be null);
+ *   EXO_METRIC_SOLVE       L out = in - c by forward substitution: ((in_i - c_i) - L_i0 out_0 - ...) / L_ii, j ascending.
+ * exo_metric_accumulate_f64: with dq = q - shift, row d ascending, every row whose n elements are all finite adds dq_i into
+ *   sum1[i] and dq_i dq_j into sum2[i * n + j], j <= i (the upper triangle is not touched), each running sum taking the rows
+ *   in their order; the number of rows kept is added to *count.
+ * exo_metric_update_f64, one workgroup: N = *count; m_i = shift_i + sum1_i / N; S_ij = (sum2_ij - sum1_i sum1_j / N) / (N - 1);
+ *   Sigma = N / (N + 5) S + 1e-3 (5 / (N + 5)) diag(S) (Stan's shrinkage, relative to each variance); the Cholesky factor, entry (i, j) = Sigma_ij less
+ *   L_ik L_jk for k ascending, divided by L_jj off the diagonal, the square root on it.  On success cov (symmetric), chol
+ *   (upper part zero) and center = m are written and *status = EXO_METRIC_STATUS_OK.  N < 2 (TOO_FEW), a non-finite m, Sigma
+ *   or pivot (NOT_FINITE), a pivot <= 0 (NOT_POSITIVE): NOTHING but *status is written -- the previous metric stays in force.
+ * EXO_ERR_INVALID_ARGUMENT, before any launch: negative sizes, n outside 1 .. EXO_METRIC_MAX_N, an unknown mode, a null
+ * pointer.  n_row == 0: EXO_OK, nothing launched (sizes are checked first).  (Added without a new ABI number: no caller breaks.)
+ * ------------------------------------------------------------------------- */
+#define EXO_METRIC_MAX_N 64
+#define EXO_METRIC_FORWARD 0
+#define EXO_METRIC_TRANSPOSED 1
+#define EXO_METRIC_SOLVE 2
+#define EXO_METRIC_STATUS_OK 0
+#define EXO_METRIC_STATUS_TOO_FEW 1
+#define EXO_METRIC_STATUS_NOT_FINITE 2
+#define EXO_METRIC_STATUS_NOT_POSITIVE 3
+int exo_metric_apply_f64(const double* chol, const double* center, const double* in, double* out, int64_t n_row, int32_t n,
+                         int32_t mode, void* stream);
+int exo_metric_accumulate_f64(const double* q, int64_t n_row, int32_t n, const double* shift, double* sum1, double* sum2,
+                              int64_t* count, void* stream);
+int exo_metric_update_f64(const double* sum1, const double* sum2, const int64_t* count, const double* shift, int32_t n,
+                          double* cov, double* chol, double* center, int32_t* status, void* stream);
 
 #ifdef __cplusplus
 }
