@@ -10,5 +10,6 @@ from .orbits import KeplerianOrbit  # noqa: F401
 from .graph import GraphedStep  # noqa: F401
 from .sampling import HMC, NUTS, Trace, sample  # noqa: F401
 from .optimize import LBFGS, optimize  # noqa: F401  (xo.optimize is the function; the module: `from exoplanet_amd.optimize import ...`)
+from .laplace import Laplace, laplace  # noqa: F401  (xo.laplace is the function, as xo.optimize is)
 
 __version__ = "0.1.0"

@@ -240,6 +240,12 @@ _SIGNATURES = {
     "exo_metric_accumulate_f64": (ctypes.c_int, [_c_dp, _i64, _i32, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp]),
     # sum1, sum2, count, shift, n, cov, chol, center, status, stream
     "exo_metric_update_f64": (ctypes.c_int, [_c_dp, _c_dp, _c_dp, _c_dp, _i32, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp]),
+    # x, n_chain, n, free_index, m, scale, scale_per_chain, hess, delta, order, points, dx, stream
+    "exo_laplace_points_f64": (ctypes.c_int, [_c_dp, _i64, _i32, _c_dp, _i32, _c_dp, _i32, _c_dp, ctypes.c_double, _i32, _c_dp,
+                                              _c_dp, _c_dp]),
+    # grad, dx, logp, n_chain, n, free_index, m, order, hess, cov, sd, logdet, log_evidence, asymmetry, fd_error, status, stream
+    "exo_laplace_factor_f64": (ctypes.c_int, [_c_dp, _c_dp, _c_dp, _i64, _i32, _c_dp, _i32, _i32, _c_dp, _c_dp, _c_dp, _c_dp,
+                                              _c_dp, _c_dp, _c_dp, _c_dp, _c_dp]),
     "exo_sho_coefficients_f64": (ctypes.c_int, [_c_dp, _c_dp, _c_dp, _u32, ctypes.c_double, _i64, _c_dp, _c_dp, _c_dp]),
     "exo_sho_coefficients_vjp_f64": (ctypes.c_int, [_c_dp, _c_dp, _c_dp, _u32, ctypes.c_double, _i64, _c_dp, _c_dp, _c_dp,
                                                     _c_dp, _c_dp]),

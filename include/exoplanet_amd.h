@@ -59,7 +59,8 @@ extern "C" {
  *     exo_keplerian_workspace_bytes, exo_keplerian_power_f64, EXO_KEP_*; exo_astrometric_workspace_bytes,
  *     exo_astrometric_power_f64, EXO_AST_NCOEF; exo_column_quantiles_f64, EXO_QUANTILE_MAX_Q;
  *     exo_column_psis_f64, EXO_PSIS_MAX_TAIL; exo_keplerian_max_workspace_bytes, exo_keplerian_max_f64;
- *     exo_metric_apply_f64, exo_metric_accumulate_f64, exo_metric_update_f64, EXO_METRIC_*.) */
+ *     exo_metric_apply_f64, exo_metric_accumulate_f64, exo_metric_update_f64, EXO_METRIC_*;
+ *     exo_laplace_points_f64, exo_laplace_factor_f64, EXO_LAPLACE_*.) */
 #define EXO_ABI_VERSION 21
 int32_t exo_abi_version(void);
 
@@ -1376,6 +1377,41 @@ int exo_metric_accumulate_f64(const double* q, int64_t n_row, int32_t n, const d
                               int64_t* count, void* stream);
 int exo_metric_update_f64(const double* sum1, const double* sum2, const int64_t* count, const double* shift, int32_t n,
                           double* cov, double* chol, double* center, int32_t* status, void* stream);
+
+/* -------------------------------------------------------------------------
+ * The Laplace approximation at the chains' modes (exoplanet_amd/laplace.py; the definition is
+ * tests/laplace_oracle.py): the Hessian of f = -logp by central differences of the batched gradient, and from it, per chain,
+ * the covariance H^-1 and the Laplace log-evidence.  x: (n_chain, n) positions; free_index: m ascending int32 indices into a
+ * row, on the device, the same for every chain; order: 2 or 4; n and m at most EXO_LAPLACE_MAX_N.  Every sum has one stated
+ * order and no product is fused with an addition, so a result is bitwise reproducible and bitwise that of the host build of
+ * csrc/exo_laplace_core.hpp.  No atomics, no workspace, no host synchronisation; capturable.
+ *
+ * exo_laplace_points_f64: points (n_chain, order m, n), dx (n_chain, order m).  Row r = s m + k is x with coordinate
+ *   free_index[k] moved by +h_k (s = 0), -h_k (1), +2 h_k (2), -2 h_k (3); dx[r] is the REALISED offset fl(fl(x + off) - x).
+ *   h_k = eps^(1/3) scale_k, scale (n), or (n_chain, n) with scale_per_chain != 0, or null: max(|x|, 1); with hess (n_chain, m,
+ *   m; a previous pass's) h_k = delta / sqrt(hess_kk) where that and hess_kk are finite and positive.
+ * exo_laplace_factor_f64, one wave per chain: grad (n_chain, order m, n), the gradient of logp at the points.
+ *   A1_ik = -(g_{k}[F_i] - g_{m+k}[F_i]) / (dx_k - dx_{m+k}), A2 from the rows 2m + k, 3m + k; A = A1 (order 2) or
+ *   (4 A1 - A2) / 3; hess = (A + A^T) / 2 (n_chain, m, m); asymmetry = max_{i>k} |A_ik - A_ki| / sqrt(|H_ii H_kk|); fd_error =
+ *   max_{i>=k} |H1_ik - H2_ik| / sqrt(|H_ii H_kk|) (NaN at order 2).  s_i = 1 / sqrt(H_ii), C = S H S with a unit diagonal
+ *   = R R^T; logdet = sum log H_ii + 2 sum log R_ii; cov = S (R^-1)^T R^-1 S (n_chain, m, m), sd_i = sqrt(cov_ii);
+ *   log_evidence = logp + (m / 2) log(2 pi) - logdet / 2.  status: EXO_LAPLACE_STATUS_NOT_FINITE -- a non-finite offset or free
+ *   gradient entry, dx_+ - dx_- == 0, a non-finite H_ii --, EXO_LAPLACE_STATUS_NOT_POSITIVE -- an H_ii <= 0 or a pivot of C at
+ *   or below m eps --: hess, asymmetry and fd_error are written, everything else of that chain is NaN.
+ * EXO_ERR_INVALID_ARGUMENT, before any launch: n_chain < 0, m < 1, m > n, n or m above EXO_LAPLACE_MAX_N, order outside
+ * {2, 4}, hess with delta <= 0, a null pointer (scale and hess may be null).  n_chain == 0: EXO_OK, nothing launched (sizes
+ * are checked first).  (Added without a new ABI number: no caller breaks.)
+ * ------------------------------------------------------------------------- */
+#define EXO_LAPLACE_MAX_N 64
+#define EXO_LAPLACE_STATUS_OK 0
+#define EXO_LAPLACE_STATUS_NOT_FINITE 1
+#define EXO_LAPLACE_STATUS_NOT_POSITIVE 2
+int exo_laplace_points_f64(const double* x, int64_t n_chain, int32_t n, const int32_t* free_index, int32_t m, const double* scale,
+                           int32_t scale_per_chain, const double* hess, double delta, int32_t order, double* points, double* dx,
+                           void* stream);
+int exo_laplace_factor_f64(const double* grad, const double* dx, const double* logp, int64_t n_chain, int32_t n,
+                           const int32_t* free_index, int32_t m, int32_t order, double* hess, double* cov, double* sd, double* logdet,
+                           double* log_evidence, double* asymmetry, double* fd_error, int32_t* status, void* stream);
 
 #ifdef __cplusplus
 }
